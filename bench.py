@@ -10,6 +10,11 @@ weight cast, patch embed, 12 transformer layers, head, cross-entropy, full backw
 parameter gradient and (N > 1) the bucketed RCCL gradient all-reduce, overlapped with backward.
 Inputs are resident in HBM before timing.  The optimiser step is outside the metric.
 Weak scaling: 256 images per GPU at every N.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, print the line.
+--full adds the side measurements (TiTok-S / ViT-VQGAN-B `also`, the GEMM `roofline`, the CPU-oracle
+`cpu_baseline`; each can still be dropped with its --no-* option).  --dump-outputs DIR writes what the
+last timed step computed (loss, logits, a fixed sample of every parameter gradient) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -332,15 +337,39 @@ def spawn_ranks(n, script, script_args, env=None, capture=False):
     return subprocess.run(cmd, env=e).returncode
 
 
+GRAD_SAMPLE = 65536        # --dump-outputs: gradients larger than this are written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """What the timed path hands its caller after the last timed step, as float32 .npy files: loss.npy, logits.npy and grad.<parameter>.npy
+    (the whole gradient, or for a larger one the elements at GRAD_SAMPLE sorted indices drawn from a generator seeded per parameter, so that
+    two builds sample the same elements).  About 12 MB in all at the headline config."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1), "logits": logits.detach().float()}
+    for i, (name, p) in enumerate(model.named_parameters()):
+        g = p.grad.detach().float().reshape(-1)
+        if g.numel() > GRAD_SAMPLE:
+            idx = torch.randperm(g.numel(), generator=torch.Generator(device="cpu").manual_seed(i))[:GRAD_SAMPLE].sort().values
+            g = g[idx.to(g.device)]
+        arrays["grad." + name] = g
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the TiTok-S / ViT-VQGAN-B side measurements")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements (also, roofline, cpu_baseline) after the headline timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, logits and sampled gradients to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the GEMM roofline timings")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the TiTok-S / ViT-VQGAN-B side measurements")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this parent only launches the N ranks (no GPU call happens in it) and exits with their code
@@ -391,7 +420,8 @@ def main():
     def step(timed=False):
         model.zero_grad(set_to_none=True)
         WEIGHTS.clear()                      # weights are re-cast to bf16 every step, as in training
-        loss = torch.nn.functional.cross_entropy(net(images), labels)
+        logits = net(images)
+        loss = torch.nn.functional.cross_entropy(logits, labels)
         loss.backward()
         if world > 1:
             if timed:
@@ -401,7 +431,7 @@ def main():
             if timed:
                 e1.record()
                 finish_events.append((e0, e1))
-        return loss
+        return loss, logits
 
     for _ in range(args.warmup):
         step()
@@ -410,7 +440,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step(timed=True)
+        loss, logits = step(timed=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -426,6 +456,9 @@ def main():
     if world > 1:
         wait_ms = sum(a.elapsed_time(b) for a, b in finish_events) / max(1, len(finish_events))
         dist_info = gather_dist_info(dev.index, own_ms, wait_ms, net.diagnostics())
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, logits, model)
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -445,17 +478,17 @@ def main():
             out["device"] = box_identity(dev)
         except Exception as e:                 # noqa: BLE001
             out["device"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_also:
+        if args.full and world == 1 and not args.no_also:
             try:
                 out["also"] = also_models(dev)
             except Exception as e:             # noqa: BLE001
                 out["also"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 out["roofline"] = kernel_roofline(dev)
             except Exception as e:             # noqa: BLE001
                 out["roofline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:             # noqa: BLE001

@@ -17,5 +17,5 @@ find $O/prof_ss -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/final_
 rm -rf $O/prof $O/prof_ss $O/pmc_mfma $O/pmc_hbm
 # the bench line last, against THIS pass's counters (bench.py reads profiles/r04/final_pmc_*: refresh the box's copy first)
 cp $O/final_pmc_mfma.json $O/final_pmc_hbm_traffic.json $O/final_pmc_meta.json $R/profiles/r04/
-python3 $R/bench.py --steps 10 --warmup 3 > $O/bench.log 2>&1
+python3 $R/bench.py --steps 10 --warmup 3 --full > $O/bench.log 2>&1
 tail -1 $O/bench.log | cut -c1-160
