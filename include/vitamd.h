@@ -1,4 +1,5 @@
-/* vitamd.h — C ABI of libvitamd.so, the MI355X (gfx950) kernels behind the ViT training hot path.
+/* vitamd.h — C ABI of libvitamd.so, the MI355X (gfx950) kernels behind the ViT training hot path
+ * (and the KV-cached decoding of the causal stack).
  *
  * The reference (SnakeOnex/vit-is-all-you-need) has no FFI layer: its hot path is a handful of
  * PyTorch ATen calls made from transformer.py and train_vit.py.  Each entry point below replaces
@@ -31,7 +32,7 @@ extern "C" {
 #define VITAMD_ERR_LAUNCH 3  /* HIP reported a launch error */
 #define VITAMD_ERR_INIT 4    /* vitamd_init has not run for the current device (GELU epilogues need its table) */
 
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header (bumped on any signature change): 9 (the KV-cached decoding entry points). */
 int vitamd_abi_version(void);
 
 /* Per-device set-up, once per device and process (idempotent; device < 0 = the current device; never inside a stream capture): builds the
@@ -149,6 +150,38 @@ int vitamd_attention_fwd_resid(const void* qkv, void* o, float* lse2, const floa
 int vitamd_attention_bwd(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv,
                          float* delta, float* dbias, int B, int N, int H, int head_dim, int causal, float dropout_p,
                          unsigned long long seed, void* stream);
+
+/* ---- KV-cached decoding (autoregressive generation on a causal stack) ---------------------------------
+ * The reference has no cache: VideoGPT.generate (train_videogpt.py:56-65) re-runs the whole stack over the whole prefix for every new
+ * token.  These three entry points run one token per sequence per call against a per-layer cache instead.
+ * Cache layout (per layer): k_cache, v_cache bf16 [B][H][Lmax][64].  `len` is a DEVICE int32: the number of positions already held
+ * (the grids are sized from Lmax, work past the length exits early, so a decode step needs no host synchronisation).
+ * head_dim must be 64 and 1 <= Lmax <= 16384, else VITAMD_ERR_SHAPE.  The caller advances *len after a token's layers have run.
+ *
+ * Append: copies the k and v slices of T rows of a packed QKV GEMM output qkv bf16 [B*T, 3*H*64] (the layout vitamd_attention_fwd
+ * reads) to cache positions *len .. *len+T-1.  T = 1 decodes, T = prompt length prefills.  T > Lmax: VITAMD_ERR_SHAPE; rows whose
+ * position would reach Lmax are not written (the host binding refuses len + T > Lmax against its own copy of the length).
+ * replaces the K/V half of transformer.py:27 for the cached path (the reference recomputes it for the whole prefix). */
+int vitamd_kv_append(const void* qkv, void* k_cache, void* v_cache, const int* len, int B, int T, int H, int head_dim, int Lmax,
+                     void* stream);
+/* Single-query attention: for each (b, h) the query row of qkv bf16 [B, 3*H*64] (one new token per sequence, already appended at
+ * position *len) against cache positions 0 .. *len, scale 1/8, fp32 softmax -> o bf16 [B, H*64] (vitamd_attention_fwd's layout).
+ * Long caches are split across workgroups (flash-decoding); the partials go to `ws` (vitamd_decode_attention_ws_bytes(B, H, Lmax)
+ * bytes, may be NULL when that is 0) and are merged in a fixed order: results are bit-reproducible.  B*H <= 65535.
+ * replaces transformer.py:28-29 (causal SDPA) for the last query row. */
+long vitamd_decode_attention_ws_bytes(int B, int H, int Lmax);
+int vitamd_decode_attention(const void* qkv, const void* k_cache, const void* v_cache, void* o, const int* len, int B, int H,
+                            int head_dim, int Lmax, float* ws, long ws_bytes, void* stream);
+/* Skinny-M GEMM: out = epi(A[M,K] . W[N,K]^T), bf16 operands, fp32 accumulation, 1 <= M <= 64 (VITAMD_ERR_SHAPE otherwise), K % 64 == 0,
+ * N % 4 == 0.  The weights are streamed once, split over N and, where N alone leaves CUs idle, over K; split-K partials go to `ws`
+ * (vitamd_gemm_skinny_ws_bytes(M, N, K) bytes, may be NULL when that is 0) and are summed in a fixed order (bit-reproducible).
+ * epi: VITAMD_EPI_BIAS_BF16, VITAMD_EPI_GELU (out = pre-activation, out2 = erf-GELU from the vitamd_init table: the same rounding as
+ * every GELU epilogue of vitamd_gemm_nt_bf16), VITAMD_EPI_RESID_F32 (aux fp32 [M,N]) or VITAMD_EPI_F32 (out f32 = acc + bias), with
+ * the semantics of vitamd_gemm_nt_bf16; bias (fp32 [N], rounded to bf16 as autocast does) may be NULL.  Rows are dense (ld = K / N).
+ * replaces transformer.py:21,27,37-39,44 and train_videogpt.py:43,53 (the Linears) at one row per sequence. */
+long vitamd_gemm_skinny_ws_bytes(int M, int N, int K);
+int vitamd_gemm_skinny_bf16(const void* A, const void* W, void* out, void* out2, const float* bias, const float* aux, int M, int N,
+                            int K, int epi, float* ws, long ws_bytes, void* stream);
 
 /* ---- helpers around the GEMMs ---------------------------------------------------------------- */
 /* fp32 -> bf16 (autocast's per-step weight / activation cast, train_vit.py:100). */

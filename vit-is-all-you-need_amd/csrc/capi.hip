@@ -3,7 +3,7 @@
 #include "vitamd_internal.h"
 #include "../../include/vitamd.h"
 
-extern "C" int vitamd_abi_version(void) { return 8; }
+extern "C" int vitamd_abi_version(void) { return 9; }
 
 // Per-device set-up: the only entry point that allocates (16 KiB: the erf-GELU table) or synchronises.  Idempotent; device < 0 = the current device.
 extern "C" int vitamd_init(int device, void* stream) { return vitamd_init_impl(device, (hipStream_t)stream); }

@@ -377,6 +377,8 @@ static const unsigned* gelu_table() {
 
 }  // namespace
 
+const unsigned* vitamd_gelu_table() { return gelu_table(); }
+
 int vitamd_init_impl(int device, hipStream_t stream) {
   static std::mutex mu;
   static unsigned host[4096];

@@ -51,4 +51,5 @@ struct GemmTnArgs {
 int vitamd_gemm_nt_impl(const GemmNtArgs& p, hipStream_t stream);
 int vitamd_gemm_nt_plan_impl(const GemmNtArgs& p);
 int vitamd_init_impl(int device, hipStream_t stream);
+const unsigned* vitamd_gelu_table();   // the current device's erf-GELU table image (vitamd_init), or null: shared by every GELU epilogue
 int vitamd_gemm_tn_impl(const GemmTnArgs& p, hipStream_t stream);

@@ -1,0 +1,113 @@
+"""MI355X-native drop-in for the model half of the reference's `train_videogpt` module (reference train_videogpt.py:18-66):
+VideoGPTConfig and VideoGPT with the same constructor signatures, attributes and state_dict keys (`tok_embed.weight`,
+`pos_embed.weight`, `transformer.layers.*` including the causal `mask` buffers, `proj.{weight,bias}`), so reference checkpoints load.
+
+The causal stack runs on the HIP kernels (transformer.Transformer -> TransformerStackFn), the output projection on the MFMA GEMMs
+(functions.linear in forward, the skinny-M GEMM with fp32 logits in generate); the embedding gathers, the cross-entropy and the argmax
+are torch device ops (as the loss is in train_vit.train_step).  `generate` adds a KV cache (vitamd/decode.py): the prompt is prefilled
+once and every further token costs one single-row pass through the stack.  The reference's training loop and its external TiTok
+video tokenizer (train_videogpt.py:68-150) are not part of this module."""
+from dataclasses import dataclass
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from transformer import Transformer, transformer_configs
+from vitamd import ops
+from vitamd.functions import WEIGHTS, linear
+
+
+@dataclass
+class VideoGPTConfig:
+    frame_size: int
+    codebook_size: int
+    transformer: str
+    max_frames: int
+    dropout: float
+
+    def __post_init__(self):
+        self.max_tokens = self.max_frames * self.frame_size
+        self.trans_config = transformer_configs[self.transformer](block_size=self.max_tokens, dropout=self.dropout, causal=True)
+        self.n_embd = self.trans_config.n_embd
+
+
+class VideoGPT(nn.Module):
+    """Next-token model over flattened video tokens [B, T*N]; index codebook_size is the start-of-sequence token."""
+
+    def __init__(self, config: VideoGPTConfig):
+        super().__init__()
+        self.config = config
+        self.tok_embed = nn.Embedding(config.codebook_size + 1, config.n_embd)
+        self.pos_embed = nn.Embedding(config.max_tokens, config.n_embd)
+        self.transformer = Transformer(config.trans_config)
+        self.proj = nn.Linear(config.n_embd, config.codebook_size)
+
+    def _embed(self, ids, pos0=0):
+        """token + position embeddings of ids [B, S] at positions pos0 .. pos0+S-1 (train_videogpt.py:49,59), fp32"""
+        pos = torch.arange(pos0, pos0 + ids.shape[1], device=ids.device)
+        return (self.tok_embed(ids) + self.pos_embed(pos)).float()
+
+    def _sos(self, B, device):
+        return torch.full((B, 1), self.config.codebook_size, device=device, dtype=torch.long)
+
+    def forward(self, x):
+        """x [B, T, N] token ids -> (logits [B, T*N, codebook_size], cross-entropy) (train_videogpt.py:44-53)"""
+        B, T, N = x.shape
+        y = x.reshape(B, T * N)
+        inp = torch.cat([self._sos(B, x.device), y[:, :-1]], dim=-1)
+        h = self.transformer(self._embed(inp))
+        logits = linear(h, self.proj.weight, self.proj.bias)
+        loss = F.cross_entropy(logits.reshape(B * T * N, -1), y.reshape(B * T * N))
+        return logits, loss
+
+    def _head(self, h_last):
+        """fp32 logits [B, codebook_size] of hidden states [B, D]: the skinny-M GEMM (one row per sequence) where its shape rules hold,
+        else the padded generic Linear"""
+        B, D = h_last.shape
+        Nc = self.config.codebook_size
+        if Nc % 4 == 0 and D % 64 == 0:
+            hb = ops.cast_bf16(h_last.float().contiguous())
+            wb, _ = WEIGHTS.get(self.proj.weight, False)
+            bias = self.proj.bias.detach().float().contiguous()
+            rows = [ops.gemm_skinny(hb[i:i + ops.SKINNY_MAX_M], wb, ops.EPI_F32, bias=bias) for i in range(0, B, ops.SKINNY_MAX_M)]
+            return rows[0] if len(rows) == 1 else torch.cat(rows)
+        return linear(h_last, self.proj.weight, self.proj.bias)
+
+    def _use_cache(self, use_cache):
+        if use_cache is None:
+            return self.config.dropout == 0
+        if use_cache and self.config.dropout > 0:
+            raise ValueError(f"generate(use_cache=True) needs dropout == 0 (got {self.config.dropout}): the reference applies SDPA dropout "
+                             "in eval mode too, which a KV cache cannot reproduce; use use_cache=False")
+        return bool(use_cache)
+
+    @torch.no_grad()
+    def generate(self, tokens, n=1, use_cache=None):
+        """Greedy continuation of tokens [B, S] by n tokens -> [B, S + n] (train_videogpt.py:54-63).  use_cache: None = cached when
+        dropout == 0; False = the reference's loop (the whole prefix through the stack per token) on the HIP stack."""
+        B, S = tokens.shape
+        if n < 1:
+            return tokens
+        if S + n > self.config.max_tokens:
+            raise ValueError(f"generate: {S} + {n} tokens need {S + n} positions, the model has max_tokens = {self.config.max_tokens}")
+        if not self._use_cache(use_cache):
+            for _ in range(n):
+                h = self.transformer(self._embed(torch.cat([self._sos(B, tokens.device), tokens], dim=-1)))
+                nxt = torch.argmax(self._head(h[:, -1]), dim=-1, keepdim=True)
+                tokens = torch.cat([tokens, nxt], dim=-1)
+            return tokens
+        cache = self.transformer.new_cache(B, max_len=S + n)
+        h = self.transformer.forward_cached(self._embed(torch.cat([self._sos(B, tokens.device), tokens], dim=-1)), cache)   # prefill
+        out = [tokens]
+        for step in range(n):
+            nxt = torch.argmax(self._head(h[:, -1]), dim=-1, keepdim=True)
+            out.append(nxt)
+            if step + 1 < n:
+                h = self.transformer.forward_cached(self._embed(nxt, pos0=cache.len), cache)
+        return torch.cat(out, dim=-1)
+
+    def generate_frames(self, video_tokens, n=1, use_cache=None):
+        """video_tokens [B, T, N] -> [B, T*N + n*frame_size] (train_videogpt.py:64-66)"""
+        B, T, N = video_tokens.shape
+        return self.generate(video_tokens.reshape(B, T * N), n * self.config.frame_size, use_cache=use_cache)

@@ -16,6 +16,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
+from vitamd import decode
 from vitamd.functions import AttentionFn, TransformerLayerFn, TransformerStackFn
 
 
@@ -100,6 +101,16 @@ class Transformer(nn.Module):
         params = [p for layer in self.layers for p in layer._params()]
         p_mlp = float(self.dropout) if self.training else 0.0
         return TransformerStackFn.apply(x, self.n_heads, bool(self.causal), float(self.dropout), p_mlp, *params)
+
+    # KV-cached inference (no reference counterpart: the reference re-runs forward over the whole prefix per token, train_videogpt.py:56-65)
+    def new_cache(self, batch, max_len=None):
+        """A KV cache for `batch` sequences of up to `max_len` (default block_size) positions on this module's device.  causal=True only."""
+        return decode.new_cache(self, batch, max_len)
+
+    def forward_cached(self, x, cache):
+        """Hidden states of positions cache.len .. cache.len+T-1 given x [B, T, D] of those positions; appends their K/V to `cache`.
+        T > 1 prefills an empty cache with the full causal path, T == 1 decodes one token per sequence.  No-grad; dropout must be 0."""
+        return decode.forward_cached(self, x, cache)
 
 
 def S(**kwargs): return TransformerConfig(n_layers=6, n_heads=8, n_embd=512, **kwargs)

@@ -12,7 +12,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvitamd.so")
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _c = ctypes
 _P, _I, _F, _L, _U64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_long, _c.c_ulonglong
@@ -51,6 +51,11 @@ SIGNATURES = {
     "vitamd_conv3x3_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_conv3x3_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_adamw_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P],
+    "vitamd_kv_append": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vitamd_decode_attention_ws_bytes": [_I, _I, _I],
+    "vitamd_decode_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
+    "vitamd_gemm_skinny_ws_bytes": [_I, _I, _I],
+    "vitamd_gemm_skinny_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
 }
 
 ERRORS = {1: "unsupported shape", 2: "bad argument", 3: "HIP launch failure", 4: "vitamd_init has not run for this device"}

@@ -437,3 +437,96 @@ def conv3x3_bwd(x, w, dy, need_dx=True, need_dw=True, has_bias=True):
     db = torch.zeros((Co,), dtype=F32, device=x.device) if (need_dw and has_bias) else None
     _lib.check(_L().vitamd_conv3x3_bwd(_p(x), _p(w), _p(dy), _p(dx), _p(dw), _p(db), B, C, Co, H, W, _stream()), "conv3x3_bwd")
     return dx, dw, db
+
+
+# ------------------------------------------------------------------------------------------ KV-cached decoding
+SKINNY_MAX_M = 64         # include/vitamd.h vitamd_gemm_skinny_bf16
+SKINNY_EPIS = (EPI_BIAS_BF16, EPI_GELU, EPI_RESID_F32, EPI_F32)
+DECODE_MAX_LEN = 16384    # cache capacity limit (attention.hip MAX_N_LONG)
+
+
+def _need_len(length):
+    _need(length, torch.int32, "len")
+    if length.numel() != 1:
+        raise _lib.VitamdError("len: expected a one-element device int32")
+    return length
+
+
+def _need_cache(k_cache, v_cache, B, H):
+    _need(k_cache, BF16, "k_cache", 4); _need(v_cache, BF16, "v_cache", 4)
+    if k_cache.shape != v_cache.shape or k_cache.shape[0] != B or k_cache.shape[1] != H or k_cache.shape[3] != 64:
+        raise _lib.VitamdError(f"cache: expected k and v bf16 [B={B}, H={H}, Lmax, 64], got {tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    Lmax = k_cache.shape[2]
+    if not 1 <= Lmax <= DECODE_MAX_LEN:
+        raise _lib.VitamdError(f"cache: Lmax must be in [1, {DECODE_MAX_LEN}], got {Lmax}")
+    return Lmax
+
+
+def kv_append(qkv, k_cache, v_cache, length, B, T, H, host_len=None):
+    """Copy the k / v slices of qkv bf16 [B*T, 3*H*64] to cache positions len .. len+T-1 of k_cache / v_cache bf16 [B, H, Lmax, 64].
+    length: device int32 [1] (read by the kernel).  host_len: the caller's copy of it, checked against Lmax when given."""
+    _need(qkv, BF16, "qkv", 2); _need_len(length)
+    Lmax = _need_cache(k_cache, v_cache, B, H)
+    if tuple(qkv.shape) != (B * T, 3 * H * 64):
+        raise _lib.VitamdError(f"kv_append: qkv must be [B*T, 3*H*64] = [{B * T}, {3 * H * 64}], got {tuple(qkv.shape)}")
+    if T > Lmax or (host_len is not None and host_len + T > Lmax):
+        raise _lib.VitamdError(f"kv_append: len {host_len} + T {T} exceeds the cache length {Lmax}")
+    _lib.check(_L().vitamd_kv_append(_p(qkv), _p(k_cache), _p(v_cache), _p(length), B, T, H, 64, Lmax, _stream()),
+               f"kv_append[B={B},T={T},H={H},Lmax={Lmax}]")
+
+
+def decode_attention(qkv, k_cache, v_cache, length, B, H, host_len=None):
+    """One query row per sequence: qkv bf16 [B, 3*H*64] (its K/V already appended at position len) against cache positions 0 .. len ->
+    o bf16 [B, H*64].  length: device int32 [1]; host_len: the caller's copy, checked (len + 1 <= Lmax) when given."""
+    _need(qkv, BF16, "qkv", 2); _need_len(length)
+    Lmax = _need_cache(k_cache, v_cache, B, H)
+    if tuple(qkv.shape) != (B, 3 * H * 64):
+        raise _lib.VitamdError(f"decode_attention: qkv must be [B, 3*H*64] = [{B}, {3 * H * 64}], got {tuple(qkv.shape)}")
+    if host_len is not None and host_len + 1 > Lmax:
+        raise _lib.VitamdError(f"decode_attention: len {host_len} + 1 exceeds the cache length {Lmax}")
+    nbytes = _L().vitamd_decode_attention_ws_bytes(B, H, Lmax)
+    if nbytes < 0:
+        raise _lib.VitamdError(f"decode_attention[B={B},H={H},Lmax={Lmax}]: {_lib.ERRORS.get(-nbytes, nbytes)}")
+    ws = _workspace(qkv.device, nbytes) if nbytes > 0 else None
+    o = torch.empty((B, H * 64), dtype=BF16, device=qkv.device)
+    _lib.check(_L().vitamd_decode_attention(_p(qkv), _p(k_cache), _p(v_cache), _p(o), _p(length), B, H, 64, Lmax, _p(ws),
+                                            0 if ws is None else ws.numel() * 4, _stream()), f"decode_attention[B={B},H={H},Lmax={Lmax}]")
+    return o
+
+
+def gemm_skinny(a, w, epi, *, bias=None, aux=None, out=None):
+    """out = epilogue(a[M,K] @ w[N,K]^T) for 1 <= M <= 64 (the decode-step Linears): weights streamed once across the chip, split-K
+    partials in the per-stream workspace, summed in a fixed order.  epi: EPI_BIAS_BF16, EPI_GELU (-> (pre, gelu)), EPI_RESID_F32 (aux fp32
+    [M,N]) or EPI_F32 (fp32 acc + bias).  Epilogue semantics as gemm_nt's."""
+    _need(a, BF16, "a", 2); _need(w, BF16, "w", 2)
+    M, K = a.shape
+    N, K2 = w.shape
+    if K != K2:
+        raise _lib.VitamdError(f"gemm_skinny: K mismatch {K} vs {K2}")
+    if epi not in SKINNY_EPIS:
+        raise _lib.VitamdError(f"gemm_skinny: unsupported epilogue {epi}")
+    if not 1 <= M <= SKINNY_MAX_M or N % 4 != 0 or K % 64 != 0:
+        raise _lib.VitamdError(f"gemm_skinny[M={M},N={N},K={K}]: needs 1 <= M <= {SKINNY_MAX_M}, N % 4 == 0, K % 64 == 0")
+    out_dtype = F32 if epi in (EPI_RESID_F32, EPI_F32) else BF16
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=a.device)
+    _need(out, out_dtype, "out", 2)
+    out2 = torch.empty((M, N), dtype=BF16, device=a.device) if epi == EPI_GELU else None
+    if bias is not None:
+        _need(bias, F32, "bias", 1)
+        if bias.numel() != N:
+            raise _lib.VitamdError(f"gemm_skinny: bias must have {N} elements")
+    if epi == EPI_RESID_F32:
+        _need(aux, F32, "aux", 2)
+        if tuple(aux.shape) != (M, N):
+            raise _lib.VitamdError(f"gemm_skinny: aux must be [{M}, {N}]")
+    if tuple(out.shape) != (M, N):
+        raise _lib.VitamdError(f"gemm_skinny: out must be [{M}, {N}]")
+    if epi == EPI_GELU:
+        init(a.device)
+    nbytes = _L().vitamd_gemm_skinny_ws_bytes(M, N, K)
+    ws = _workspace(a.device, nbytes) if nbytes > 0 else None
+    code = _L().vitamd_gemm_skinny_bf16(_p(a), _p(w), _p(out), _p(out2), _p(bias), _p(aux) if epi == EPI_RESID_F32 else None, M, N, K, epi,
+                                        _p(ws), 0 if ws is None else ws.numel() * 4, _stream())
+    _lib.check(code, f"gemm_skinny[M={M},N={N},K={K},epi={epi}]")
+    return (out, out2) if epi == EPI_GELU else out
