@@ -319,6 +319,35 @@ def test_gemm_nt_loader_form_bit_identical(hip, M, N, K):
         ops.gemm_nt(a[:, :64].contiguous(), b[:, :64].contiguous(), ops.EPI_BIAS_BF16, bias=bias, tile=2048)      # an odd number of K-tiles: refused, not mis-computed
 
 
+@pytest.mark.parametrize("M,N,K,rows,epi", [(25216, 2304, 704, 256, "bias"), (25216, 2304, 704, 256, "gelu_dg"), (25216, 2304, 704, 256, "dmul"),
+                                            (50432, 3072, 768, 320, "bias")])
+def test_gemm_nt_seam_form_bit_identical(hip, M, N, K, rows, epi):
+    """The seam kernel (gemm_nt_seam.h) where the library's own rule plans it - 256-row tiles for an odd number of K-tiles (K = 704: no loader-wave
+    form), 320-row tiles for plain-bias launches with >= 3 of them per CU (N = 3072, K = 768 at M = 50 432) - against gemm_nt_pp_kernel on one
+    workgroup per tile (tile code 256): RANDOM data, twice (a race would not repeat), bit for bit; column sums (atomics, order differs) to 1e-5."""
+    from vitamd import ops, lib
+    code = {"bias": ops.EPI_BIAS_BF16, "gelu_dg": ops.EPI_GELU_DG, "dmul": ops.EPI_DMUL}[epi]
+    plan = lib.load().vitamd_gemm_nt_plan(M, N, K, N, code, 0)
+    assert plan & 0x7f == ops.NT_FORM_SEAM and plan >> 8 == rows, hex(plan)
+    a, b = r16(randn((M, K), 111)).to(dev(), BF16), r16(randn((N, K), 112, 0.05)).to(dev(), BF16)
+    bias = randn((N,), 113).to(dev())
+    aux = r16(randn((M, N), 114, 0.5)).to(dev(), BF16)
+
+    def run(tile):
+        cs = torch.zeros(N, device=dev())
+        kw = dict(aux=aux, colsum=cs) if code == ops.EPI_DMUL else dict(bias=bias)
+        o = ops.gemm_nt(a, b, code, tile=tile, **kw)
+        return list(o if isinstance(o, tuple) else (o,)), cs
+
+    ref, cs_ref = run(256)
+    for rep in range(2):
+        got, cs = run(ops._RAW_AUTO)                                 # tile 0 of the C ABI: the library's automatic choice, no host-side policy
+        for x, y in zip(got, ref):
+            assert torch.equal(x, y), (epi, rep)
+        if code == ops.EPI_DMUL:
+            assert O.rel_l2(cs.cpu(), cs_ref.cpu()) < 1.0e-5
+
+
 def test_gelu_needs_vitamd_init_and_init_is_idempotent(hip):
     """C-ABI contract (include/vitamd.h): vitamd_init is the only entry point that allocates; it is idempotent; the host wrapper calls it before
     the first GELU launch on a device."""
@@ -416,18 +445,6 @@ def test_gemm_tn_overwrite_mode_without_workspace_is_refused(hip):
     assert hip.vitamd_gemm_tn_bf16_ws(l.data_ptr(), r.data_ptr(), out.data_ptr(), 128, 256, 256, 256, 256, 256, 0, small.data_ptr(), 64, 0, 0, st) == 2
     torch.cuda.synchronize()
     assert torch.equal(out.cpu(), torch.full((256, 256), 5.0))          # untouched
-
-
-def test_experimental_library_alternatives(hip):
-    """What libvitamd_exp.so (make EXPERIMENTAL=1) carries beyond the product - explicit seam-kernel codes, the loader kernel's first request
-    schedule, the round-3 weight-gradient loaders, the split-role and plain-loop attention backward - is checked bit for bit against production by
-    tools/check_experimental.py, in a child process so that this process only ever maps the production library."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists(os.path.join(root, "vit-is-all-you-need_amd", "vitamd", "libvitamd_exp.so")):
-        pytest.skip("libvitamd_exp.so not built (make EXPERIMENTAL=1)")
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_experimental.py")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
 
 
 # ------------------------------------------------------------------------------------------ layernorm

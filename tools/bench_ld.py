@@ -5,12 +5,9 @@ usage: bench_ld.py [rows]"""
 import os, sys, statistics, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "vit-is-all-you-need_amd"))
-from vitamd import ops, lib as _lib
-EXP = "--exp" in sys.argv            # experimental library: the burst schedule (tile 2049) and the timing-only ablations (dbg bits 0 / 1, results garbage)
-if EXP: _lib.use_experimental()
-_args = [a for a in sys.argv[1:] if not a.startswith("--")]
+from vitamd import ops
 dev = torch.device("cuda")
-M, D = (int(_args[0]) if _args else 256 * 197), 768
+M, D = (int(sys.argv[1]) if len(sys.argv) > 1 else 256 * 197), 768
 g = torch.Generator(device="cpu").manual_seed(1)
 def rb(*s, scale=1.0): return (torch.randn(*s, generator=g) * scale).to(dev, torch.bfloat16)
 x1, x3, x4 = rb(M, D), rb(M, 3 * D), rb(M, 4 * D)
@@ -26,22 +23,15 @@ calls = [
     ("dgrad_fc1", lambda t: ops.gemm_nt(x4, w1_t, ops.EPI_BIAS_BF16, tile=t), 2.0 * M * D * 4 * D),
     ("dgrad_qkv", lambda t: ops.gemm_nt(x3, wqkv_t, ops.EPI_BIAS_BF16, tile=t), 2.0 * M * D * 3 * D),
 ]
-cfgs = {"auto": (0, 0), "loader": (2048, 0)}
-if EXP: cfgs.update({"ld10_320": (4096, 0), "ld_burst": (2049, 0), "ld_oob": (2048, 1), "ld_noreq": (2048, 2), "ld_Ares": (2048, 4), "ld_Bres": (2048, 8), "ld_ABres": (2048, 12), "ld_Acont": (2048, 16), "ld_ABcont": (2048, 48)})
-def setdbg(d):
-    if EXP: _lib.load().vitamd_set_debug(d & 0xff); _lib.load().vitamd_set_debug2(d >> 8 << 8)
+cfgs = {"auto": 0, "loader": 2048}
 tot = {k: 0.0 for k in cfgs}
 for name, fn, fl in calls:
     ref = None
     res = {k: [] for k in cfgs}
     for rnd in range(5):
-        for k, (t, dbg) in cfgs.items():
-            setdbg(dbg)
-            try:
-                out = fn(t)
-            except _lib.VitamdError:
-                setdbg(0); res[k].append(float("nan")); continue
-            if rnd == 0 and dbg == 0:
+        for k, t in cfgs.items():
+            out = fn(t)
+            if rnd == 0:
                 torch.cuda.synchronize()
                 outs = out if isinstance(out, tuple) else (out,)
                 got = [o.float().clone() for o in outs] + ([cs.clone()] if name == "dgrad_fc2" else [])
@@ -57,7 +47,6 @@ for name, fn, fl in calls:
             for _ in range(10): fn(t)
             e.record(); torch.cuda.synchronize()
             res[k].append(s.elapsed_time(e) / 10 * 1e3)
-            setdbg(0)
     for k in cfgs:
         med = statistics.median(res[k]); tot[k] += med
         print(f"{name:10s} {k:8s} {med:7.1f} us  {fl / med / 1e6:7.1f} TF  {['%.0f' % v for v in res[k]]}", flush=True)

@@ -4,11 +4,7 @@ overlap gain = alone_P + alone_TN - together."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "vit-is-all-you-need_amd"))
-if os.environ.get("TN_SMALL_RING"):        # co-residency experiment: the 5-slot-ring (80 KiB) weight-gradient kernel of the experimental library
-    from vitamd import lib as _explib; _explib.use_experimental()
 from vitamd import ops, functions as F
-if os.environ.get("TN_SMALL_RING"):
-    _explib.load().vitamd_set_debug(-2147483648)     # bit 31
 dev = torch.device("cuda")
 B, N, H, D = 256, 197, 12, 768
 M = B * N

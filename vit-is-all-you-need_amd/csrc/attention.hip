@@ -240,40 +240,7 @@ struct AttnArgs {
   // (transformer.py:44 `x = x + attn(...)`), so the LayerNorm that follows reads x once instead of x and o and writing x
   const float* resid_in;
   float* resid_out;
-  int dbg;             // experimental builds: A/B bits (0 in production)
 };
-
-// Phase probe of experimental builds (dbg bit 15; tools/attn_phases.py): every wave sums the shader-clock cycles it spends in each
-// phase (a tick drains its own loads and waits for the accumulator named) and adds them to g_attn_probe at exit.
-#ifdef VITAMD_EXPERIMENTAL
-constexpr int PROBE_WAVES = 16384;
-__device__ unsigned long long g_attn_probe[2 * PROBE_WAVES * 8];   // [kernel slot][wave][phase]: one private row per wave (no atomics)
-#define PROBE_DECL                                                  \
-  const bool pr_on = VITAMD_DBG(a) & 0x8000;                        \
-  const unsigned long long pr_wall0 = pr_on ? wall_clock64() : 0ull;  \
-  unsigned long long pr_last = pr_on ? clock64() : 0ull, pr_acc[6] = {0, 0, 0, 0, 0, 0};
-#define PROBE_TICK_(i, dep, WAITS)                                                         \
-  if (pr_on) {                                                                             \
-    const int d_ = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)(dep)));  \
-    asm volatile(WAITS ::"s"(d_) : "memory");                                              \
-    const unsigned long long t_ = clock64();                                               \
-    pr_acc[i] += t_ - pr_last;                                                             \
-    pr_last = t_;                                                                          \
-  }
-#define PROBE_TICK(i, dep) PROBE_TICK_(i, dep, "s_waitcnt vmcnt(0) lgkmcnt(0)")
-#define PROBE_TICK_NOVM(i, dep) PROBE_TICK_(i, dep, "s_waitcnt lgkmcnt(0)")
-#define PROBE_END(slot)                                                                               \
-  if (pr_on && lane == 0 && blockIdx.x * 4 + wave < PROBE_WAVES) {                                    \
-    unsigned long long* row_ = g_attn_probe + ((size_t)(slot) * PROBE_WAVES + blockIdx.x * 4 + wave) * 8; \
-    for (int i_ = 0; i_ < 6; ++i_) row_[i_] = pr_acc[i_];                                            \
-    row_[6] = 1ull;                                                                                   \
-  }
-#else
-#define PROBE_DECL
-#define PROBE_TICK(i, dep)
-#define PROBE_TICK_NOVM(i, dep)
-#define PROBE_END(slot)
-#endif
 
 // keep-scale of probability (b, head, query, key): 1/(1-p) or 0
 __device__ __forceinline__ float attn_keep(const AttnArgs& a, int bh, int query, int key) {
@@ -363,7 +330,6 @@ template <int NKT, bool DROP, bool CAUSAL, bool RES = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  PROBE_DECL
   const int head = blockIdx.x;     // one workgroup per (batch, head); a persistent two-per-CU grid walking the heads is slower (backward 276 against 256 us)
   const int b = head / a.H, hh = head % a.H;
   const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
@@ -387,7 +353,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) asm volatile("" : "+v"(qf[kk]), "+v"(qf2[kk]));   // pins the loads above the wait (hipcc sinks plain loads to their first use)
   __syncthreads();
-  PROBE_TICK(0, 0.f)
 
   const float c = a.scale_log2e;
   for (int qb = wrot; qb < nt; qb += 4) {
@@ -418,7 +383,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a
       }
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    PROBE_TICK(2, mx)
     const float mc = mx * c;
     float l = 0.f;
     f32x16 oacc[2];
@@ -446,7 +410,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a
       }
     }
     l += __shfl_xor(l, 32, 64);
-    PROBE_TICK(3, l + oacc[0][15] + oacc[1][15])
     const float inv = 1.0f / l;
     if constexpr (RES)
       store_rows_T_lds_resid(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg, a.resid_in + (size_t)b * N * D + hh * DH,
@@ -454,12 +417,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a
     else
       store_rows_T_lds(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg);
     if (lane < 32 && qrow < N) a.lse2[((size_t)b * a.H + hh) * N + qrow] = mc + log2f(l);
-    PROBE_TICK_NOVM(4, 0.f)
   }
-#ifdef VITAMD_EXPERIMENTAL
-  if (pr_on) pr_acc[5] = wall_clock64() - pr_wall0;      // 100-MHz wall clock over the wave's life: calibrates the cycle counter
-#endif
-  PROBE_END(0)
 }
 
 // ------------------------------------------------------------------------------------------ forward, 129 <= N <= 256, EIGHT waves (round 3)
@@ -566,12 +524,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
   char* vtile = smem + npad * 128;
   char* oimg = smem + 2 * npad * 128 + wave * 4096;
   const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
-  PROBE_DECL
   stage_tile(qbase + D, D3, N, npad, ktile, wave, lane);
   stage_tile(qbase + 2 * D, D3, N, npad, vtile, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  PROBE_TICK(0, 0.f)
 
   const float c = a.scale_log2e;
   const __bf16* obase = a.o + (size_t)b * N * D + hh * DH;
@@ -593,7 +549,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
     const size_t stat = ((size_t)b * a.H + hh) * N + min(qrow, N - 1);
     const float lse2 = a.lse2[stat];
     if (lane < 32 && qrow < N) a.delta[stat] = delta;
-    PROBE_TICK(1, delta + lse2)
 
     f32x16 dq[2];
 #pragma unroll
@@ -610,7 +565,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(ktile, T, kk, lane), qf[kk], s, 0, 0, 0);
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(vtile, T, kk, lane), dof[kk], dp, 0, 0, 0);
       }
-      PROBE_TICK(2, s[15] + dp[15])
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float pexp = fast_exp2(__builtin_fmaf(s[r], c, -lse2));
@@ -625,7 +579,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
           if (!(key < N && (!CAUSAL || key <= qrow))) s[r] = 0.f;
         }
       }
-      PROBE_TICK(3, s[0] + s[15])
 #pragma unroll
       for (int sidx = 0; sidx < 2; ++sidx) {
         const bf16x8 dsf = acc_to_frag(s, sidx);
@@ -633,19 +586,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
         for (int dt = 0; dt < 2; ++dt)
           dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(ktile, T, sidx, dt, lane), dsf, dq[dt], 0, 0, 0);
       }
-      PROBE_TICK(4, dq[0][15] + dq[1][15])
     }
     store_rows_T_lds(a.dqkv + (size_t)b * N * D3 + hh * DH, D3, N, q0, lane, dq, a.scale, oimg, a.dbias ? &csum_q : nullptr);
-    PROBE_TICK_NOVM(5, 0.f)
   }
   if (a.dbias) atomicAdd(a.dbias + hh * DH + lane, csum_q);   // 256 contiguous bytes per wave
-  PROBE_END(0)
 }
 
 // ------------------------------------------------------------------------------------------ backward, dQ: software-pipelined form
 // The loop above leaves the schedule to hipcc, which reads every LDS fragment right in front of the MFMA that consumes it and
 // keeps the three stages of a key tile (S/dP products, exp + dS on the VALU, dQ products) strictly one after the other: the phase
-// probe (tools/attn_phases.py) shows 1 660 cycles per tile against ~400 of matrix-pipe and ~300 of VALU work.  Here the tile count
+// probe showed 1 660 cycles per tile against ~400 of matrix-pipe and ~300 of VALU work.  Here the tile count
 // is a template parameter, the loop is unrolled and the stages of neighbouring tiles overlap by construction:
 //   iteration T:  request K/V row fragments of tile T+2 and the transposed K fragments of tile T
 //                 S, dP products of tile T+1 (fragments requested one iteration earlier)   } one scheduling region: hipcc interleaves
@@ -656,7 +606,6 @@ template <int NT>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  PROBE_DECL
   const int head = blockIdx.x;     // one workgroup per (batch, head); a persistent two-per-CU grid walking the heads is slower (backward 276 against 256 us)
   const int b = head / a.H, hh = head % a.H;
   const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
@@ -671,7 +620,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
   const __bf16* dobase = a.d_o + (size_t)b * N * D + hh * DH;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  PROBE_TICK(0, 0.f)
 
   const float c = a.scale_log2e;
   float csum_q = 0.f;
@@ -696,7 +644,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
     const size_t stat = ((size_t)b * a.H + hh) * N + min(qrow, N - 1);
     const float lse2 = a.lse2[stat];
     if (lane < 32 && qrow < N) a.delta[stat] = delta;
-    PROBE_TICK(1, delta + lse2)
 
     f32x16 dq[2];
 #pragma unroll
@@ -752,12 +699,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
         for (int dt = 0; dt < 2; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktr[sidx][dt], dsf, dq[dt], 0, 0, 0);
       }
     }
-    PROBE_TICK(2, dq[0][15] + dq[1][15])
     store_rows_T_lds(a.dqkv + (size_t)b * N * D3 + hh * DH, D3, N, q0, lane, dq, a.scale, oimg, a.dbias ? &csum_q : nullptr);
-    PROBE_TICK_NOVM(5, 0.f)
   }
   if (a.dbias) atomicAdd(a.dbias + hh * DH + lane, csum_q);   // 256 contiguous bytes per wave
-  PROBE_END(0)
 }
 
 // ------------------------------------------------------------------------------------------ backward, dK and dV
@@ -775,7 +719,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
   char* oimg = smem + 2 * npad * 128 + 2 * npad * 4 + wave * 4096;
   const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   const __bf16* dobase = a.d_o + (size_t)b * N * D + hh * DH;
-  PROBE_DECL
   stage_tile(qbase, D3, N, npad, qtile, wave, lane);
   stage_tile(dobase, D, N, npad, dotile, wave, lane);
   for (int i = threadIdx.x; i < npad; i += 256) {
@@ -785,7 +728,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  PROBE_TICK(0, 0.f)
 
   const float c = a.scale_log2e;
   float csum_k = 0.f, csum_v = 0.f;
@@ -795,7 +737,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
     bf16x8 kf[4], vf[4];
     load_lane_frags(qbase + D, D3, N, k0, lane, kf);
     load_lane_frags(qbase + 2 * D, D3, N, k0, lane, vf);
-    PROBE_TICK(1, (float)kf[3][7] + (float)vf[3][7])
     f32x16 dk[2], dv[2];
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
@@ -811,7 +752,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(qtile, T, kk, lane), kf[kk], s, 0, 0, 0);
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(dotile, T, kk, lane), vf[kk], dp, 0, 0, 0);
       }
-      PROBE_TICK(2, s[15] + dp[15])
       f32x16 pmat;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -835,7 +775,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
           }
         }
       }
-      PROBE_TICK(3, s[0] + pmat[15])
 #pragma unroll
       for (int sidx = 0; sidx < 2; ++sidx) {
         const bf16x8 pf = acc_to_frag(pmat, sidx);
@@ -846,18 +785,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
           dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(qtile, T, sidx, dt, lane), dsf, dk[dt], 0, 0, 0);
         }
       }
-      PROBE_TICK(4, dk[1][15] + dv[1][15])
     }
     __bf16* dbase = a.dqkv + (size_t)b * N * D3 + hh * DH;
     store_rows_T_lds(dbase + D, D3, N, k0, lane, dk, a.scale, oimg, a.dbias ? &csum_k : nullptr);
     store_rows_T_lds(dbase + 2 * D, D3, N, k0, lane, dv, 1.0f, oimg, a.dbias ? &csum_v : nullptr);
-    PROBE_TICK_NOVM(5, 0.f)
   }
   if (a.dbias) {
     atomicAdd(a.dbias + D + hh * DH + lane, csum_k);
     atomicAdd(a.dbias + 2 * D + hh * DH + lane, csum_v);
   }
-  PROBE_END(1)
 }
 
 // ------------------------------------------------------------------------------------------ backward, dK and dV: software-pipelined form
@@ -869,7 +805,6 @@ template <int NT>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  PROBE_DECL
   const int head = blockIdx.x;     // one workgroup per (batch, head); a persistent two-per-CU grid walking the heads is slower (backward 276 against 256 us)
   const int b = head / a.H, hh = head % a.H;
   const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
@@ -890,7 +825,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArg
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  PROBE_TICK(0, 0.f)
 
   const float c = a.scale_log2e;
   float csum_k = 0.f, csum_v = 0.f;
@@ -899,7 +833,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArg
     bf16x8 kf[4], vf[4];
     load_lane_frags(qbase + D, D3, N, k0, lane, kf);
     load_lane_frags(qbase + 2 * D, D3, N, k0, lane, vf);
-    PROBE_TICK(1, (float)kf[3][7] + (float)vf[3][7])
     f32x16 dk[2], dv[2];
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
@@ -964,22 +897,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArg
         for (int kk = 0; kk < 4; ++kk) { qr[kk] = row_frag(qtile, T + 2, kk, lane); dor[kk] = row_frag(dotile, T + 2, kk, lane); }
       }
     }
-    PROBE_TICK(2, dk[1][15] + dv[1][15])
     __bf16* dbase = a.dqkv + (size_t)b * N * D3 + hh * DH;
     store_rows_T_lds(dbase + D, D3, N, k0, lane, dk, a.scale, oimg, a.dbias ? &csum_k : nullptr);
     store_rows_T_lds(dbase + 2 * D, D3, N, k0, lane, dv, 1.0f, oimg, a.dbias ? &csum_v : nullptr);
-    PROBE_TICK_NOVM(5, 0.f)
   }
   if (a.dbias) {
     atomicAdd(a.dbias + D + hh * DH + lane, csum_k);
     atomicAdd(a.dbias + 2 * D + hh * DH + lane, csum_v);
   }
-  PROBE_END(1)
 }
-
-#ifdef VITAMD_EXPERIMENTAL
-#include "experimental/attention_split.inc"
-#endif
 
 // ------------------------------------------------------------------------------------------ long sequences (N > 512)
 // Same three algorithms with both sides tiled: the grid gets a second dimension over blocks of 128 "lane-side" rows
@@ -1305,7 +1231,7 @@ static int attention_fwd_impl(const void* qkv, void* o, float* lse2, const float
   hipStream_t stream = (hipStream_t)stream_;
   if (head_dim != DH) return VITAMD_ERR_SHAPE;
   AttnArgs a{(const __bf16*)qkv, (__bf16*)o, lse2, nullptr, nullptr, nullptr, nullptr, B, N, H, causal, 0.125f * 1.4426950408889634f, 0.125f,
-             0u, 1.0f, 0u, 0u, resid_in, resid_out, VITAMD_GDBG};
+             0u, 1.0f, 0u, 0u, resid_in, resid_out};
   if (int e = check(a)) return e;
   if (!qkv || !o || !lse2 || !attn_dropout(a, dropout_p, seed)) return VITAMD_ERR_ARG;
   const bool drop = a.drop_thresh != 0u;
@@ -1322,7 +1248,7 @@ static int attention_fwd_impl(const void* qkv, void* o, float* lse2, const float
     }
     return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
   }
-  if (nkt >= 5 && nkt <= 8 && !drop && !causal && !(VITAMD_GDBG & 0x8000)) {      // eight waves, one query block each (dbg bit 15 of experimental builds: off)
+  if (nkt >= 5 && nkt <= 8 && !drop && !causal) {      // eight waves, one query block each
     const int lds = 2 * npad * 128 + 8 * 2048;
     int e = VITAMD_OK;
 #define FWD_SMALL8(K) case K: \
@@ -1332,7 +1258,7 @@ static int attention_fwd_impl(const void* qkv, void* o, float* lse2, const float
 #undef FWD_SMALL8
     if (e) return e;
   } else if (nkt <= 8) {
-    const int lds = 2 * npad * 128 + 4 * 4096 + ((VITAMD_GDBG & 0x4000) ? 32768 : 0);      // (dbg bit 14, experimental builds: occupancy probe - one workgroup per CU)
+    const int lds = 2 * npad * 128 + 4 * 4096;
     int e = VITAMD_OK;
 #define FWD_SMALL(K) case K: e = drop ? launch_fwd_small<K, true>(a, lds, stream) : launch_fwd_small<K, false>(a, lds, stream); break;
     switch (nkt) { FWD_SMALL(1) FWD_SMALL(2) FWD_SMALL(3) FWD_SMALL(4) FWD_SMALL(5) FWD_SMALL(6) FWD_SMALL(7) FWD_SMALL(8) }
@@ -1357,7 +1283,7 @@ extern "C" int vitamd_attention_bwd(const void* qkv, const void* o, const float*
   hipStream_t stream = (hipStream_t)stream_;
   if (head_dim != DH) return VITAMD_ERR_SHAPE;
   AttnArgs a{(const __bf16*)qkv, (__bf16*)o, (float*)lse2, (const __bf16*)d_o, (__bf16*)dqkv, delta, dbias, B, N, H, causal,
-             0.125f * 1.4426950408889634f, 0.125f, 0u, 1.0f, 0u, 0u, nullptr, nullptr, VITAMD_GDBG};
+             0.125f * 1.4426950408889634f, 0.125f, 0u, 1.0f, 0u, 0u, nullptr, nullptr};
   if (int e = check(a)) return e;
   if (!qkv || !o || !lse2 || !d_o || !dqkv || !delta || !attn_dropout(a, dropout_p, seed)) return VITAMD_ERR_ARG;
   if (N > MAX_N) {
@@ -1380,18 +1306,8 @@ extern "C" int vitamd_attention_bwd(const void* qkv, const void* o, const float*
   const int lds1 = 2 * npad * 128 + 4 * 4096, lds2 = 2 * npad * 128 + 2 * npad * 4 + 4 * 4096;
   const dim3 grid(B * H), block(256);
   const int nkt = npad / 32;
-  if (!a.drop_thresh && !a.causal && nkt >= 2 && nkt <= 7 && !(VITAMD_GDBG & 0x20000)) {      // (round 4, tools/ab_attn_bwd_pipe.py: with 8 / 9 key tiles - 256 tokens: ViT-VQGAN, 288: TiTok - the fully unrolled kernels LOSE to the plain loops, 604 against 402 us at B 256, N 256, H 12 and 597 against 440 at N 288; 2-7 tiles: equal to 13 % faster)     // the ViT shapes: pipelined forms (dbg bit 17 of experimental builds: the plain loops)
+  if (!a.drop_thresh && !a.causal && nkt >= 2 && nkt <= 7) {      // the ViT shapes: pipelined forms.  (Round 4, DESIGN.md section 8: with 8 / 9 key tiles - 256 tokens: ViT-VQGAN, 288: TiTok - the fully unrolled kernels LOSE to the plain loops, 604 against 402 us at B 256, N 256, H 12 and 597 against 440 at N 288; 2-7 tiles: equal to 13 % faster)
     int e = VITAMD_OK;
-#ifdef VITAMD_EXPERIMENTAL
-    if (nkt <= 7 && (g_vitamd_debug2 & 16)) {            // one staging of the head, split roles (attn_bwd_split_kernel)
-      const int lds3 = 4 * npad * 128 + 2 * npad * 4 + 8 * 4096;
-#define SPLIT(K) case K: e = set_lds(attn_bwd_split_kernel<K>, lds3); if (!e) hipLaunchKernelGGL(attn_bwd_split_kernel<K>, grid, dim3(512), lds3, stream, a); break;
-      switch (nkt) { SPLIT(2) SPLIT(3) SPLIT(4) SPLIT(5) SPLIT(6) SPLIT(7) }
-#undef SPLIT
-      if (e) return e;
-      return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
-    }
-#endif
 #define DQ_PIPE(K) case K: e = set_lds(attn_bwd_dq_pipe_kernel<K>, lds1); if (!e) hipLaunchKernelGGL(attn_bwd_dq_pipe_kernel<K>, grid, block, lds1, stream, a); break;
     switch (nkt) { DQ_PIPE(2) DQ_PIPE(3) DQ_PIPE(4) DQ_PIPE(5) DQ_PIPE(6) DQ_PIPE(7) }
 #undef DQ_PIPE
@@ -1414,20 +1330,3 @@ extern "C" int vitamd_attention_bwd(const void* qkv, const void* o, const float*
 #undef BWD_SMALL
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
-
-#ifdef VITAMD_EXPERIMENTAL
-// experimental library only: sum (and clear) the per-wave phase-probe rows into out[16] = two kernel slots x (6 phases, waves, -)
-extern "C" int vitamd_debug_attn_probe(unsigned long long* out) {
-  static unsigned long long host[2 * PROBE_WAVES * 8];
-  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_attn_probe), sizeof(host)) != hipSuccess) return VITAMD_ERR_LAUNCH;
-  for (int k = 0; k < 2; ++k)
-    for (int j = 0; j < 8; ++j) {
-      unsigned long long t = 0;
-      for (int w = 0; w < PROBE_WAVES; ++w) t += host[((size_t)k * PROBE_WAVES + w) * 8 + j];
-      out[k * 8 + j] = t;
-    }
-  void* dptr = nullptr;
-  if (hipGetSymbolAddress(&dptr, HIP_SYMBOL(g_attn_probe)) != hipSuccess) return VITAMD_ERR_LAUNCH;
-  return hipMemset(dptr, 0, sizeof(host)) == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
-}
-#endif

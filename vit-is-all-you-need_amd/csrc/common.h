@@ -13,18 +13,6 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 
-// Timing-only / A-B debug knobs exist only in experimental builds (`make EXPERIMENTAL=1` -> libvitamd_exp.so); in the production
-// library every knob reads as the constant 0 and the code behind it is compiled out.
-#ifdef VITAMD_EXPERIMENTAL
-extern int g_vitamd_debug;
-extern int g_vitamd_debug2;
-#define VITAMD_DBG(p) ((p).dbg)
-#define VITAMD_GDBG g_vitamd_debug
-#else
-#define VITAMD_DBG(p) 0
-#define VITAMD_GDBG 0
-#endif
-
 #define VITAMD_OK 0
 #define VITAMD_ERR_SHAPE 1
 #define VITAMD_ERR_ARG 2

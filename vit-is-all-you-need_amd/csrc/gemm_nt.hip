@@ -3,13 +3,14 @@
 //   forward  y = x W^T + b      : A = x [M,K],  B = W  [N,K]           (reference transformer.py:21,37,39)
 //   dgrad    dx = dy W          : A = dy [M,N'], B = W^T [K',N'] (the host keeps a bf16 transposed copy)
 //
-// Kernels in the production library:
+// Kernels:
 //   gemm_nt_pp_kernel   (32 MT) x 256 x 64 ping-pong kernel, MT = 8 (256 rows) or 10 (320 rows): LDS-DMA that never drains, one wave of
 //                       every SIMD in its matrix section while its partner reads LDS and issues DMA.  Every large GEMM of the step.
+//   gemm_nt_seam_kernel persistent ping-pong kernel that requests the next tile's pipeline fill before the epilogue (gemm_nt_seam.h).
+//   gemm_nt_ld_kernel   eight compute waves fed by four loader waves, 256-row tiles (gemm_nt_ld.h).
 //   gemm_nt_kernel      128 x 128 x 64 plain double-buffered kernel for small problems (classifier head, tiny models).
 // Epilogues (gemm_nt_epilogue.h): gemm_epilogue_rows (LDS-transposed, row-major 16-B accesses), gemm_epilogue (direct; small tiles, fp32).
-// The round-1 kernels (pipe / persistent / ring / deep) are measured alternatives in experimental/gemm_nt_variants.inc, built only with
-// `make EXPERIMENTAL=1` (libvitamd_exp.so, for the A/B tools); DESIGN.md section 4 holds their numbers.
+// plan_single below picks the form.  The measured alternatives of rounds 1-4 were removed; DESIGN.md section 4 holds their numbers.
 #include <type_traits>
 #include <mutex>
 #include <atomic>
@@ -175,11 +176,6 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmNtArgs p) {
   const int nkt = K / 64;
   const srd_t srdA = make_srd(p.A, (size_t)p.M * K * 2);
   const srd_t srdB = make_srd(p.B, (size_t)p.N * K * 2);
-  if constexpr (PERS) {     // start-up stagger of the persistent form: dbg bits 20-23 = groups, bits 8-15 = delay per group in ~us
-    const int P = (VITAMD_DBG(p) >> 20) & 0xf, unit = (VITAMD_DBG(p) >> 8) & 0xff;
-    if (P > 1)
-      for (int i = 0; i < unit * (int)(((VITAMD_DBG(p) & (1 << 24)) ? (blockIdx.x & 7) : (blockIdx.x >> 3)) % P); ++i) __builtin_amdgcn_s_sleep(32);   // bit 24: whole XCDs share a group
-  }
   for (int ti = blockIdx.x; ti < ntiles; ti += PERS ? (int)gridDim.x : ntiles) {
   const int tile = xcd_remap(ti, ntiles);
   int tm, tn;
@@ -193,27 +189,23 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmNtArgs p) {
     const unsigned chunk = (unsigned)(((lane & 7) ^ (lr & 7)) * 16);
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-      const int ga = min(((VITAMD_DBG(p) & 0x40000) ? (m0 & 0x3ff) : m0) + (lr >> 5) * (16 * MT) + j * 32 + (lr & 31), p.M - 1);     // clamp: rows past M are never stored (dbg bit 18, timing only: every tile loads one of a few L2-resident panels)
+      const int ga = min(m0 + (lr >> 5) * (16 * MT) + j * 32 + (lr & 31), p.M - 1);     // clamp: rows past M are never stored
       voffA[j] = (unsigned)ga * (unsigned)(K * 2) + chunk;
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int gb = min(((VITAMD_DBG(p) & 0x40000) ? 0 : n0) + 64 * q + lr, p.N - 1);
+      const int gb = min(n0 + 64 * q + lr, p.N - 1);
       voffB[q] = (unsigned)gb * (unsigned)(K * 2) + chunk;
     }
   }
   const unsigned lds0 = lds_addr(smem) + wave * 1024;
   constexpr unsigned OOB = 0x80000000u;
-  // (experimental builds, timing only, results garbage: dbg bit 28 = every request out of range - the instruction is issued, nothing is fetched;
-  //  dbg bit 24 = no request instructions at all: what the main loop costs without its feed)
   auto request_a = [&](int kt, int j) {
-    const bool live = kt >= 0 && kt < nkt && !(VITAMD_DBG(p) & 0x10000000);
-    if (VITAMD_DBG(p) & 0x1000000) return;
+    const bool live = kt >= 0 && kt < nkt;
     asm_glds16(srdA, lds0 + (kt & 1) * BUFB + j * PART, live ? voffA[j] : OOB, live ? (unsigned)kt * 128u : 0u);
   };
   auto request_b = [&](int kt, int q) {
-    const bool live = kt >= 0 && kt < nkt && !(VITAMD_DBG(p) & 0x10000000);
-    if (VITAMD_DBG(p) & 0x1000000) return;
+    const bool live = kt >= 0 && kt < nkt;
     asm_glds16(srdB, lds0 + (kt & 1) * BUFB + NP * PART + q * 8192, live ? voffB[q] : OOB, live ? (unsigned)kt * 128u : 0u);
   };
 
@@ -316,7 +308,7 @@ int launch_pp(const GemmNtArgs& p, hipStream_t stream) {
   auto kern = gemm_nt_pp_kernel<EPI, MT, LA, LB, PERS>;
   if (int e = set_lds(kern, lds)) return e;
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + 255) / 256);
-  const int cus = PERS ? device_cus() - 16 * ((VITAMD_DBG(p) >> 25) & 7) : tiles;     // (dbg bits 25-27 of experimental builds: 16 k fewer persistent workgroups than CUs)
+  const int cus = PERS ? device_cus() : tiles;
   hipLaunchKernelGGL(kern, dim3(PERS && tiles > cus ? cus : tiles), dim3(512), lds, stream, p);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
@@ -335,9 +327,8 @@ int launch(const GemmNtArgs& p, hipStream_t stream) {
 // N = 768 outputs take 591 tiles = 3 rounds of 256 rows but 474 tiles = 2 rounds of 320 rows (-0.6 ms/step); N = 3072 is a tie
 // (10 x 256 = 8 x 320), N = 2304 stays on 256 (7 x 256 < 6 x 320; forcing 320 there measured equal).  A 384-row tile would need
 // 192 accumulator registers (compiles to 256 VGPRs) and a two-pass epilogue, and quantises worse at this M.
-// dbg bit 19 disables the tall tile (A/B knob).
 static bool prefer_tall(const GemmNtArgs& p) {
-  if ((VITAMD_DBG(p) & 0x80000) || p.N % 8 != 0 || p.ldo % 8 != 0 || p.K % 64 != 0) return false;
+  if (p.N % 8 != 0 || p.ldo % 8 != 0 || p.K % 64 != 0) return false;
   if (p.epi != EPI_BIAS_BF16 && p.epi != EPI_RESID_F32 && p.epi != EPI_GELU && p.epi != EPI_DGELU) return false;
   const long tn = (p.N + 255) / 256;
   const long r256 = (((p.M + 255) / 256) * tn + 255) / 256, r320 = (((p.M + 319) / 320) * tn + 255) / 256;
@@ -420,44 +411,11 @@ int vitamd_init_impl(int device, hipStream_t stream) {
 
 namespace {
 
-#ifdef VITAMD_EXPERIMENTAL
-#include "experimental/gemm_nt_ld10.inc"
-// tile codes 24 / 25 / 30 (experimental builds): the seam kernel (gemm_nt_seam.h) on 256- / 320-row tiles whatever the automatic rule says
-template <int EPI>
-int dispatch_seam_explicit(const GemmNtArgs& p, hipStream_t stream, int tile) {
-  if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU) {
-    if (!seam_ok(p)) return VITAMD_ERR_SHAPE;
-    if (tile == 24 || tile == 30) return launch_seam<EPI, 8, EPI == EPI_GELU>(p, stream, device_cus());      // (GELU: always the table form)
-    if constexpr (EPI == EPI_BIAS_BF16) {
-      if (tile == 25) return launch_seam<EPI, 10>(p, stream, device_cus());
-    }
-  }
-  return VITAMD_ERR_ARG;
-}
-#endif
-
 // ---- which kernel a launch takes (one place: the dispatcher below executes the plan, vitamd_gemm_nt_plan reports it) -------------------------
 // tile selector of the C ABI: 0 = auto, 128 = the 128x128 kernel, 256 / 320 = the ping-pong kernel on 256- / 320-row tiles, one workgroup per
 // tile; 512 = auto without persistent launches; 1024 = auto with persistent launches but without the seam form; 2048 = the loader-wave form.
 enum NtForm { NT_FORM_SMALL = 1, NT_FORM_PP = 2, NT_FORM_PP_PERSISTENT = 3, NT_FORM_SEAM = 4, NT_FORM_LOADER = 5 };
 struct NtPlan { int form, rows, err; };
-
-// The loader-wave form (gemm_nt_ld.h) in the automatic choice.  Measured (profiles/r04/ab_nt_loader_whole_step*.log, two boxes,
-// bit-identical losses): in place of the 256-row seam kernel on the three K = 768 launch classes of a layer (QKV, fc1 + GELU, dgrad-fc2 x gelu') the
-// whole step gains 0.11 / 0.26 ms; on the N = 768 GEMMs (K = 2304 / 3072) it loses - 591 tiles of 256 rows are three rounds of the 256 CUs where
-// gemm_nt_pp_kernel runs two rounds of 320-row tiles, and twelve waves at <= 168 registers cannot hold a 320-row accumulator tile - so those stay.
-// `short_k`: the launch meets the 256-row seam rule (K <= 1536, >= 3 tiles per CU).
-static bool ld_auto(const GemmNtArgs& p, bool short_k) {
-  bool on = short_k;
-#ifdef VITAMD_EXPERIMENTAL
-  // whole-step A/B (tools/ab_ld.py; vitamd_set_debug2): bits 0 / 1 / 2 FLIP the default for plain-bias / GELU / dGELU-multiply launches with a short K
-  // loop; bit 3 = also the plain-bias launches with a long K loop (the N = 768 GEMMs), bit 5 = those of them without a bias (the input-gradient GEMMs)
-  const int d = g_vitamd_debug2;
-  if (short_k) on = on != ((d & (p.epi == EPI_BIAS_BF16 ? 1 : p.epi == EPI_GELU ? 2 : 4)) != 0);
-  else if (p.epi == EPI_BIAS_BF16 && p.K > 1536) on = (d & 8) != 0 || ((d & 32) != 0 && !p.bias);
-#endif
-  return on;
-}
 
 static NtPlan plan_single(const GemmNtArgs& p) {
   int tile = p.tile;
@@ -474,22 +432,23 @@ static NtPlan plan_single(const GemmNtArgs& p) {
   // Automatic choice, more tiles than CUs: the PERSISTENT form (one workgroup per CU walking a strided tile list; same kernel, same
   // results).  Alone it is as fast as one workgroup per tile; inside the training step, next to the weight-gradient GEMMs of the
   // second stream, it is faster: -0.45 / -0.04 / -0.34 / -0.45 ms per step on four boxes (tools/ab_persistent.py).  The explicit
-  // tile codes 256 / 320 keep the one-workgroup-per-tile launch.  (dbg bit 5 of experimental builds: no persistent launches)
+  // tile codes 256 / 320 keep the one-workgroup-per-tile launch.
   if (tile == 512) tile = 0;              // ABI code 512: the automatic choice WITHOUT persistent launches (one workgroup per tile)
-  else if (tile == 0 && big && !(VITAMD_DBG(p) & 0x20)) {
+  else if (tile == 0 && big) {
     const int cus = device_cus();
     // Short K loops with several tiles per CU: the SEAM form of the persistent kernel (gemm_nt_seam.h: the next tile's pipeline fill is requested
     // before the epilogue, the epilogue runs beside the operand buffers).  Measured on the ViT-B launches (tools/bench_seam.py): QKV 172 -> 163 us,
     // fc1+GELU 316 -> 298 (265-276 with the GELU table, which needs the 256-row ring), dgrad-fc2 298 -> 268 (K = 768, 7-10 tiles per CU); equal or
     // 4 % slower where a CU sees only two tiles of a long K loop (dgrad-fc1 K = 3072, dgrad-QKV K = 2304), which therefore stay on the form
-    // below.  Bit-identical results.  (dbg bit 17: off)
-    if (seam_epi && !no_seam && seam_ok(p)) {
-      if (p.K <= 1536 && !(VITAMD_DBG(p) & 0x20000)) {
-        if (epi == EPI_BIAS_BF16 && tall && (long)((p.M + 319) / 320) * ((p.N + 255) / 256) >= 3L * cus) return NtPlan{NT_FORM_SEAM, 320, VITAMD_OK};
-        // 256-row tiles: the loader-wave form (gemm_nt_ld.h) where it applies (an even number of K-tiles), else the seam kernel
-        if (big_tiles >= 3L * cus) return NtPlan{ld_ok(p) && ld_auto(p, true) ? NT_FORM_LOADER : NT_FORM_SEAM, 256, VITAMD_OK};
-      }
-      if (ld_ok(p) && ld_auto(p, false)) return NtPlan{NT_FORM_LOADER, 256, VITAMD_OK};
+    // below.  Bit-identical results.
+    if (seam_epi && !no_seam && seam_ok(p) && p.K <= 1536) {
+      if (epi == EPI_BIAS_BF16 && tall && (long)((p.M + 319) / 320) * ((p.N + 255) / 256) >= 3L * cus) return NtPlan{NT_FORM_SEAM, 320, VITAMD_OK};
+      // 256-row tiles: the loader-wave form (gemm_nt_ld.h) where it applies (an even number of K-tiles), else the seam kernel.  Measured (DESIGN.md
+      // section 4.7; profiles/r04/ab_nt_loader_whole_step*.log, two boxes, bit-identical losses): in place of the 256-row seam kernel on the three
+      // K = 768 launch classes of a layer (QKV, fc1 + GELU, dgrad-fc2 x gelu') the whole step gains 0.11 / 0.26 ms; on the N = 768 GEMMs (K = 2304 /
+      // 3072) it loses - 591 tiles of 256 rows are three rounds of the 256 CUs where gemm_nt_pp_kernel runs two rounds of 320-row tiles, and twelve
+      // waves at <= 168 registers cannot hold a 320-row accumulator tile - so those stay.
+      if (big_tiles >= 3L * cus) return NtPlan{ld_ok(p) ? NT_FORM_LOADER : NT_FORM_SEAM, 256, VITAMD_OK};
     }
     return NtPlan{NT_FORM_PP_PERSISTENT, tall ? 320 : 256, VITAMD_OK};
   }
@@ -504,20 +463,6 @@ template <int EPI>
 int dispatch_tile(const GemmNtArgs& p, hipStream_t stream) {
   constexpr bool seam_epi = EPI == EPI_BIAS_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU;
   constexpr bool tall_epi = seam_epi || EPI == EPI_RESID_F32;
-#ifdef VITAMD_EXPERIMENTAL
-  {   // experimental builds: further tile codes force a kernel form whatever the automatic rule says
-    int tile = p.tile;
-    if (tile >= 24 && tile <= 30) return dispatch_seam_explicit<EPI>(p, stream, tile);
-    if (tile == 4096) {                     // the 320-row loader form on ten compute + two loader waves (experimental/gemm_nt_ld10.inc)
-      if constexpr (EPI == EPI_BIAS_BF16) return ld10_ok(p) ? launch_ld10(p, stream, device_cus()) : VITAMD_ERR_SHAPE;
-      return VITAMD_ERR_SHAPE;
-    }
-    if (tile == 2049) {                     // the loader-wave form with its first request schedule (burst in phase 0)
-      if constexpr (seam_epi) return ld_ok(p) ? launch_ld<EPI, EPI == EPI_GELU, 0>(p, stream, device_cus()) : VITAMD_ERR_SHAPE;
-      return VITAMD_ERR_SHAPE;
-    }
-  }
-#endif
   const NtPlan pl = plan_single(p);
   if (pl.err) return pl.err;
   switch (pl.form) {
@@ -558,9 +503,9 @@ static int dispatch_epi(const GemmNtArgs& p, hipStream_t stream) {
 // the chip for a full tile time.  Two remedies: the tile height (prefer_tall) and the tail split decided here.
 // Tail split: the last, mostly empty round of big tiles is re-cut into 128x128 tiles.  Only ever paid for the fused-residual fc2 FORWARD GEMM
 // on 256-row tiles (591 tiles = 2.31 rounds; -0.2 ms/step), which the 320-row tile has since replaced (474 tiles = 1.85 rounds:
-// no split).  Everywhere else it loses on the whole step: +0.9 ms forced on every GEMM (bit 4) because the weight-gradient GEMMs
+// no split).  Everywhere else it loses on the whole step: +0.9 ms forced on every GEMM because the weight-gradient GEMMs
 // of the side stream already fill the backward tails, +0.2 ms on fc1+GELU at 7.4 rounds of 320-row tiles (the 128x128 kernel's
-// direct-store GELU epilogue costs more than the 0.6 idle round).  Experimental builds: vitamd_set_debug bit 7 turns it off, bit 4 forces it.
+// direct-store GELU epilogue costs more than the 0.6 idle round).
 static int tail_split_rows(const GemmNtArgs& p, bool& tall) {       // rows of the head part, 0 = no split
   const int CUS = device_cus();
   tall = (p.tile == 0 || p.tile == 512 || p.tile == 1024) && prefer_tall(p);
@@ -568,7 +513,7 @@ static int tail_split_rows(const GemmNtArgs& p, bool& tall) {       // rows of t
   const int tiles_m = (p.M + bm - 1) / bm, tiles_n = (p.N + 255) / 256;
   const long big_tiles = (long)tiles_m * tiles_n;
   const long rem = big_tiles % CUS;
-  const bool split_on = (VITAMD_DBG(p) & 16) != 0 || (!(VITAMD_DBG(p) & 128) && p.epi == EPI_RESID_F32 && !tall);
+  const bool split_on = p.epi == EPI_RESID_F32 && !tall;
   if (!((p.tile == 0 || p.tile == 512 || p.tile == 1024) && split_on && p.epi != EPI_PATCH_F32 && p.N >= 256 && p.K % 64 == 0 && big_tiles > 2 * CUS && rem != 0 && rem * 10 < CUS * 6))
     return 0;
   const int rows_a = (int)((big_tiles - rem) / tiles_n) * bm;       // M-panels whose tiles fill whole rounds
@@ -588,9 +533,6 @@ static int check_args(const GemmNtArgs& p) {
 int vitamd_gemm_nt_impl(const GemmNtArgs& p0, hipStream_t stream) {
   if (int e = check_args(p0)) return e;
   GemmNtArgs p = p0;
-#ifdef VITAMD_EXPERIMENTAL
-  p.dbg2 = g_vitamd_debug2;
-#endif
   if (p.epi == EPI_GELU) {                 // ONE rounding of GELU whatever kernel the launch takes: every GELU epilogue reads the table
     p.gelu_tab = gelu_table();
     if (!p.gelu_tab) return VITAMD_ERR_INIT;

@@ -1,4 +1,4 @@
-// Epilogues of the NT GEMM kernels (shared by gemm_nt.hip and, in experimental builds, its measured alternatives).
+// Epilogues of the NT GEMM kernels (gemm_nt.hip, gemm_nt_seam.h, gemm_nt_ld.h).
 #pragma once
 #include "common.h"
 #include "vitamd_internal.h"
@@ -94,9 +94,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmNtArgs& p, f32x4 (&acc)[
         u32x2 o1 = pz, o2;                                                           // `out` carries the pre-activation, or gelu'(pre) for the backward (gelu_dg)
         gelu_lookup<u32x2>(pz, (const char*)p.gelu_tab, p.gelu_dg != 0, o2, o1);
         *(u32x2*)((__bf16*)p.out + (size_t)m * ldo + n) = o1;
-        if (!(VITAMD_DBG(p) & 2)) *(u32x2*)((__bf16*)p.out2 + (size_t)m * ldo + n) = o2;
+        *(u32x2*)((__bf16*)p.out2 + (size_t)m * ldo + n) = o2;
       } else if constexpr (EPI == EPI_RESID_F32) {
-        const f32x4 res = (VITAMD_DBG(p) & 4) ? v : *(const f32x4*)((const float*)p.aux + (size_t)m * ldo + n);
+        const f32x4 res = *(const f32x4*)((const float*)p.aux + (size_t)m * ldo + n);
         f32x4 o;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -173,12 +173,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmNtArgs& p, f32x4 (&acc)[
 // owns 8 consecutive columns of one row: every global access is 16 B per lane and a wave-instruction
 // covers whole 128-B (bf16) / 256-B (fp32) row segments of 8 rows.
 // output stores are non-temporal (keeps the 32 MB-per-round output burst from evicting operand
-// panels out of the 8 x 4 MiB L2s: -5..7 % on the K = 3072 shapes); VITAMD_DBG(p) bit 3 turns that off (A/B knob)
-#define ST16(ptr, val)                                              \
-  do {                                                              \
-    if (VITAMD_DBG(p) & 8) *(ptr) = (val);                                  \
-    else __builtin_nontemporal_store((val), (ptr));                                            \
-  } while (0)
+// panels out of the 8 x 4 MiB L2s: -5..7 % on the K = 3072 shapes)
+#define ST16(ptr, val) __builtin_nontemporal_store((val), (ptr))
 
 template <int EPI, int MT = 8>
 __device__ __forceinline__ void gemm_epilogue_rows(const GemmNtArgs& p, f32x4 (&acc)[MT][4], int m0, int n0, int wm, int wn,
@@ -252,10 +248,9 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmNtArgs& p, f32x4 (&
 #pragma unroll
   for (int it = 0; it < 2 * MT; ++it) {
     const int rloc = rsub + 8 * it;
-    const int m_true = mbase + 8 * it;
-    const int m = (VITAMD_DBG(p) & 4) ? m_true % 640 : m_true;          // dbg bit 2: timing-only, every tile stores to the same few (L2-resident) rows
+    const int m = mbase + 8 * it;
     const u32x4 v = *(const u32x4*)(tile + rloc * 128 + pc * 16);
-    const bool ok = m_true < p.M && ncol_ok && !(VITAMD_DBG(p) & 0x10000);   // dbg bit 16: timing-only, no output stores
+    const bool ok = m < p.M && ncol_ok;
     if constexpr (EPI == EPI_BIAS_BF16) {
       if (ok) ST16((u32x4*)((__bf16*)p.out + (size_t)m * ldo + n), v);
     } else if constexpr (EPI == EPI_GELU) {

@@ -20,22 +20,24 @@
 // LDS: A(even K-tiles) | A(odd) | B(even) | B(odd), 32 KiB each (every fragment read = one of four base registers + a 16-bit immediate), then
 // 8 x 2 KiB wave-private epilogue staging and (GELU table form) the 16-KiB table.  An A block is two REGIONS of 128 rows (rows [64 h, 64 h + 64)
 // of both wave rows).  Region life: A0 and B of K-tile t are read in phases 0 and 2, A1 in phases 1 and 3; a region is refilled (with K-tile
-// t + 2) two phases after its last read, i.e. loader iteration (t + 1, phase 0) requests B and A0 of K-tile t + 2... in stream order: iteration
-// (t, 0) requests B(t + 1), A0(t + 1) into the buffer K-tile t - 1 left, iteration (t, 1) requests A1(t + 1); they are waited for in iterations
-// (t, 3) [vmcnt(4): everything but A1(t + 1)] and (t + 1, 0) [vmcnt(12): everything but the 12 new requests]: 3.5 phases in flight, up to 64 KiB
-// per CU.  K % 128 == 0 (an even number of K-tiles: the buffer parity is a compile-time constant of the twice-unrolled loop).
+// t + 2) two phases after its last read.  In stream order: iteration (t, 0) requests B(t + 1) pieces 0-5 into the buffer K-tile t - 1 left,
+// (t, 1) B pieces 6, 7 and A0(t + 1), (t, 2) A1(t + 1), half of each phase's requests behind its first barrier (SCHED below); they are waited
+// for in iterations (t, 3) [vmcnt(4): everything but A1(t + 1)] and (t + 1, 0) [vmcnt(6): everything but that phase's 6 new requests]: 2.5
+// phases in flight.  K % 128 == 0 (an even number of K-tiles: the buffer parity is a compile-time constant of the twice-unrolled loop).
 #pragma once
 #include "gemm_nt_epilogue.h"
 #include "gemm_nt_seam.h"
 
 namespace {
 
-// SCHED: how the loaders spread a K-tile's 16 requests (each) over its four phases.  0 = as early as the ring allows (12 in phase 0, 4 in phase 1:
-// 3.5 phases in flight, but the burst - ~60 cycles per piece - makes the loaders late for phase 0's barrier); 1 = 6 / 6 / 4 / 0, half of each
-// phase's requests behind its first barrier (2.5 phases in flight, <= 360 cycles of issue per phase): the shipped form.
+// SCHED: how the loaders spread a K-tile's 16 requests (each) over its four phases.  1 = 6 / 6 / 4 / 0, half of each phase's requests behind its
+// first barrier (2.5 phases in flight, <= 360 cycles of issue per phase) is the only schedule left.  The first one - as early as the ring allows,
+// 12 in phase 0 and 4 in phase 1: 3.5 phases in flight - lost: the burst (~60 cycles per piece) made the loaders late for phase 0's barrier.  The
+// parameter stays part of the kernel's name, which the recorded profiles key on.
 template <int EPI, bool TAB = false, int SCHED = 1>
 __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
   static_assert(EPI == EPI_BIAS_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU, "epilogues of the loader form");
+  static_assert(SCHED == 1, "request schedule");
   static_assert(!TAB || EPI == EPI_GELU, "table = GELU");
   constexpr int BM = 256, BN = 256, MT = 8, NT = 4;
   constexpr int AREG = 16384, ABUF = 32768, BBUF = 32768, BBASE = 2 * ABUF, OPS = BBASE + 2 * BBUF;
@@ -76,40 +78,33 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int a = 4 * l + i;
-          const int row = min(((VITAMD_DBG(p) & 4) ? (t.m0 & 0x3ff) : t.m0) + (a >> 3) * 128 + h * 64 + (a & 7) * 8 + r8, p.M - 1);      // clamp: rows past M are never stored (dbg bit 2, timing only: every tile loads one of four L2-resident A panels)
+          const int row = min(t.m0 + (a >> 3) * 128 + h * 64 + (a & 7) * 8 + r8, p.M - 1);      // clamp: rows past M are never stored
           voffA[h][i] = (unsigned)row * (unsigned)(K * 2) + chunk;
-          if (VITAMD_DBG(p) & 16) voffA[h][i] = (unsigned)min(t.m0, p.M - 256) * (unsigned)(K * 2) + (unsigned)((h * 16 + a) * 1024 + lane * 16);   // (dbg bit 4, timing only: every piece = 1 KiB CONTIGUOUS of the same panel - what a K-tile-blocked operand layout would fetch)
         }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const int row = min(((VITAMD_DBG(p) & 8) ? 0 : t.n0) + (8 * l + i) * 8 + r8, p.N - 1);      // (dbg bit 3, timing only: every tile loads the first B panel)
+        const int row = min(t.n0 + (8 * l + i) * 8 + r8, p.N - 1);
         voffB[i] = (unsigned)row * (unsigned)(K * 2) + chunk;
-        if (VITAMD_DBG(p) & 32) voffB[i] = (unsigned)min(t.n0, p.N - 256) * (unsigned)(K * 2) + (unsigned)((8 * l + i) * 1024 + lane * 16);     // (dbg bit 5: the same for B)
       }
     };
     // K-tile kt of the tile whose offsets are loaded; !live: past the last tile - requested out of range (zero fill, no traffic) so that the
-    // counts are the same in every iteration.  (experimental builds, timing only, results garbage: dbg bit 0 = every request out of range - the
-    // instruction is issued, nothing is fetched; dbg bit 1 = no request instructions at all)
+    // counts are the same in every iteration.
     bool live = true;
-    unsigned so = 0u, soA = 0u, soB = 0u, par = 0u;
+    unsigned so = 0u, par = 0u;
     // (a K loop that starts at a different K-tile per row panel - so that the CUs of different panels do not ask L2 for the same B lines at the same moment - was
     // measured equal: 1 308 against 1 296 us per layer, profiles/r04/nt_loader_k_rotation.log; removed)
     // (cache policies on these requests - nt, sc1, sc0 sc1 - were measured in round 4: sc1 equal, nt and sc0 sc1 3-8 % slower, and the two extra scalar
     // branches per request that selecting them at run time cost made the whole kernel 20-40 % slower: the loaders' issue loop is on every barrier's
     // critical path; profiles/r04/nt_loader_cache_policy.log)
     auto request_b = [&](int i) {
-      if (VITAMD_DBG(p) & 2) return;
-      asm_glds16(srdB, ldsB + par * BBUF + i * 1024, live ? voffB[i] : OOB, soB);
+      asm_glds16(srdB, ldsB + par * BBUF + i * 1024, live ? voffB[i] : OOB, so);
     };
     auto request_a = [&](int h, int i) {
-      if (VITAMD_DBG(p) & 2) return;
-      asm_glds16(srdA, ldsA + par * ABUF + h * AREG + i * 1024, live ? voffA[h][i] : OOB, soA);
+      asm_glds16(srdA, ldsA + par * ABUF + h * AREG + i * 1024, live ? voffA[h][i] : OOB, so);
     };
     auto target = [&](int kt, bool lv) {                // the K-tile the following requests fetch
-      live = lv && !(VITAMD_DBG(p) & 1);
+      live = lv;
       so = live ? (unsigned)kt * 128u : 0u;
-      soA = (VITAMD_DBG(p) & 16) ? so * 256u : so;      // contiguous-piece ablations: a K-tile of a 256-row panel = 32 KiB
-      soB = (VITAMD_DBG(p) & 32) ? so * 256u : so;
       par = (unsigned)(kt & 1);
     };
     __builtin_amdgcn_s_setprio(3);                      // the loaders' few instructions go first: a late request costs every wave of the workgroup
@@ -124,7 +119,6 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
     for (int i = 0; i < 4; ++i) request_a(0, i);
 #pragma unroll
     for (int i = 0; i < 4; ++i) request_a(1, i);
-    if (VITAMD_DBG(p) & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); else
     VITAMD_WAIT_VM(4);                                  // B(0), A0(0) landed; A1(0) is waited for in iteration (0, 0)
     __builtin_amdgcn_s_barrier();                       // START
     for (;;) {
@@ -140,58 +134,32 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
         // The buffer these requests fill held K-tile kt - 1: its B and A0 parts were last read in phase 2 of that K-tile (free from phase 0
         // of this one), its A1 part in phase 3 (free behind the first barrier of phase 0).  First reads: B, A0 in phase 0 of the next
         // K-tile (waited for in phase 3), A1 in its phase 1 (waited for in its phase 0).
-        if constexpr (SCHED == 0) {
-          // ---- phase 0
-#pragma unroll
-          for (int i = 0; i < 8; ++i) request_b(i);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) request_a(0, i);
-          __builtin_amdgcn_s_barrier();
-          VITAMD_WAIT_VM(12);                           // A1(kt) (first read in phase 1) has landed
-          __builtin_amdgcn_s_barrier();
-          // ---- phase 1
-          if constexpr (EPI != EPI_DGELU) {
-            if (kt == 0) {
-              asm_glds4(srdBias, lds_addr(smem) + OPS + l * STG, (unsigned)(bias_n0 + l * 64 + lane) * 4u, 0u);
-              asm_glds4(srdBias, lds_addr(smem) + OPS + (4 + l) * STG, (unsigned)(bias_n0 + l * 64 + lane) * 4u, 0u);
-            }
+        // ---- phase 0: B pieces 0-5
+        request_b(0); request_b(1); request_b(2);
+        __builtin_amdgcn_s_barrier();
+        request_b(3); request_b(4); request_b(5);
+        VITAMD_WAIT_VM(6);                              // A1(kt) (first read in phase 1) has landed
+        __builtin_amdgcn_s_barrier();
+        // ---- phase 1: B pieces 6, 7 and A0
+        if constexpr (EPI != EPI_DGELU) {
+          // first K-tile of a tile: every compute wave is inside the main loop, its staging image idle - the bias of ITS 64 columns goes there
+          // (256 B by LDS-DMA; both wave rows), long before the epilogue reads it
+          if (kt == 0) {
+            asm_glds4(srdBias, lds_addr(smem) + OPS + l * STG, (unsigned)(bias_n0 + l * 64 + lane) * 4u, 0u);
+            asm_glds4(srdBias, lds_addr(smem) + OPS + (4 + l) * STG, (unsigned)(bias_n0 + l * 64 + lane) * 4u, 0u);
           }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) request_a(1, i);
-          __builtin_amdgcn_s_barrier();
-          __builtin_amdgcn_s_barrier();
-          // ---- phase 2
-          __builtin_amdgcn_s_barrier();
-          __builtin_amdgcn_s_barrier();
-        } else {
-          // ---- phase 0: B pieces 0-5
-          request_b(0); request_b(1); request_b(2);
-          __builtin_amdgcn_s_barrier();
-          request_b(3); request_b(4); request_b(5);
-          VITAMD_WAIT_VM(6);                            // A1(kt) (first read in phase 1) has landed
-          __builtin_amdgcn_s_barrier();
-          // ---- phase 1: B pieces 6, 7 and A0
-          if constexpr (EPI != EPI_DGELU) {
-            // first K-tile of a tile: every compute wave is inside the main loop, its staging image idle - the bias of ITS 64 columns goes there
-            // (256 B by LDS-DMA; both wave rows), long before the epilogue reads it
-            if (kt == 0) {
-              asm_glds4(srdBias, lds_addr(smem) + OPS + l * STG, (unsigned)(bias_n0 + l * 64 + lane) * 4u, 0u);
-              asm_glds4(srdBias, lds_addr(smem) + OPS + (4 + l) * STG, (unsigned)(bias_n0 + l * 64 + lane) * 4u, 0u);
-            }
-          }
-          request_b(6); request_b(7); request_a(0, 0);
-          __builtin_amdgcn_s_barrier();
-          request_a(0, 1); request_a(0, 2); request_a(0, 3);
-          __builtin_amdgcn_s_barrier();
-          // ---- phase 2: A1
-          request_a(1, 0); request_a(1, 1);
-          __builtin_amdgcn_s_barrier();
-          request_a(1, 2); request_a(1, 3);
-          __builtin_amdgcn_s_barrier();
         }
+        request_b(6); request_b(7); request_a(0, 0);
+        __builtin_amdgcn_s_barrier();
+        request_a(0, 1); request_a(0, 2); request_a(0, 3);
+        __builtin_amdgcn_s_barrier();
+        // ---- phase 2: A1
+        request_a(1, 0); request_a(1, 1);
+        __builtin_amdgcn_s_barrier();
+        request_a(1, 2); request_a(1, 3);
+        __builtin_amdgcn_s_barrier();
         // ---- phase 3
         __builtin_amdgcn_s_barrier();
-        if (VITAMD_DBG(p) & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); else
         VITAMD_WAIT_VM(4);                              // B, A0 of the next K-tile (first read in its phase 0) have landed; its A1 may be in flight
         __builtin_amdgcn_s_barrier();
       }

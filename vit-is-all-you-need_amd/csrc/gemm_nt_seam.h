@@ -252,11 +252,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
         for (int j = 0; j < NT; ++j) pk[i][j] = (u32x2){pack_bf16x2(acc[i][j][0], acc[i][j][1]), pack_bf16x2(acc[i][j][2], acc[i][j][3])};
 #pragma unroll
       for (int it = 0; it < 2 * MT; ++it) {
-#ifdef VITAMD_EXPERIMENTAL
-        aux[it] = asm_bload16(srdAux, (mrow0 + 8 * it < p.M && !(p.dbg & 4)) ? obase : OOB, rstep * (unsigned)it);      // (dbg bit 2, timing only: no factor traffic)
-#else
         aux[it] = asm_bload16(srdAux, mrow0 + 8 * it < p.M ? obase : OOB, rstep * (unsigned)it);      // rows >= M: out of range -> 0
-#endif
       }
     } else {
       // the wave's 64 bias values -> the head of its (idle) staging area, by LDS-DMA: nothing lands in a register before the wait below
@@ -324,10 +320,6 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
             asm_bstore16_nt(v, rsO, voff, soff);
           } else if constexpr (EPI == EPI_GELU) {
             u32x4 a, d = v;
-#ifdef VITAMD_EXPERIMENTAL
-            if (p.dbg & 1) a = v;                                                // timing-only ablation: no erf / exp
-            else
-#endif
             if constexpr (TAB) gelu_lookup8(v, smem + TABOFF, p.gelu_dg != 0, a, d);
             else
 #pragma unroll
@@ -336,9 +328,6 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
               a[c] = pack_bf16x2(gelu_fwd_grad(bf16lo(v[c]), dlo), gelu_fwd_grad(bf16hi(v[c]), dhi));
               if (p.gelu_dg) d[c] = pack_bf16x2(dlo, dhi);                       // `out` carries gelu'(pre) for the backward
             }
-#ifdef VITAMD_EXPERIMENTAL
-            if (!(p.dbg & 2))                                                    // timing-only ablation: no second output
-#endif
             asm_bstore16_nt(d, rsO, voff, soff);
             asm_bstore16_nt(a, rsO2, voff, soff);
           } else {
@@ -356,11 +345,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
         }
       }
     }
-#ifdef VITAMD_EXPERIMENTAL
-    if (EPI == EPI_DGELU && !(p.dbg & 8)) {         // (dbg bit 3, timing only: no column sums)
-#else
     if constexpr (EPI == EPI_DGELU) {
-#endif
       // column sums of the stored tile (bias gradient of the producing Linear).  Lanes (rsub, pc) with equal pc ^ rsub hold partial sums of the
       // same 8 columns (their rows differ): a butterfly over rsub (partner lane ^ 9 b keeps pc ^ rsub) totals them in registers, then lane
       // (rsub, pc) adds column rsub of its chunk - exactly one atomic instruction per wave (N % 256 == 0 is a launch condition), no barrier and
@@ -372,9 +357,6 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
       float s = cs[0];
 #pragma unroll
       for (int c = 1; c < 8; ++c) s = rsub == c ? cs[c] : s;
-#ifdef VITAMD_EXPERIMENTAL
-      if (p.dbg & 16) { if (s == 123.456f) p.colsum[0] = s; } else      // (dbg bit 4, timing only: the butterfly without the atomic)
-#endif
       atomicAdd(p.colsum + n0 + wn * 64 + 8 * (pc ^ rsub) + rsub, s);
     }
     if (!has_next) break;

@@ -9,7 +9,7 @@
 // bank-conflict-free (tools/lds_banks.py).  mfma_f32_32x32x16_bf16 so one accumulator register of a wave = two 128-B row segments:
 // the shape float atomics run at full rate with.  Split over the reduction dimension (grid = tiles x splits): partial tiles go to a
 // workspace with plain stores and a reduce pass sums them (bitwise reproducible), or fp32 atomics straight into `out`.
-// The production kernel is the ping-pong kernel below; the round-1 kernels are in experimental/gemm_tn_variants.inc.
+// Two kernels: the ping-pong kernel below and its loader-wave form (GemmTnArgs::form = 1).  The round-1 kernels were removed in round 4.
 #include "common.h"
 #include "vitamd_internal.h"
 
@@ -202,9 +202,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_tn_pp_kernel(const GemmTnArgs a,
 // Measured (tools/bench_tn.py, profiles/r03/tn_loader_waves.log): alone 171 / 214 / 216 us against 201 / 247 / 258 for the three ViT-B weight
 // gradients (-15 %); inside the step it wins where the launch runs beside kernels that fill their CUs anyway (the fc2 weight gradient, beside
 // the two input-gradient GEMMs: -0.1 ... -0.36 ms per step) and loses where the 8-wave form shared CUs with LayerNorm (all launches: +0.46 ms).
-// LSPLIT (round 4, from the NT loader kernel where it was worth 5-14 %): the loaders issue half of a quarter's four requests behind the phase's
-// first barrier instead of all four in front of it, and run at priority 3 - a loader that is late for a barrier holds up all twelve waves.
-template <int NQ, int D, int ABL = 0, bool LSPLIT = true>      // ABL (experimental builds, timing only, results are garbage): 1 = no MFMAs, 2 = no transposed LDS reads, 3 = neither
+// Round 4 (from the NT loader kernel where it was worth 5-14 %): the loaders issue half of a quarter's four requests behind the phase's first
+// barrier instead of all four in front of it, and run at priority 3 - a loader that is late for a barrier holds up all twelve waves.
+template <int NQ, int D>
 __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int tiles_p, int tiles_q, int splits) {
   static_assert(D >= 2 && D <= NQ - 2, "prefetch distance: WAR rule");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -248,20 +248,15 @@ __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int
       slot_w = slot_w + 1 == NQ ? 0 : slot_w + 1;
     };
     auto issue = [&]() { issue_l(); issue_r(); };
-    if constexpr (LSPLIT) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int d = 0; d < D; ++d) issue();
     VITAMD_WAIT_VM(4 * (D - 1));
     __builtin_amdgcn_s_barrier();
     for (int g = g_lo; g < g_hi; ++g) {
-      if constexpr (LSPLIT) {
-        issue_l();
-        __builtin_amdgcn_s_barrier();
-        issue_r();
-      } else {
-      issue();
+      issue_l();
       __builtin_amdgcn_s_barrier();
-      }
+      issue_r();
       // quarter g + 1 is first read by the first wave row BEHIND the second barrier of this iteration, so the wait may sit here rather than in
       // front of the first barrier (one more interval for the requests to land).  Measured equal (164 / 212 / 215 us either way).
       VITAMD_WAIT_VM(4 * (D - 1));
@@ -300,9 +295,9 @@ __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int
     const char* q = smem + slot_r * QSLOT;
     bf16x8 af[MT], bfr[NT];
 #pragma unroll
-    for (int j = 0; j < NT; ++j) { if (ABL & 2) { for (int e = 0; e < 8; ++e) bfr[j][e] = (__bf16)1.0f; asm volatile("" : "+v"(bfr[j])); } else bfr[j] = tr_frag(q + offB[j]); }
+    for (int j = 0; j < NT; ++j) bfr[j] = tr_frag(q + offB[j]);
 #pragma unroll
-    for (int i = 0; i < MT; ++i) { if (ABL & 2) { for (int e = 0; e < 8; ++e) af[i][e] = (__bf16)1.0f; asm volatile("" : "+v"(af[i])); } else af[i] = tr_frag(q + offA[i]); }
+    for (int i = 0; i < MT; ++i) af[i] = tr_frag(q + offA[i]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -311,7 +306,7 @@ __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int j = 0; j < NT; ++j) { if (ABL & 1) { acc[i][j][0] += (float)af[i][0] * (float)bfr[j][0]; } else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0); }
+      for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -399,40 +394,13 @@ int vitamd_gemm_tn_impl(const GemmTnArgs& a, hipStream_t stream) {
   if (!use_ws && !a.accumulate) return VITAMD_ERR_ARG;      // overwrite mode needs the workspace: the atomic form can only add to `out`
   const dim3 grid(ntile * splits), block(NW * 64);
   if (use_ws) {
-    bool loader = a.form == 1;
-#ifdef VITAMD_EXPERIMENTAL
-    // A/B: bit 23 = the loader-wave form for every launch; bits 20 / 21 / 22 = where P <= 768 (fc2), P = 2304 (QKV), P = 3072 (fc1); bit 19 = never
-    loader = !(g_vitamd_debug & 0x80000) && (loader || (g_vitamd_debug & 0x800000) || ((g_vitamd_debug & 0x100000) && a.P <= 768) ||
-                                             ((g_vitamd_debug & 0x200000) && a.P == 2304) || ((g_vitamd_debug & 0x400000) && a.P == 3072));
-#endif
-    if (loader) {
-#ifdef VITAMD_EXPERIMENTAL
-      const int dv = (g_vitamd_debug >> 16) & 3;     // bits 16-17: timing-only ablations of the loader form (1 no MFMAs, 2 no transposed reads, 3 neither; results garbage)
-      if (dv) {
-        auto kern = dv == 1 ? gemm_tn_ld_kernel<8, 4, 1> : dv == 2 ? gemm_tn_ld_kernel<8, 4, 2> : gemm_tn_ld_kernel<8, 4, 3>;
-        if (int e = set_lds(kern, lds)) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(768), lds, stream, a, tiles_p, tiles_q, splits);
-      } else
-#endif
-      {
-#ifdef VITAMD_EXPERIMENTAL
-      if (g_vitamd_debug2 & 64) {                    // A/B (vitamd_set_debug2 bit 6): the round-3 loaders (all four requests in front of the first barrier, priority 0)
-        if (int e = set_lds((gemm_tn_ld_kernel<8, 4, 0, false>), lds)) return e;
-        hipLaunchKernelGGL((gemm_tn_ld_kernel<8, 4, 0, false>), grid, dim3(768), lds, stream, a, tiles_p, tiles_q, splits);
-      } else
-#endif
-      {
+    if (a.form == 1) {
       if (int e = set_lds(gemm_tn_ld_kernel<8, 4>, lds)) return e;
       hipLaunchKernelGGL((gemm_tn_ld_kernel<8, 4>), grid, dim3(768), lds, stream, a, tiles_p, tiles_q, splits);
-      }
-      }
     } else {
-    if (int e = set_lds(gemm_tn_pp_kernel<true, 8, 4>, lds)) return e;
-    hipLaunchKernelGGL((gemm_tn_pp_kernel<true, 8, 4>), grid, block, lds, stream, a, tiles_p, tiles_q, splits);
+      if (int e = set_lds(gemm_tn_pp_kernel<true, 8, 4>, lds)) return e;
+      hipLaunchKernelGGL((gemm_tn_pp_kernel<true, 8, 4>), grid, block, lds, stream, a, tiles_p, tiles_q, splits);
     }
-#ifdef VITAMD_EXPERIMENTAL
-    if (!(g_vitamd_debug2 & 128))                    // (vitamd_set_debug2 bit 7, timing only, gradients garbage: NO reduce pass - the bound on what folding / batching it could gain)
-#endif
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(BP * BQ / 4 / 256 / RPT, ntile), dim3(256), 0, stream, a.ws, a.out, a.P, a.Q, a.ldo, tiles_q, ntile, splits,
                        a.accumulate);
   } else {

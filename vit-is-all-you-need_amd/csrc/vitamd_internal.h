@@ -23,7 +23,6 @@ struct GemmNtArgs {
   int epi;
   int n_patches, seq, extra;  // EPI_PATCH_F32 row remap
   int tile;                   // 0 = auto, 128, 256
-  int dbg;                    // timing-only ablation bits (vitamd_set_debug); 0 in production
   // EPI_RESID_F32 only: dropout on the Linear output before the residual add (reference nn.Dropout, transformer.py:40)
   unsigned drop_thresh;       // p * 2^32, 0 = off
   float drop_scale;           // 1 / (1 - p)
@@ -32,7 +31,6 @@ struct GemmNtArgs {
   // stored-derivative GELU (ABI codes VITAMD_EPI_GELU_DG / VITAMD_EPI_DMUL): EPI_GELU writes out = bf16(gelu'(pre)) instead
   // of pre, EPI_DGELU multiplies by aux as stored instead of evaluating gelu'(aux)
   int gelu_dg;
-  int dbg2;                   // second word of A/B bits (experimental builds; vitamd_set_debug2)
   const unsigned* gelu_tab;   // EPI_GELU: device image of the erf-GELU table (vitamd_init; set by vitamd_gemm_nt_impl for every GELU launch)
 };
 

@@ -109,14 +109,13 @@ class WeightCache:
 WEIGHTS = WeightCache()
 
 
-ATTN_FUSED_RESID = False  # A/B knob: x1 = x0 + attention written by the attention forward kernel (N <= 256): correct, measured EQUAL (34.47 vs 34.43 ms)
 TN_TARGET_WGS = None   # None = follow the NT launch form (252 beside persistent NT launches, 128 beside one workgroup per tile), read on every call; an int overrides.  Workgroups per layer weight-gradient GEMM (tiles x split-K factor); 0 = the kernel's own rule (~256 = every CU).  Whole-step A/B (tools/ab_splits.py) with the PERSISTENT NT launches: 96 -> 31.21 ms, 128 -> 30.86, 160 -> 30.79, 192 -> 30.55, 216 -> 30.44, 252 -> 30.3, 288 -> 31.0, 504 -> 31.8 (with one NT workgroup per tile the optimum was 128-144: 31.45 vs 32.26 at 252)
 
 
 TN_FORM_POLICY = "auto"   # which weight-gradient kernel (ops.TN_FORM_*; same results).  "auto": the 12-wave EXCLUSIVE form for the fc2 weight gradient -
 # launched at the start of a layer's backward, beside the two input-gradient GEMMs of the MLP, whose workgroups fill their CUs anyway - and for every weight
 # gradient when there is no second stream; the 8-wave SHARED form elsewhere (the fc1 / QKV weight gradients run beside LayerNorm backward, whose waves share
-# CUs with it).  Whole-step A/B (tools/ab_dbg.py, profiles/r03/ab_tn_loader_*.log): fc2 only -0.10 / -0.36 ms on two boxes; all three +0.46 ms; fc1 or QKV
+# CUs with it).  Whole-step A/B (profiles/r03/ab_tn_loader_*.log): fc2 only -0.10 / -0.36 ms on two boxes; all three +0.46 ms; fc1 or QKV
 # alone +0.26 / +0.29; without the second stream all three -0.62 ms.  "shared" / "exclusive" force one form.
 
 
@@ -148,10 +147,6 @@ def tn_target_wgs():
     return 252 if ops.NT_PERSISTENT else 128
 
 
-SIDE_POLICY = 0           # A/B knob (tools/ab_side.py): when the MLP weight-gradient GEMMs enter the side stream: 0 = as soon as their inputs exist (beside the
-                          # input-gradient GEMMs), 1 = both after dgrad-fc1 (beside LayerNorm / attention backward), 2 = dW2 beside dgrad-fc1, dW1 after it
-LN_BWD_XHAT = True        # A/B knob (tools/ab_gelu.py): LayerNorm backward reads xhat from the saved bf16 LN output instead of recomputing it from fp32 x
-GELU_STORED_GRAD = True   # A/B knob (tools/ab_gelu.py); False = keep the pre-activation and evaluate gelu' in the backward
 DEFER_RESID = True        # inside a stack: fc2 writes bf16 y and the NEXT layer's first LayerNorm adds it to the residual stream (x2 = x1 + y, the same
                           # fp32 + bf16 sum the fused epilogue formed: bit-identical).  The same HBM bytes in total, but they move from the GEMM's
                           # epilogue (40 fp32 loads + 40 fp32 stores per wave and tile on the CU's one path to L1, matrix pipes idle) into an
@@ -231,17 +226,12 @@ def layer_forward(x0, wqkv, bqkv, w1, b1, w2, b2, B, N, H, causal, need_grad, p_
     w2_b, _ = WEIGHTS.get(w2, need_grad)
     x0, a, mean1, rstd1 = ops.layernorm_fwd(x0, addend=pending)                  # (residual of the layer below +) LN1   transformer.py:43-44
     qkv = ops.gemm_nt(a, wqkv_b, ops.EPI_BIAS_BF16, bias=bqkv)                   # fused QKV      transformer.py:27
-    if ATTN_FUSED_RESID and N <= ops.ATTN_RESID_MAX_N:
-        # SDPA (transformer.py:28-29) with the residual add of transformer.py:44 in its epilogue: the LayerNorm below then reads the
-        # fp32 stream once (6 B/element) instead of reading x0 and o and writing x1 (12 B/element)
-        o, lse, x1 = ops.attention_fwd(qkv, B, N, H, causal, dropout=drop[:2], resid=x0)
-        _, bln, mean2, rstd2 = ops.layernorm_fwd(x1)                             # LN2            transformer.py:43
-    else:
-        o, lse = ops.attention_fwd(qkv, B, N, H, causal, dropout=drop[:2])       # SDPA           transformer.py:28-29
-        x1, bln, mean2, rstd2 = ops.layernorm_fwd(x0, addend=o)                  # residual + LN2 transformer.py:43-44
+    # (the residual add can also ride in the attention kernel's epilogue - ops.attention_fwd(resid=) - which measured equal: 34.47 vs 34.43 ms)
+    o, lse = ops.attention_fwd(qkv, B, N, H, causal, dropout=drop[:2])           # SDPA           transformer.py:28-29
+    x1, bln, mean2, rstd2 = ops.layernorm_fwd(x0, addend=o)                      # residual + LN2 transformer.py:43-44
     # fc1 + GELU (transformer.py:37-38); `pre` holds bf16(gelu'(fc1 out)) for the backward - the derivative is evaluated
     # here, where its exp is shared with the erf and the VALU work hides under the output stores (-85 us per layer in dgrad fc2)
-    pre, h = ops.gemm_nt(bln, w1_b, ops.EPI_GELU_DG if GELU_STORED_GRAD else ops.EPI_GELU, bias=b1)
+    pre, h = ops.gemm_nt(bln, w1_b, ops.EPI_GELU_DG, bias=b1)
     y = None
     if p_mlp > 0:
         x2 = ops.linear_dropout_resid(h, w2_b, b2, x1, drop[2:])                 # fc2 + dropout + residual
@@ -392,25 +382,20 @@ def layer_backward(g2, saved, wqkv, w1, w2, B, N, H, causal, grads, dy2=None, ha
         ops.gemm_tn(dy2, h, dW2, accumulate=False, splits=_tn_splits(dW2), form=_tn_form("fc2"))
         if not have_db2:
             ops.colsum(dy2, db2)
-    if SIDE_POLICY == 0:
-        on_side(wgrad_fc2, dy2, h, dW2, db2)
-    dpre = ops.gemm_nt(dy2, w2_t, ops.EPI_DMUL if GELU_STORED_GRAD else ops.EPI_DGELU, aux=pre, colsum=db1)   # dgrad fc2 . gelu'
-    if SIDE_POLICY == 0:
-        on_side(lambda: ops.gemm_tn(dpre, bln, dW1, accumulate=False, splits=_tn_splits(dW1), form=_tn_form("fc1")), dpre, bln, dW1)
-    if SIDE_POLICY == 2:
-        on_side(wgrad_fc2, dy2, h, dW2, db2)
+    # the MLP weight gradients enter the side stream as soon as their inputs exist, beside the input-gradient GEMMs (holding them back until
+    # after dgrad-fc1, beside LayerNorm / attention backward, measured equal or up to 0.4 ms slower: DESIGN.md section 4)
+    on_side(wgrad_fc2, dy2, h, dW2, db2)
+    dpre = ops.gemm_nt(dy2, w2_t, ops.EPI_DMUL, aux=pre, colsum=db1)             # dgrad fc2 . gelu' (stored by the forward in `pre`)
+    on_side(lambda: ops.gemm_tn(dpre, bln, dW1, accumulate=False, splits=_tn_splits(dW1), form=_tn_form("fc1")), dpre, bln, dW1)
     dbln = ops.gemm_nt(dpre, w1_t, ops.EPI_BIAS_BF16)                            # dgrad fc1
-    if SIDE_POLICY == 1:
-        on_side(wgrad_fc2, dy2, h, dW2, db2)
-    if SIDE_POLICY in (1, 2):
-        on_side(lambda: ops.gemm_tn(dpre, bln, dW1, accumulate=False, splits=_tn_splits(dW1), form=_tn_form("fc1")), dpre, bln, dW1)
-    g1, d_o = ops.layernorm_bwd(dbln, x1, mean2, rstd2, g_res=g2, want_bf16=True, xhat=bln if LN_BWD_XHAT else None)
+    # LayerNorm backward reads xhat from the saved bf16 LN output instead of recomputing it from fp32 x
+    g1, d_o = ops.layernorm_bwd(dbln, x1, mean2, rstd2, g_res=g2, want_bf16=True, xhat=bln)
     # ---- attention
     dqkv = ops.attention_bwd(qkv, o, lse, d_o, B, N, H, causal, dbias=dbqkv, dropout=drop[:2])   # also adds the QKV bias gradient
     on_side(lambda: ops.gemm_tn(dqkv, a, dWqkv, accumulate=False, splits=_tn_splits(dWqkv), form=_tn_form("qkv")), dqkv, a, dWqkv)
     da = ops.gemm_nt(dqkv, wqkv_t, ops.EPI_BIAS_BF16)                            # dgrad qkv
     g0, g0b = ops.layernorm_bwd(da, x0, mean1, rstd1, g_res=g1, want_bf16=emit_bf16, colsum=emit_colsum, dropout=emit_dropout,
-                                xhat=a if LN_BWD_XHAT else None)
+                                xhat=a)
     return g0, g0b
 
 

@@ -67,31 +67,14 @@ class VitamdError(RuntimeError):
     pass
 
 
-EXP_LIB_PATH = os.path.join(_HERE, "libvitamd_exp.so")
-
-
-def build(verbose: bool = False, experimental: bool = False) -> str:
-    """Compile libvitamd.so for gfx950 with hipcc (cross-compiles without a GPU).  experimental=True also builds libvitamd_exp.so: the
-    same sources with -DVITAMD_EXPERIMENTAL (measured alternative kernels + vitamd_set_debug) for the A/B tools under tools/ - those
-    call build(experimental=True) themselves through use_experimental().  The product and its tests load libvitamd.so only."""
-    for args in ([], ["EXPERIMENTAL=1"])[: 2 if experimental else 1]:
-        r = subprocess.run(["make", "-C", CSRC, "-j8", *args], capture_output=True, text=True)
-        if verbose or r.returncode != 0:
-            print(r.stdout[-4000:], r.stderr[-4000:])
-        if r.returncode != 0:
-            raise VitamdError("building libvitamd%s.so failed" % ("_exp" if args else ""))
+def build(verbose: bool = False) -> str:
+    """Compile libvitamd.so for gfx950 with hipcc (cross-compiles without a GPU)."""
+    r = subprocess.run(["make", "-C", CSRC, "-j8"], capture_output=True, text=True)
+    if verbose or r.returncode != 0:
+        print(r.stdout[-4000:], r.stderr[-4000:])
+    if r.returncode != 0:
+        raise VitamdError("building libvitamd.so failed")
     return LIB_PATH
-
-
-def use_experimental():
-    """A/B tools only: make load() return libvitamd_exp.so (alternative kernels behind extra `tile` codes, vitamd_set_debug).
-    Must be called before the first load()."""
-    global LIB_PATH
-    if _lib is not None:
-        raise VitamdError("use_experimental() must come before the first load()")
-    if not os.path.exists(EXP_LIB_PATH):
-        build(experimental=True)
-    LIB_PATH = EXP_LIB_PATH
 
 
 def hip_runtimes(maps_path="/proc/self/maps"):
@@ -131,10 +114,6 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     check_single_hip_runtime()
-    if LIB_PATH == EXP_LIB_PATH:
-        for dbg in (lib.vitamd_set_debug, lib.vitamd_set_debug2):
-            dbg.argtypes = [ctypes.c_int]
-            dbg.restype = ctypes.c_int
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
