@@ -183,6 +183,25 @@ long vitamd_gemm_skinny_ws_bytes(int M, int N, int K);
 int vitamd_gemm_skinny_bf16(const void* A, const void* W, void* out, void* out2, const float* bias, const float* aux, int M, int N,
                             int K, int epi, float* ws, long ws_bytes, void* stream);
 
+/* Sampled generation: one token per row of fp32 logits [B, V] (row stride ld >= V elements, 2 <= V <= 65536, else VITAMD_ERR_SHAPE), in one
+ * launch, one workgroup per row, in the order of the usual logits processors:
+ *   1. z = x / temperature (temperature > 0);
+ *   2. top-k: K = { i : z_i >= the k-th largest z } when 0 < top_k < V, else every i; ties with the k-th value are all kept;
+ *   3. top-p (0 < top_p <= 1): q = softmax of z over K, t = the largest value v with sum_{i in K, z_i >= v} q_i >= top_p,
+ *      S = { i in K : z_i >= t } (ties with t all kept, never empty); top_p = 1: S = K;
+ *   4. draw: the first i of S, in ascending index order, whose running sum of q over S exceeds u * sum_S q.
+ * -inf logits are legal (never kept, zero mass); a row holds at least one finite logit; NaN / +inf are the caller's error.
+ * u fp32 [B] in [0, 1), or NULL: then u = (first word of Philox4x32-10 >> 8) * 2^-24 with key = seed (low word, high word) and counter =
+ * (row, 0, *step low, *step high); step is a DEVICE uint64 read by the kernel (NULL = 0) that the caller advances between calls, so a draw
+ * never needs the host and a captured decode step replays with fresh numbers.
+ * token int64 [B]; info (may be NULL) fp32 [B, 4] = (the smallest kept logit, |S|, sum_S / sum_all of the temperature softmax, q(token)
+ * renormalised over S).  Logits are compared as they are (never after the division) and the softmax weights are summed as 2^-40
+ * fixed-point integers: no result depends on an order of summation, every call gives the same bits.
+ * temperature, top_k or top_p out of range, or a missing pointer: VITAMD_ERR_ARG (after the shape check).
+ * replaces the `torch.argmax` of train_videogpt.py:63 where a sampled continuation is wanted (the reference has no sampler). */
+int vitamd_sample_logits(const float* logits, long long* token, float* info, const float* u, const unsigned long long* step, int B, int V,
+                         int ld, float temperature, int top_k, float top_p, unsigned long long seed, void* stream);
+
 /* ---- helpers around the GEMMs ---------------------------------------------------------------- */
 /* fp32 -> bf16 (autocast's per-step weight / activation cast, train_vit.py:100). */
 int vitamd_cast_f32_bf16(const float* in, void* out_bf16, long n, void* stream);

@@ -2,6 +2,8 @@
 64 tokens per frame, 1024 codes, 16 frames, 8 conditioning frames, batch 32): prints one JSON line.
 
   cached      - one whole VideoGPT.generate_frames call (prefill of 513 positions + 511 decode steps), ms per generated token and tokens/s
+  sampled     - the same call with temperature=1.0, top_k=100, top_p=0.95 (one sampling kernel + one counter add per token in place of the
+                argmax), timed in rounds interleaved with the greedy ones
   uncached    - the reference's loop (the whole prefix through the stack per token, on the HIP stack), timed for single steps at prefix
                 lengths spread over the run (513 .. 1024) and averaged: ms per generated token
   kernels     - hipEvent time of each decode kernel at the shapes of one decode step, against its HBM byte floor (skinny GEMMs: the weight
@@ -52,14 +54,23 @@ def main():
     # ---- cached: whole generate_frames calls
     out = model.generate_frames(video, n=FRAMES - COND)            # warm-up (code objects, allocator, weight cache)
     torch.cuda.synchronize()
-    times = []
-    for _ in range(args.reps):
+    SAMPLING = dict(temperature=1.0, top_k=100, top_p=0.95)
+    model.generate_frames(video, n=FRAMES - COND, seed=0, **SAMPLING)
+    torch.cuda.synchronize()
+    times, times_s = [], []
+    for r in range(args.reps):                                     # greedy and sampled rounds interleaved: one process, one clock state
         t0 = time.perf_counter()
         out = model.generate_frames(video, n=FRAMES - COND)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        model.generate_frames(video, n=FRAMES - COND, seed=r, **SAMPLING)
+        torch.cuda.synchronize()
+        times_s.append(time.perf_counter() - t0)
     t_cached = sorted(times)[len(times) // 2]
+    t_sampled = sorted(times_s)[len(times_s) // 2]
     cached_ms_tok = t_cached * 1e3 / n_gen
+    sampled_ms_tok = t_sampled * 1e3 / n_gen
 
     # ---- uncached: single steps of the reference loop at prefix lengths spread over the run
     toks = out[:, : S0 + n_gen - 1]
@@ -103,11 +114,19 @@ def main():
     length = torch.tensor([S0], dtype=torch.int32, device="cuda")
     rec("kv_append[T=1]", lambda: ops.kv_append(qkv, kc, vc, length, B, 1, H), 2 * 2 * B * D * 2)
 
+    for V in (1024, 16384):
+        lg = torch.randn(B, V, device="cuda") * 3
+        rec(f"sample_logits[{B}x{V}]", lambda: ops.sample_logits(lg, **SAMPLING), B * V * 4)
+    lg = torch.randn(B, CODES, device="cuda") * 3
+    kern["argmax[32x1024]"] = {"us": round(_events_ms(lambda: torch.argmax(lg, dim=-1, keepdim=True), 50) * 1e3, 2)}      # what greedy launches instead
+
     print(json.dumps({
         "config": {"preset": "B", "frame_size": FRAME, "codebook": CODES, "max_frames": FRAMES, "condition_frames": COND, "batch": B,
                    "generated_tokens_per_sequence": n_gen},
         "cached": {"generate_frames_s": round(t_cached, 4), "ms_per_token": round(cached_ms_tok, 4),
                    "tokens_per_s": round(B * n_gen / t_cached, 1)},
+        "sampled": dict(SAMPLING, generate_frames_s=round(t_sampled, 4), ms_per_token=round(sampled_ms_tok, 4),
+                        tokens_per_s=round(B * n_gen / t_sampled, 1), over_cached=round(sampled_ms_tok / cached_ms_tok, 4)),
         "uncached": {"ms_per_token": round(uncached_ms_tok, 3), "step_ms_by_length": step_ms,
                      "generate_frames_s_estimate": round(uncached_ms_tok * n_gen / 1e3, 3)},
         "speedup": round(uncached_ms_tok / cached_ms_tok, 2),

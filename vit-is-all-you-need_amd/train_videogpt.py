@@ -3,8 +3,9 @@ VideoGPTConfig and VideoGPT with the same constructor signatures, attributes and
 `pos_embed.weight`, `transformer.layers.*` including the causal `mask` buffers, `proj.{weight,bias}`), so reference checkpoints load.
 
 The causal stack runs on the HIP kernels (transformer.Transformer -> TransformerStackFn), the output projection on the MFMA GEMMs
-(functions.linear in forward, the skinny-M GEMM with fp32 logits in generate); the embedding gathers, the cross-entropy and the argmax
-are torch device ops (as the loss is in train_vit.train_step).  `generate` adds a KV cache (vitamd/decode.py): the prompt is prefilled
+(functions.linear in forward, the skinny-M GEMM with fp32 logits in generate); the embedding gathers, the cross-entropy and the greedy
+argmax are torch device ops (as the loss is in train_vit.train_step); sampled generation (temperature / top-k / top-p) draws each token
+in one HIP kernel (csrc/sample.hip).  `generate` adds a KV cache (vitamd/decode.py): the prompt is prefilled
 once and every further token costs one single-row pass through the stack.  The reference's training loop and its external TiTok
 video tokenizer (train_videogpt.py:68-150) are not part of this module."""
 from dataclasses import dataclass
@@ -82,32 +83,54 @@ class VideoGPT(nn.Module):
                              "in eval mode too, which a KV cache cannot reproduce; use use_cache=False")
         return bool(use_cache)
 
+    def _sampler(self, temperature, top_k, top_p, seed):
+        """None when all three are None (greedy), else the Sampler of one generate call; parameter errors as ValueError, no device work"""
+        if temperature is None and top_k is None and top_p is None:
+            return None
+        from vitamd import ops as _ops
+        from vitamd.sampling import Sampler
+        sampler = Sampler(1.0 if temperature is None else temperature, 0 if top_k is None else top_k, 1.0 if top_p is None else top_p, seed)
+        _ops.check_sampling(sampler.temperature, sampler.top_k, sampler.top_p, self.config.codebook_size)
+        return sampler
+
     @torch.no_grad()
-    def generate(self, tokens, n=1, use_cache=None):
-        """Greedy continuation of tokens [B, S] by n tokens -> [B, S + n] (train_videogpt.py:54-63).  use_cache: None = cached when
-        dropout == 0; False = the reference's loop (the whole prefix through the stack per token) on the HIP stack."""
+    def generate(self, tokens, n=1, use_cache=None, *, temperature=None, top_k=None, top_p=None, seed=0):
+        """Continuation of tokens [B, S] by n tokens -> [B, S + n] (train_videogpt.py:54-63).  use_cache: None = cached when
+        dropout == 0; False = the reference's loop (the whole prefix through the stack per token) on the HIP stack.
+        temperature / top_k / top_p all None: greedy (the reference's argmax).  Any of them given: sampled on the device, one kernel
+        launch per token (vitamd.sampling.Sampler: temperature -> top-k -> top-p -> draw; the others default to 1.0 / 0 / 1.0 = off),
+        token t of the continuation drawn at position t of the Philox stream of `seed` on either loop: one seed, one continuation."""
         B, S = tokens.shape
         if n < 1:
             return tokens
         if S + n > self.config.max_tokens:
             raise ValueError(f"generate: {S} + {n} tokens need {S + n} positions, the model has max_tokens = {self.config.max_tokens}")
-        if not self._use_cache(use_cache):
+        cached = self._use_cache(use_cache)
+        sampler = self._sampler(temperature, top_k, top_p, seed)
+
+        def pick(logits):
+            if sampler is None:
+                return torch.argmax(logits, dim=-1, keepdim=True)
+            return sampler(logits).unsqueeze(-1)
+
+        if not cached:
             for _ in range(n):
                 h = self.transformer(self._embed(torch.cat([self._sos(B, tokens.device), tokens], dim=-1)))
-                nxt = torch.argmax(self._head(h[:, -1]), dim=-1, keepdim=True)
+                nxt = pick(self._head(h[:, -1]))
                 tokens = torch.cat([tokens, nxt], dim=-1)
             return tokens
         cache = self.transformer.new_cache(B, max_len=S + n)
         h = self.transformer.forward_cached(self._embed(torch.cat([self._sos(B, tokens.device), tokens], dim=-1)), cache)   # prefill
         out = [tokens]
         for step in range(n):
-            nxt = torch.argmax(self._head(h[:, -1]), dim=-1, keepdim=True)
+            nxt = pick(self._head(h[:, -1]))
             out.append(nxt)
             if step + 1 < n:
                 h = self.transformer.forward_cached(self._embed(nxt, pos0=cache.len), cache)
         return torch.cat(out, dim=-1)
 
-    def generate_frames(self, video_tokens, n=1, use_cache=None):
+    def generate_frames(self, video_tokens, n=1, use_cache=None, *, temperature=None, top_k=None, top_p=None, seed=0):
         """video_tokens [B, T, N] -> [B, T*N + n*frame_size] (train_videogpt.py:64-66)"""
         B, T, N = video_tokens.shape
-        return self.generate(video_tokens.reshape(B, T * N), n * self.config.frame_size, use_cache=use_cache)
+        return self.generate(video_tokens.reshape(B, T * N), n * self.config.frame_size, use_cache=use_cache, temperature=temperature,
+                             top_k=top_k, top_p=top_p, seed=seed)

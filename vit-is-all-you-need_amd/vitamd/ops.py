@@ -530,3 +530,51 @@ def gemm_skinny(a, w, epi, *, bias=None, aux=None, out=None):
                                         _p(ws), 0 if ws is None else ws.numel() * 4, _stream())
     _lib.check(code, f"gemm_skinny[M={M},N={N},K={K},epi={epi}]")
     return (out, out2) if epi == EPI_GELU else out
+
+
+# ------------------------------------------------------------------------------------------ sampled generation
+SAMPLE_MAX_V = 65536      # include/vitamd.h vitamd_sample_logits
+
+
+def check_sampling(temperature, top_k, top_p, V=None):
+    """The parameter rules of sample_logits, as ValueError (no device is looked at)."""
+    if not (isinstance(temperature, (int, float)) and 0 < temperature < float("inf")):
+        raise ValueError(f"sampling: temperature must be a finite number > 0, got {temperature!r}")
+    if not (isinstance(top_k, int) and not isinstance(top_k, bool) and top_k >= 0):
+        raise ValueError(f"sampling: top_k must be an integer >= 0 (0 = off), got {top_k!r}")
+    if not (isinstance(top_p, (int, float)) and 0 < top_p <= 1):
+        raise ValueError(f"sampling: top_p must be in (0, 1] (1 = off), got {top_p!r}")
+    if V is not None and not 2 <= V <= SAMPLE_MAX_V:
+        raise ValueError(f"sampling: the vocabulary must hold 2 .. {SAMPLE_MAX_V} entries, got {V}")
+
+
+def sample_logits(logits, temperature=1.0, top_k=0, top_p=1.0, *, u=None, seed=0, step=None, return_info=False):
+    """One token per row of logits fp32 [B, V] (unit inner stride; the row stride may exceed V): temperature -> top-k (0 = off) -> top-p
+    (1 = off) -> draw, in one kernel launch and without host synchronisation (semantics: include/vitamd.h vitamd_sample_logits).
+    u: fp32 [B] in [0, 1), the caller's uniform numbers; None = Philox4x32-10 keyed by `seed`, counter (row, step), with `step` a device
+    uint64 [1] read by the kernel (None = 0) that the caller advances (Sampler does).  -> tokens int64 [B], and with return_info the kernel's
+    account of its decision, fp32 [B, 4] = (smallest kept logit, number kept, kept share of the softmax mass, probability of the token)."""
+    V = logits.shape[-1] if isinstance(logits, torch.Tensor) and logits.dim() == 2 else None
+    check_sampling(temperature, top_k, top_p, V)
+    if not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"sampling: seed must be an integer in [0, 2^64), got {seed!r}")
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise _lib.VitamdError("logits: expected a ROCm device tensor (the HIP kernels are the only implementation)")
+    if logits.dtype != F32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise _lib.VitamdError(f"logits: expected fp32 [B, V] with unit inner stride, got {logits.dtype} {tuple(logits.shape)} strides {logits.stride()}")
+    B, V = logits.shape
+    if B < 1:
+        raise _lib.VitamdError("logits: expected at least one row")
+    if u is not None:
+        _need(u, F32, "u", 1)
+        if u.numel() != B:
+            raise _lib.VitamdError(f"u: expected {B} elements, got {u.numel()}")
+    if step is not None:
+        _need(step, torch.uint64, "step")
+        if step.numel() != 1:
+            raise _lib.VitamdError("step: expected a one-element device uint64")
+    token = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    info = torch.empty((B, 4), dtype=F32, device=logits.device) if return_info else None
+    _lib.check(_L().vitamd_sample_logits(_p(logits), _p(token), _p(info), _p(u), _p(step), B, V, logits.stride(0), float(temperature), int(top_k),
+                                         float(top_p), seed, _stream()), f"sample_logits[B={B},V={V},T={temperature},top_k={top_k},top_p={top_p}]")
+    return (token, info) if return_info else token
