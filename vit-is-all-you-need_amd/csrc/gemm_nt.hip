@@ -8,6 +8,7 @@
 //                       every SIMD in its matrix section while its partner reads LDS and issues DMA.  Every large GEMM of the step.
 //   gemm_nt_seam_kernel persistent ping-pong kernel that requests the next tile's pipeline fill before the epilogue (gemm_nt_seam.h).
 //   gemm_nt_ld_kernel   eight compute waves fed by four loader waves, 256-row tiles (gemm_nt_ld.h).
+//   (gemm_nt_pp.h: request schedule, operand offsets and K-tile body of the first two; tile walk, fragment bases and launch helper of all three.)
 //   gemm_nt_kernel      128 x 128 x 64 plain double-buffered kernel for small problems (classifier head, tiny models).
 // Epilogues (gemm_nt_epilogue.h): gemm_epilogue_rows (LDS-transposed, row-major 16-B accesses), gemm_epilogue (direct; small tiles, fp32).
 // plan_single below picks the form.  The measured alternatives of rounds 1-4 were removed; DESIGN.md section 4 holds their numbers.
@@ -16,7 +17,8 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
-#include "gemm_nt_epilogue.h"
+#include <climits>
+#include "gemm_nt_ld.h"      // and through it gemm_nt_seam.h, gemm_nt_pp.h, gemm_nt_epilogue.h
 
 namespace {
 
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNtArgs 
 //     every LDS region is read in ONE known phase and is free long before the K-tile ends.
 //   * every phase requests one A piece LA phases ahead of its use and (most phases) one B piece LB phases ahead, into the region
 //     the same part of two K-tiles earlier left.  Waits are COUNTED (never 0 in the loop): the count per phase is computed at
-//     compile time from the request schedule (PpSchedule below).
+//     compile time from the request schedule (gemm_nt_pp.h::NtSchedule).
 //   * phase = [ds_reads | DMA requests | counted wait] s_barrier [16 MFMAs, s_setprio 1] s_barrier; the second wave row (waves 4-7,
 //     the second wave of every SIMD) runs ONE barrier behind the first, so on every SIMD one wave feeds the matrix pipe while its
 //     partner reads LDS and issues DMA (cdna_hip_programming.md section 5, the 8-phase template).
@@ -132,36 +134,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNtArgs 
 // Requests for K-tiles that do not exist (before the first, past the last) are issued out of range (zero fill, no traffic) so the
 // counts are the same in every phase.  The DMA is issued from inline asm (common.h::asm_glds16): hipcc would otherwise put
 // vmcnt(0) in front of every ds_read.
-template <int NP, int LA, int LB>
-struct PpSchedule {
-  // phase p of K-tile t issues: A-part (p + LA) % NP of K-tile t + (p + LA) / NP ; and B piece q = (p + LB) % NP (if q < 4) of K-tile
-  // t + (p + LB - q) / NP.  Program order inside a phase: A request, then B request.
-  static constexpr int a_part(int p) { return (p + LA) % NP; }
-  static constexpr int a_tile(int p) { return (p + LA) / NP; }
-  static constexpr int b_piece(int p) { return (p + LB) % NP < 4 ? (p + LB) % NP : -1; }
-  static constexpr int b_tile(int p) { return (p + LB - (p + LB) % NP) / NP; }
-  // outstanding requests allowed after phase p's requests so that everything first read in phase p+1 has landed
-  static constexpr int wait(int p) {
-    int allowed = 0;
-    for (int d = 0; d < 4 * NP; ++d) {          // walk back over the phases p, p-1, ... (program order reversed: B then A)
-      const int ph = ((p - d) % NP + NP) % NP;
-      if (b_piece(ph) >= 0) {
-        if (d + 1 >= LB - b_piece(ph)) return allowed;      // needed in phase (p-d) + LB - q <= p+1
-        ++allowed;
-      }
-      if (d + 1 >= LA) return allowed;                         // A request of phase p-d is needed in phase p-d+LA <= p+1
-      ++allowed;
-    }
-    return allowed;
-  }
-  static constexpr int lookback = (LA > LB ? LA : LB);          // phases before the first whose requests the prologue replays
-};
-
 template <int EPI, int MT, int LA, int LB, bool PERS = false>     // PERS: one workgroup per CU walks a strided list of tiles (the automatic choice for large problems)
 __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmNtArgs p) {
-  constexpr int NP = MT / 2;
-  static_assert(MT % 2 == 0 && LA >= 2 && LA <= 2 * NP - 2 && LB >= 5 && LB <= 2 * NP - 2, "request leads");
-  using S = PpSchedule<NP, LA, LB>;
+  using S = NtSchedule<MT, LA>;
+  static_assert(LB == S::LB, "the B lead the shared schedule implements");
+  constexpr int NP = S::NP;
   constexpr int BM = 32 * MT, BN = 256, WN = 4, NT = 4;
   constexpr int PART = 64 * 128;                  // bytes of an A-part
   constexpr int BUFB = NP * PART + 256 * 128;     // one K-tile buffer: A-parts, then the B block
@@ -177,27 +154,10 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmNtArgs p) {
   const srd_t srdA = make_srd(p.A, (size_t)p.M * K * 2);
   const srd_t srdB = make_srd(p.B, (size_t)p.N * K * 2);
   for (int ti = blockIdx.x; ti < ntiles; ti += PERS ? (int)gridDim.x : ntiles) {
-  const int tile = xcd_remap(ti, ntiles);
-  int tm, tn;
-  tile_coords(tile, tiles_m, tiles_n, tiles_n >= 6, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  // this wave's piece of A-part j: LDS rows 8*wave + (lane>>3) of the part = rows 32 j + (lr&31) of wave row lr>>5;
-  // its piece q of the B block: rows 64 q + 8*wave + (lane>>3).  16-B chunk lane&7, XOR (row&7) on the source side.
+  const NtTile t = nt_tile<BM>(ti, tiles_m, tiles_n);
+  const int m0 = t.m0, n0 = t.n0;
   unsigned voffA[NP], voffB[4];
-  {
-    const int lr = 8 * wave + (lane >> 3);
-    const unsigned chunk = (unsigned)(((lane & 7) ^ (lr & 7)) * 16);
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      const int ga = min(m0 + (lr >> 5) * (16 * MT) + j * 32 + (lr & 31), p.M - 1);     // clamp: rows past M are never stored
-      voffA[j] = (unsigned)ga * (unsigned)(K * 2) + chunk;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int gb = min(n0 + 64 * q + lr, p.N - 1);
-      voffB[q] = (unsigned)gb * (unsigned)(K * 2) + chunk;
-    }
-  }
+  pp_offsets<MT, false>(p, t, wave, lane, voffA, voffB);
   const unsigned lds0 = lds_addr(smem) + wave * 1024;
   constexpr unsigned OOB = 0x80000000u;
   auto request_a = [&](int kt, int j) {
@@ -215,63 +175,21 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmNtArgs p) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  // fragment reads: 16-row tile at LDS row rb: lane -> row rb + (lane&15), chunk ((lane>>4) + 4 ks) ^ (row&7); k-substep 1 flips
-  // chunk bit 2 = XOR 64 on the swizzled offset, hence one base pointer per substep
-  const int frag_off = (lane & 15) * 128 + ((((lane >> 4) ^ (lane & 7)) & 7) << 4);
-  const char* const rdA[2] = {smem + wm * 32 * 128 + frag_off, smem + wm * 32 * 128 + (frag_off ^ 64)};                    // + part*PART + i*2048 (+ buffer)
-  const char* const rdB[2] = {smem + NP * PART + wn * 64 * 128 + frag_off, smem + NP * PART + wn * 64 * 128 + (frag_off ^ 64)};   // + j*2048 (+ buffer)
+  const char *rdA[2], *rdB[2];
+  frag_bases(smem + wm * 32 * 128, lane, rdA);                  // + part*PART + i*2048 (+ buffer)
+  frag_bases(smem + NP * PART + wn * 64 * 128, lane, rdB);      // + j*2048 (+ buffer)
 
-#define VITAMD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-  // prologue: replay the requests of the S::lookback phases before phase 0 (those for K-tiles < 0 go out of range: the queue then
-  // looks exactly as in steady state and the same counted waits apply from the first phase on)
 #pragma unroll
-  for (int P = -S::lookback; P < 0; ++P) {
-    const int ph = ((P % NP) + NP) % NP, t = (P - ph) / NP;      // P = NP * t + ph, t < 0
-    request_a(t + S::a_tile(ph), S::a_part(ph));
-    if (S::b_piece(ph) >= 0) request_b(t + S::b_tile(ph), S::b_piece(ph));
-  }
+  for (int P = -S::lookback; P < 0; ++P) S::requests(S::tile_of(P), S::phase_of(P), request_a, request_b);
   VITAMD_WAIT_VM(S::wait(NP - 1));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if (wm == 1) __builtin_amdgcn_s_barrier();        // second wave row: one barrier behind from here on
 
-  bf16x8 bq[NT][2], af[2][2];
   auto ktile = [&](int kt, auto bufc) {
-    constexpr int BUF = decltype(bufc)::value;
-#pragma unroll
-    for (int ph = 0; ph < NP; ++ph) {
-      // ---- read section
-      if (ph == 0) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) bq[j][ks] = *(const bf16x8*)(rdB[ks] + BUF * BUFB + j * 2048);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) af[i][ks] = *(const bf16x8*)(rdA[ks] + BUF * BUFB + ph * PART + i * 2048);
-      request_a(kt + S::a_tile(ph), S::a_part(ph));
-      if (S::b_piece(ph) >= 0) request_b(kt + S::b_tile(ph), S::b_piece(ph));
-      VITAMD_WAIT_VM(S::wait(ph));
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- matrix section: A-part ph x the whole B block
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            acc[2 * ph + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[j][ks], af[i][ks], acc[2 * ph + i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    }
+    constexpr int BUF = decltype(bufc)::value;                  // the buffer is a compile-time constant of the twice-unrolled loop
+    pp_ktile<MT, PART>(acc, rdA[0] + BUF * BUFB, rdA[1] + BUF * BUFB, rdB[0] + BUF * BUFB, rdB[1] + BUF * BUFB,
+                       [&](int ph) { S::requests(kt, ph, request_a, request_b); }, [&](int ph) { VITAMD_WAIT_VM(S::wait(ph)); });
   };
   int kt = 0;
   for (; kt + 1 < nkt; kt += 2) {
@@ -281,7 +199,6 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmNtArgs p) {
   if (kt < nkt) ktile(kt, std::integral_constant<int, 0>{});
   if (wm == 0) __builtin_amdgcn_s_barrier();        // balance the stagger
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // past-the-end requests (zeros) land before the epilogue reuses LDS
-#undef VITAMD_WAIT_VM
   if constexpr (EPI == EPI_F32) gemm_epilogue<BN, 2, WN, 16 * MT, 64, MT, NT, EPI>(p, acc, m0, n0, wm, wn, lane, tid, smem);
   else if (p.N % 8 == 0 && p.ldo % 8 == 0) gemm_epilogue_rows<EPI, MT>(p, acc, m0, n0, wm, wn, lane, tid, wave, smem);
   else gemm_epilogue<BN, 2, WN, 16 * MT, 64, MT, NT, EPI>(p, acc, m0, n0, wm, wn, lane, tid, smem);
@@ -302,16 +219,10 @@ static int device_cus() {          // CU count of the current device (persistent
 
 template <int EPI, int MT, int LA, int LB, bool PERS = false>
 int launch_pp(const GemmNtArgs& p, hipStream_t stream) {
-  constexpr int BM = 32 * MT;
   constexpr int ops_b = 2 * ((MT / 2) * 8192 + 32768), epi_b = 8 * MT * 2048;     // operand buffers / epilogue images
-  constexpr int lds = ops_b > epi_b ? ops_b : epi_b;
-  auto kern = gemm_nt_pp_kernel<EPI, MT, LA, LB, PERS>;
-  if (int e = set_lds(kern, lds)) return e;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + 255) / 256);
-  const int cus = PERS ? device_cus() : tiles;
-  hipLaunchKernelGGL(kern, dim3(PERS && tiles > cus ? cus : tiles), dim3(512), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return launch_tiles(gemm_nt_pp_kernel<EPI, MT, LA, LB, PERS>, p, stream, 32 * MT, 512, ops_b > epi_b ? ops_b : epi_b, PERS ? device_cus() : INT_MAX);
 }
+#undef VITAMD_WAIT_VM
 
 template <int BM, int BN, int WM, int WN, int EPI>
 int launch(const GemmNtArgs& p, hipStream_t stream) {
@@ -334,9 +245,6 @@ static bool prefer_tall(const GemmNtArgs& p) {
   const long r256 = (((p.M + 255) / 256) * tn + 255) / 256, r320 = (((p.M + 319) / 320) * tn + 255) / 256;
   return r320 * 320 <= r256 * 256;     // ties go to the tall tile: 142 instead of 128 FLOP per staged byte (whole-step A/B: -0.5 ms on the N = 3072 GEMMs alone)
 }
-
-#include "gemm_nt_seam.h"
-#include "gemm_nt_ld.h"
 
 // bf16 nearest-even of a double, decided on exact distances (no float intermediate rounding)
 static unsigned short bf16_rne_d(double v) {
@@ -412,8 +320,7 @@ int vitamd_init_impl(int device, hipStream_t stream) {
 namespace {
 
 // ---- which kernel a launch takes (one place: the dispatcher below executes the plan, vitamd_gemm_nt_plan reports it) -------------------------
-// tile selector of the C ABI: 0 = auto, 128 = the 128x128 kernel, 256 / 320 = the ping-pong kernel on 256- / 320-row tiles, one workgroup per
-// tile; 512 = auto without persistent launches; 1024 = auto with persistent launches but without the seam form; 2048 = the loader-wave form.
+// the tile selector of the C ABI: NtTileCode (vitamd_internal.h)
 enum NtForm { NT_FORM_SMALL = 1, NT_FORM_PP = 2, NT_FORM_PP_PERSISTENT = 3, NT_FORM_SEAM = 4, NT_FORM_LOADER = 5 };
 struct NtPlan { int form, rows, err; };
 
@@ -422,19 +329,19 @@ static NtPlan plan_single(const GemmNtArgs& p) {
   const int epi = p.epi;
   const bool seam_epi = epi == EPI_BIAS_BF16 || epi == EPI_GELU || epi == EPI_DGELU;
   const bool tall_epi = seam_epi || epi == EPI_RESID_F32;
-  if (tile == 2048) return (seam_epi && ld_ok(p)) ? NtPlan{NT_FORM_LOADER, 256, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
-  const bool no_seam = tile == 1024;      // ABI code 1024: the automatic choice with persistent launches but WITHOUT the seam / loader forms (A/B and start-up probe: ops.seam_probe)
-  if (no_seam) tile = 0;
+  if (tile == NT_TILE_LOADER) return (seam_epi && ld_ok(p)) ? NtPlan{NT_FORM_LOADER, 256, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
+  const bool no_seam = tile == NT_TILE_AUTO_NO_SEAM;      // the automatic choice with persistent launches but WITHOUT the seam / loader forms (A/B and start-up probe: ops.seam_probe)
+  if (no_seam) tile = NT_TILE_AUTO;
   const long big_tiles = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
   const bool pp_ok = (size_t)p.M * p.K * 2 < 0xf0000000ull && (size_t)p.N * p.K * 2 < 0xf0000000ull && p.K % 64 == 0;
   const bool big = p.N >= 256 && big_tiles >= 192 && pp_ok;
   const bool tall = tall_epi && prefer_tall(p);
   // Automatic choice, more tiles than CUs: the PERSISTENT form (one workgroup per CU walking a strided tile list; same kernel, same
   // results).  Alone it is as fast as one workgroup per tile; inside the training step, next to the weight-gradient GEMMs of the
-  // second stream, it is faster: -0.45 / -0.04 / -0.34 / -0.45 ms per step on four boxes (tools/ab_persistent.py).  The explicit
+  // second stream, it is faster: -0.45 / -0.04 / -0.34 / -0.45 ms per step on four boxes.  The explicit
   // tile codes 256 / 320 keep the one-workgroup-per-tile launch.
-  if (tile == 512) tile = 0;              // ABI code 512: the automatic choice WITHOUT persistent launches (one workgroup per tile)
-  else if (tile == 0 && big) {
+  if (tile == NT_TILE_AUTO_NO_PERSISTENT) tile = NT_TILE_AUTO;              // the automatic choice WITHOUT persistent launches (one workgroup per tile)
+  else if (tile == NT_TILE_AUTO && big) {
     const int cus = device_cus();
     // Short K loops with several tiles per CU: the SEAM form of the persistent kernel (gemm_nt_seam.h: the next tile's pipeline fill is requested
     // before the epilogue, the epilogue runs beside the operand buffers).  Measured on the ViT-B launches (tools/bench_seam.py): QKV 172 -> 163 us,
@@ -452,10 +359,10 @@ static NtPlan plan_single(const GemmNtArgs& p) {
     }
     return NtPlan{NT_FORM_PP_PERSISTENT, tall ? 320 : 256, VITAMD_OK};
   }
-  if (tile == 0) tile = big ? (tall ? 320 : 256) : 128;
-  if (tile == 320) return (tall_epi && pp_ok) ? NtPlan{NT_FORM_PP, 320, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
-  if (tile == 256) return pp_ok ? NtPlan{NT_FORM_PP, 256, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
-  if (tile != 128) return NtPlan{0, 0, VITAMD_ERR_ARG};
+  if (tile == NT_TILE_AUTO) tile = big ? (tall ? NT_TILE_320 : NT_TILE_256) : NT_TILE_128;
+  if (tile == NT_TILE_320) return (tall_epi && pp_ok) ? NtPlan{NT_FORM_PP, 320, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
+  if (tile == NT_TILE_256) return pp_ok ? NtPlan{NT_FORM_PP, 256, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
+  if (tile != NT_TILE_128) return NtPlan{0, 0, VITAMD_ERR_ARG};
   return p.K % BK == 0 ? NtPlan{NT_FORM_SMALL, 128, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
 }
 
@@ -508,13 +415,13 @@ static int dispatch_epi(const GemmNtArgs& p, hipStream_t stream) {
 // direct-store GELU epilogue costs more than the 0.6 idle round).
 static int tail_split_rows(const GemmNtArgs& p, bool& tall) {       // rows of the head part, 0 = no split
   const int CUS = device_cus();
-  tall = (p.tile == 0 || p.tile == 512 || p.tile == 1024) && prefer_tall(p);
+  tall = is_auto(p.tile) && prefer_tall(p);
   const int bm = tall ? 320 : 256;
   const int tiles_m = (p.M + bm - 1) / bm, tiles_n = (p.N + 255) / 256;
   const long big_tiles = (long)tiles_m * tiles_n;
   const long rem = big_tiles % CUS;
   const bool split_on = p.epi == EPI_RESID_F32 && !tall;
-  if (!((p.tile == 0 || p.tile == 512 || p.tile == 1024) && split_on && p.epi != EPI_PATCH_F32 && p.N >= 256 && p.K % 64 == 0 && big_tiles > 2 * CUS && rem != 0 && rem * 10 < CUS * 6))
+  if (!(is_auto(p.tile) && split_on && p.epi != EPI_PATCH_F32 && p.N >= 256 && p.K % 64 == 0 && big_tiles > 2 * CUS && rem != 0 && rem * 10 < CUS * 6))
     return 0;
   const int rows_a = (int)((big_tiles - rem) / tiles_n) * bm;       // M-panels whose tiles fill whole rounds
   return rows_a > 0 && rows_a < p.M ? rows_a : 0;
@@ -542,14 +449,14 @@ int vitamd_gemm_nt_impl(const GemmNtArgs& p0, hipStream_t stream) {
   if (rows_a) {
     GemmNtArgs a = p, b = p;
     a.M = rows_a;
-    a.tile = tall ? p.tile : 256;                                   // (auto picks the 320-row form again for the head part)
+    a.tile = tall ? p.tile : NT_TILE_256;                                   // (auto picks the 320-row form again for the head part)
     const size_t esz_out = (p.epi == EPI_RESID_F32 || p.epi == EPI_F32) ? 4 : 2;
     b.M = p.M - rows_a;
     b.A = (const char*)p.A + (size_t)rows_a * p.K * 2;
     b.out = (char*)p.out + (size_t)rows_a * p.ldo * esz_out;
     if (p.out2) b.out2 = (char*)p.out2 + (size_t)rows_a * p.ldo * 2;
     if (p.aux) b.aux = (const char*)p.aux + (size_t)rows_a * p.ldo * (p.epi == EPI_RESID_F32 ? 4 : 2);
-    b.tile = 128;
+    b.tile = NT_TILE_128;
     b.row0 = p.row0 + rows_a;
     if (int e = dispatch_epi(a, stream)) return e;
     return dispatch_epi(b, stream);
@@ -566,7 +473,7 @@ int vitamd_gemm_nt_plan_impl(const GemmNtArgs& p0) {
   const int rows_a = tail_split_rows(p, tall);
   if (rows_a) {
     p.M = rows_a;
-    p.tile = tall ? p.tile : 256;
+    p.tile = tall ? p.tile : NT_TILE_256;
   }
   const NtPlan pl = plan_single(p);
   if (pl.err) return -pl.err;

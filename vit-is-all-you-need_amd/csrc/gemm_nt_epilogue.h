@@ -167,7 +167,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmNtArgs& p, f32x4 (&acc)[
 // ---------------------------------------------------------------------------------------------
 // Row-major epilogue for the 128x64 wave tile (8 waves, 256x256 block).  In the accumulator layout
 // a lane owns 4 columns of 16 different rows, so direct stores are 8-B pieces scattered over 16 rows:
-// the epilogue was store/load-ISSUE bound (tools/ablate_epilogue.py: the second GELU output cost
+// the epilogue was store/load-ISSUE bound (round-1 ablation: the second GELU output cost
 // 160 us, the residual read 148 us, the erf math 7 us).  Here each wave transposes its tile through
 // a private 16-KiB LDS image ([128 rows][64 bf16], 16-B chunk index XOR (row&7)), after which a lane
 // owns 8 consecutive columns of one row: every global access is 16 B per lane and a wave-instruction
@@ -322,5 +322,15 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmNtArgs& p, f32x4 (&
   }
 }
 
+// The erf-GELU table (16 KiB, gelu_lookup) copied into LDS by the first 512 threads of a persistent workgroup, once; visible to every wave after the
+// workgroup's next barrier.
+__device__ __forceinline__ void gelu_table_to_lds(const unsigned* tab, char* lds, int tid) {
+  const u32x4* src = (const u32x4*)tab + 2 * tid;
+  const u32x4 t0 = src[0], t1 = src[1];
+  u32x4* dst = (u32x4*)lds + 2 * tid;
+  dst[0] = t0;
+  dst[1] = t1;
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+}
 
 }  // namespace

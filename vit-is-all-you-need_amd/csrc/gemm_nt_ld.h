@@ -25,7 +25,6 @@
 // for in iterations (t, 3) [vmcnt(4): everything but A1(t + 1)] and (t + 1, 0) [vmcnt(6): everything but that phase's 6 new requests]: 2.5
 // phases in flight.  K % 128 == 0 (an even number of K-tiles: the buffer parity is a compile-time constant of the twice-unrolled loop).
 #pragma once
-#include "gemm_nt_epilogue.h"
 #include "gemm_nt_seam.h"
 
 namespace {
@@ -51,13 +50,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
   const int ntiles = tiles_m * tiles_n;
   const int K = p.K;
   const int nkt = K / 64;
-  struct Tile { int m0, n0; };
-  auto coords = [&](int ti) {
-    int tm, tn;
-    tile_coords(xcd_remap(ti, ntiles), tiles_m, tiles_n, tiles_n >= 6, tm, tn);
-    return Tile{tm * BM, tn * BN};
-  };
-#define VITAMD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
+  auto coords = [&](int ti) { return nt_tile<BM>(ti, tiles_m, tiles_n); };
 
   if (wave >= 8) {
     // ------------------------------------------------------------------------------------------------ loader waves
@@ -70,7 +63,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
     const unsigned ldsA = lds_addr(smem) + l * 4096;
     const unsigned ldsB = lds_addr(smem) + BBASE + l * 8192;
     unsigned voffA[2][4], voffB[8];
-    auto offsets = [&](const Tile& t) {
+    auto offsets = [&](const NtTile& t) {
       const int r8 = lane >> 3;
       const unsigned chunk = (unsigned)(((lane & 7) ^ r8) * 16);
 #pragma unroll
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
     };
     __builtin_amdgcn_s_setprio(3);                      // the loaders' few instructions go first: a late request costs every wave of the workgroup
     int ti = blockIdx.x;
-    Tile cur = coords(ti);
+    NtTile cur = coords(ti);
     offsets(cur);
     int bias_n0 = cur.n0;
     target(0, true);
@@ -177,18 +170,11 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
   const srd_t rsO = make_srd(p.out, (size_t)p.M * p.ldo * 2);
   const srd_t rsO2 = make_srd(EPI == EPI_GELU ? p.out2 : p.out, (size_t)p.M * p.ldo * 2);
   const srd_t srdAux = make_srd(EPI == EPI_DGELU ? p.aux : p.out, (size_t)p.M * p.ldo * 2);
-  if constexpr (TAB) {                                  // 16 KiB, once per (persistent) workgroup; visible to every wave after the START barrier
-    const u32x4* src = (const u32x4*)p.gelu_tab + 2 * tid;
-    const u32x4 t0 = src[0], t1 = src[1];
-    u32x4* dst = (u32x4*)(smem + TABOFF) + 2 * tid;
-    dst[0] = t0;
-    dst[1] = t1;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  }
+  if constexpr (TAB) gelu_table_to_lds(p.gelu_tab, smem + TABOFF, tid);      // visible to every wave after the START barrier
   __builtin_amdgcn_s_barrier();                         // START: the loaders waited for the first K-tile's B and A0
   asm volatile("" ::: "memory");
   for (int ti = blockIdx.x; ti < ntiles; ti += (int)gridDim.x) {
-    const Tile cur = coords(ti);
+    const NtTile cur = coords(ti);
     if (wm == 1) __builtin_amdgcn_s_barrier();          // second wave row: one barrier behind inside a tile
     f32x4 acc[MT][NT];
 #pragma unroll
@@ -196,13 +182,11 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
 #pragma unroll
       for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     {
-      // fragment reads: 16-row tile at LDS row rb: lane -> row rb + (lane & 15), chunk ((lane >> 4) + 4 ks) ^ (row & 7); K-half 1 flips chunk
-      // bit 2 = XOR 64 on the swizzled offset, hence one base per K-half
       int l2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-      asm volatile("" : "+v"(l2));                      // re-derived per tile, never carried across an epilogue
-      const int frag_off = (l2 & 15) * 128 + ((((l2 >> 4) ^ (l2 & 7)) & 7) << 4);
-      const char* const rdA[2] = {smem + wm * 8192 + frag_off, smem + wm * 8192 + (frag_off ^ 64)};                  // + buffer ABUF + h AREG + ii 2048
-      const char* const rdB[2] = {smem + BBASE + wn * 8192 + frag_off, smem + BBASE + wn * 8192 + (frag_off ^ 64)};  // + buffer BBUF + j 2048
+      asm volatile("" : "+v"(l2));                      // fragment bases re-derived per tile, never carried across an epilogue
+      const char *rdA[2], *rdB[2];
+      frag_bases(smem + wm * 8192, l2, rdA);            // + buffer ABUF + h AREG + ii 2048
+      frag_bases(smem + BBASE + wn * 8192, l2, rdB);    // + buffer BBUF + j 2048
       bf16x8 bq[NT], af[4];
       auto ktile = [&](auto bufc) {
         constexpr int BUF = decltype(bufc)::value;
@@ -240,6 +224,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
 
     // ---- epilogue: wave-private (no workgroup barrier; the loaders are already filling the next tile's K-tiles).  Lane roles from a fresh lane
     // id: values computed before the main loop would be kept in - or spilled from - registers across it.
+    // TWIN of the epilogue of gemm_nt_seam_kernel (gemm_nt_seam.h) with one slice per round: a change to one belongs in the other.
     // Accumulator layout: row mloc of a 16-row slice, columns 16 j + 4 g ..; row-major view: row rsub + 8 h, 16-B chunk pc.
     int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     asm volatile("" : "+v"(ln));
@@ -331,17 +316,12 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staging reads are done before the next tile's bias lands there (it is requested behind barriers this wave has yet to reach)
   }
-#undef VITAMD_WAIT_VM
 }
 
 template <int EPI, bool TAB = false, int SCHED = 1>
 int launch_ld(const GemmNtArgs& p, hipStream_t stream, int cus) {
-  auto kern = gemm_nt_ld_kernel<EPI, TAB, SCHED>;
   if (TAB && !p.gelu_tab) return VITAMD_ERR_ARG;
-  if (int e = set_lds(kern, 160 * 1024)) return e;
-  const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-  hipLaunchKernelGGL(kern, dim3(tiles > cus ? cus : tiles), dim3(768), 160 * 1024, stream, p);
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return launch_tiles(gemm_nt_ld_kernel<EPI, TAB, SCHED>, p, stream, 256, 768, 160 * 1024, cus);
 }
 
 // launch conditions of the loader form: the seam kernel's, and an even number of K-tiles

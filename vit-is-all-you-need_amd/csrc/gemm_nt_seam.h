@@ -18,59 +18,16 @@
 // C[M,N] = A[M,K] . B[N,K]^T with the bias / GELU / dGELU epilogues of gemm_nt_epilogue.h (reference transformer.py:21,37-39 and their
 // input gradients).  Tile (32 MT) x 256 x 64, MT = 8 or 10; schedule = gemm_nt_pp_kernel's (LA = 4, B leads 6,5,4,3), ring slots at run time.
 #pragma once
-#include "gemm_nt_epilogue.h"
+#include "gemm_nt_pp.h"
 
 namespace {
-
-// (A request-placement experiment of round 3 - the B request, or both requests, issued from inside the matrix section - measured slower everywhere
-// and was removed in round 4: profiles/r03/request_placement_experiment.log.)  Both requests of a phase are issued in its read section, ahead of the
-// phase's counted wait.
-template <int MT, int LA>
-struct SeamSchedule {
-  static constexpr int NP = MT / 2;
-  static_assert(MT % 2 == 0 && NP >= 4 && NP <= 5, "tile height");
-  static_assert(LA >= 2 && LA <= 2 * NP - 2, "A lead");
-  static constexpr int blead(int q) { return 6 - q; }
-  static constexpr int lookback = LA > 6 ? LA : 6;
-  static constexpr int prologue_requests() {       // LDS-DMA instructions per wave in one tile's prologue (the replayed lookback phases)
-    int n = 0;
-    for (int P = -lookback; P < 0; ++P) {
-      const int ph = ((P % NP) + NP) % NP;
-      ++n;
-      for (int q = 0; q < 4; ++q) n += ((ph + 6 - q) % NP == 0) ? 1 : 0;
-    }
-    return n;
-  }
-  static constexpr int a_part(int ph) { return (ph + LA) % NP; }
-  static constexpr int a_tile(int ph) { return (ph + LA) / NP; }
-  static constexpr bool b_here(int ph, int q) { return (ph + blead(q)) % NP == 0; }
-  static constexpr int b_tile(int ph, int q) { return (ph + blead(q)) / NP; }
-  // operations allowed outstanding after phase ph's requests so that everything first read in phase ph + 1 has landed.  E: operations the
-  // epilogue of the previous tile put between that tile's requests and this tile's phase 0 (first K-tile behind a seam only): they are
-  // younger than any request issued before the seam, so a wait for such a request leaves them outstanding too.
-  static constexpr int wait(int ph, int E = 0) {
-    int allowed = 0;
-    for (int d = 0; d < 4 * NP; ++d) {
-      const int f = ((ph - d) % NP + NP) % NP;
-      // reverse program order inside phase ph - d: its wait | [B requests] [A request]
-      for (int q = 3; q >= 0; --q)
-        if (b_here(f, q)) {
-          if (d + 1 >= blead(q)) return allowed + (d > ph ? E : 0);
-          ++allowed;
-        }
-      if (d + 1 >= LA) return allowed + (d > ph ? E : 0);
-      ++allowed;
-    }
-    return allowed;
-  }
-};
 
 template <int EPI, int MT, bool TAB = false>
 __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
   static_assert(EPI == EPI_BIAS_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU, "epilogues without (or with up-front) auxiliary loads");
   static_assert(!TAB || (EPI == EPI_GELU && MT == 8), "the GELU table needs the 16 KiB that only the 256-row ring leaves");
   constexpr int LA = 4;
-  using S = SeamSchedule<MT, LA>;
+  using S = NtSchedule<MT, LA>;
   constexpr int NP = S::NP;
   constexpr int BM = 32 * MT, BN = 256, WN = 4, NT = 4;
   constexpr int PART = 8192, ASLOT = NP * PART, BSLOT = 32768, BBASE = 2 * ASLOT, OPS = BBASE + 2 * BSLOT;
@@ -99,30 +56,11 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
   constexpr unsigned OOB = 0x80000000u;
   const unsigned lds0 = lds_addr(smem) + wave * 1024;
 
-  struct Tile { int m0, n0; };
-  auto coords = [&](int ti) {
-    int tm, tn;
-    tile_coords(xcd_remap(ti, ntiles), tiles_m, tiles_n, tiles_n >= 6, tm, tn);
-    return Tile{tm * BM, tn * BN};
-  };
   unsigned voffA[NP], voffB[4];
-  auto offsets = [&](const Tile& t) {
+  auto offsets = [&](const NtTile& t) {
     int l2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     asm volatile("" : "+v"(l2));                  // opaque (re-derived per tile, never carried across a main loop)
-    const int lr = 8 * wave + (l2 >> 3);                              // LDS row of this lane inside an A-part / a 64-row B piece
-    const unsigned chunk = (unsigned)(((l2 & 7) ^ (lr & 7)) * 16);      // 16-B chunk, XOR (row & 7) on the SOURCE side
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      unsigned o = (unsigned)min(t.m0 + (lr >> 5) * (16 * MT) + j * 32 + (lr & 31), p.M - 1) * (unsigned)(K * 2);
-      asm volatile("" : "+v"(o));                   // keeps the product a 32-bit v_mul_lo (hipcc otherwise forms v_mad_u64_u32: a register PAIR per offset)
-      voffA[j] = o + chunk;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      unsigned o = (unsigned)min(t.n0 + 64 * q + lr, p.N - 1) * (unsigned)(K * 2);
-      asm volatile("" : "+v"(o));
-      voffB[q] = o + chunk;
-    }
+    pp_offsets<MT, true>(p, t, wave, l2, voffA, voffB);
   };
   // K-tiles < 0 (prologue replay) and >= nkt (past the end) are requested out of range: zero fill, no traffic, same counts in every phase
   bool fill = true;            // false: the tile whose fill is being requested does not exist (last seam): every request goes out of range
@@ -136,30 +74,16 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
   };
   auto prologue = [&]() {      // the requests of the S::lookback phases before a tile's phase 0
 #pragma unroll
-    for (int P = -S::lookback; P < 0; ++P) {
-      const int ph = ((P % NP) + NP) % NP, t = (P - ph) / NP;
-      request_a(t + S::a_tile(ph), S::a_part(ph));
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (S::b_here(ph, q)) request_b(t + S::b_tile(ph, q), q);
-    }
+    for (int P = -S::lookback; P < 0; ++P) S::requests(S::tile_of(P), S::phase_of(P), request_a, request_b);
   };
 
-  const int frag_off = (lane & 15) * 128 + ((((lane >> 4) ^ (lane & 7)) & 7) << 4);
-  const char* const rdA[2] = {smem + wm * 32 * 128 + frag_off, smem + wm * 32 * 128 + (frag_off ^ 64)};
-  const char* const rdB[2] = {smem + BBASE + wn * 64 * 128 + frag_off, smem + BBASE + wn * 64 * 128 + (frag_off ^ 64)};
+  const char *rdA[2], *rdB[2];
+  frag_bases(smem + wm * 32 * 128, lane, rdA);
+  frag_bases(smem + BBASE + wn * 64 * 128, lane, rdB);
 
-#define VITAMD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-  if constexpr (TAB) {                               // 16 KiB, once per (persistent) workgroup; visible to every wave after the first barrier below
-    const u32x4* src = (const u32x4*)p.gelu_tab + 2 * tid;
-    const u32x4 t0 = src[0], t1 = src[1];
-    u32x4* dst = (u32x4*)(smem + TABOFF) + 2 * tid;
-    dst[0] = t0;
-    dst[1] = t1;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  }
+  if constexpr (TAB) gelu_table_to_lds(p.gelu_tab, smem + TABOFF, tid);      // visible to every wave after the first barrier below
   int ti = blockIdx.x;
-  Tile cur = coords(ti);
+  NtTile cur = nt_tile<BM>(ti, tiles_m, tiles_n);
   offsets(cur);
   prologue();
   VITAMD_WAIT_VM(S::wait(NP - 1));
@@ -175,52 +99,15 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
 #pragma unroll
       for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    bf16x8 bq[NT][2], af[2][2];
     auto ktile = [&](int kt) {
       const bool lenient = seam && kt == 0;          // first K-tile behind a seam: the previous epilogue's E operations may still be in flight
-      const int sa = (kt & 1) * ASLOT, sb = (kt & 1) * BSLOT;
-      const char* const pa0 = rdA[0] + sa;
-      const char* const pa1 = rdA[1] + sa;
-      const char* const pb0 = rdB[0] + sb;
-      const char* const pb1 = rdB[1] + sb;
-#pragma unroll
-      for (int ph = 0; ph < NP; ++ph) {
-        if (ph == 0) {
-#pragma unroll
-          for (int j = 0; j < NT; ++j) {
-            bq[j][0] = *(const bf16x8*)(pb0 + j * 2048);
-            bq[j][1] = *(const bf16x8*)(pb1 + j * 2048);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          af[i][0] = *(const bf16x8*)(pa0 + ph * PART + i * 2048);
-          af[i][1] = *(const bf16x8*)(pa1 + ph * PART + i * 2048);
-        }
-        request_a(kt + S::a_tile(ph), S::a_part(ph));
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (S::b_here(ph, q)) request_b(kt + S::b_tile(ph, q), q);
-        if (S::wait(ph, E) != S::wait(ph) && lenient) VITAMD_WAIT_VM(S::wait(ph, E));
-        else VITAMD_WAIT_VM(S::wait(ph));
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-              acc[2 * ph + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[j][ks], af[i][ks], acc[2 * ph + i][j], 0, 0, 0);
-            }
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
+      const int sa = (kt & 1) * ASLOT, sb = (kt & 1) * BSLOT;      // ring slots at run time
+      pp_ktile<MT, PART>(acc, rdA[0] + sa, rdA[1] + sa, rdB[0] + sb, rdB[1] + sb,
+                         [&](int ph) { S::requests(kt, ph, request_a, request_b); },
+                         [&](int ph) {
+                           if (S::wait(ph, E) != S::wait(ph) && lenient) VITAMD_WAIT_VM(S::wait(ph, E));
+                           else VITAMD_WAIT_VM(S::wait(ph));
+                         });
     };
     for (int kt = 0; kt < nkt; ++kt) ktile(kt);
     if (wm == 0) __builtin_amdgcn_s_barrier();        // balance the stagger: every wave is past its last operand read
@@ -262,7 +149,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
     const int ti_next = ti + (int)gridDim.x;
     const bool has_next = ti_next < ntiles;
     if (has_next) {
-      cur = coords(ti_next);
+      cur = nt_tile<BM>(ti_next, tiles_m, tiles_n);
       offsets(cur);
     }
     fill = has_next;
@@ -279,7 +166,8 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
     } else {
       asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NREQ) : "memory");
     }
-    // ---- epilogue: SL slices per round through the wave-private staging image ([16 rows][64 bf16] per slice, 16-B chunk XOR (row & 7))
+    // ---- epilogue: SL slices per round through the wave-private staging image ([16 rows][64 bf16] per slice, 16-B chunk XOR (row & 7)).
+    // TWIN of the epilogue of gemm_nt_ld_kernel (gemm_nt_ld.h, which is this one with SL = 1): a change to one belongs in the other.
     f32x4 bias4[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -368,17 +256,12 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
     if (wm == 1) __builtin_amdgcn_s_barrier();
     seam = true;
   }
-#undef VITAMD_WAIT_VM
 }
 
 template <int EPI, int MT, bool TAB = false>
 int launch_seam(const GemmNtArgs& p, hipStream_t stream, int cus) {
-  auto kern = gemm_nt_seam_kernel<EPI, MT, TAB>;
   if (TAB && !p.gelu_tab) return VITAMD_ERR_ARG;
-  if (int e = set_lds(kern, 160 * 1024)) return e;
-  const int tiles = ((p.M + 32 * MT - 1) / (32 * MT)) * ((p.N + 255) / 256);
-  hipLaunchKernelGGL(kern, dim3(tiles > cus ? cus : tiles), dim3(512), 160 * 1024, stream, p);
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return launch_tiles(gemm_nt_seam_kernel<EPI, MT, TAB>, p, stream, 32 * MT, 512, 160 * 1024, cus);
 }
 
 // launch conditions of the seam kernel (everything else stays on gemm_nt_pp_kernel)

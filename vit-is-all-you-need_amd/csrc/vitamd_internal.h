@@ -11,6 +11,18 @@ enum GemmEpilogue {
   EPI_F32 = 5,        // out f32 = acc
 };
 
+// `tile` codes of the NT GEMM entry points (include/vitamd.h documents the numbers; they are part of the C ABI)
+enum NtTileCode {
+  NT_TILE_AUTO = 0,                   // the library picks kernel, tile height and launch form
+  NT_TILE_128 = 128,                  // the 128x128 kernel
+  NT_TILE_256 = 256,                  // the ping-pong kernel on 256-row tiles, one workgroup per tile
+  NT_TILE_320 = 320,                  // ... on 320-row tiles
+  NT_TILE_AUTO_NO_PERSISTENT = 512,   // auto without persistent launches
+  NT_TILE_AUTO_NO_SEAM = 1024,        // auto with persistent launches but without the seam / loader forms
+  NT_TILE_LOADER = 2048,              // the loader-wave form
+};
+inline bool is_auto(int tile) { return tile == NT_TILE_AUTO || tile == NT_TILE_AUTO_NO_PERSISTENT || tile == NT_TILE_AUTO_NO_SEAM; }
+
 struct GemmNtArgs {
   const void* A;      // [M,K] bf16
   const void* B;      // [N,K] bf16
@@ -22,7 +34,7 @@ struct GemmNtArgs {
   int M, N, K, ldo;
   int epi;
   int n_patches, seq, extra;  // EPI_PATCH_F32 row remap
-  int tile;                   // 0 = auto, 128, 256
+  int tile;                   // NtTileCode
   // EPI_RESID_F32 only: dropout on the Linear output before the residual add (reference nn.Dropout, transformer.py:40)
   unsigned drop_thresh;       // p * 2^32, 0 = off
   float drop_scale;           // 1 / (1 - p)
