@@ -116,6 +116,19 @@ int vitamd_layernorm_bwd_dropout(const void* dy_bf16, const float* x, const floa
  * element of an HBM-bound kernel; D in {256, 512, 768, 1024}; dropout_p = 0 for no mask on the bf16 copy. */
 int vitamd_layernorm_bwd_xhat(const void* dy_bf16, const void* y_bf16, const float* rstd, const float* g_res, float* g_out,
                               void* g_bf16, float* colsum, int M, int D, float dropout_p, unsigned long long seed, void* stream);
+/* Kept-row forms, for the LAST layer of a stack whose caller keeps the first `keep` tokens of every `seq` (0 < keep <= seq).
+ * forward: B*keep output rows; row b*keep + t = LN(x_in[b*seq + t] + addend[b*keep + t]).  x_in is the full fp32 stream [B*seq, D];
+ * addend (bf16, required: the kept-query attention output), x_out, y, mean and rstd are compact [B*keep, ...].  Per-row arithmetic
+ * as vitamd_layernorm_fwd. */
+int vitamd_layernorm_fwd_keep(const float* x_in, const void* addend_bf16, float* x_out, void* y_bf16, float* mean, float* rstd,
+                              int B, int seq, int keep, int D, float eps, void* stream);
+/* backward over all B*seq rows with a COMPACT g_res fp32 [B*keep, D] (required): row b*seq + t adds g_res[b*keep + t] when t < keep
+ * and nothing otherwise (those rows of the dense g_res would be zeros and are never read).  use_xhat != 0: x_or_y is the forward's
+ * bf16 output as in vitamd_layernorm_bwd_xhat (D in {256, 512, 768, 1024}; mean may be NULL); 0: the fp32 input with mean / rstd as
+ * in vitamd_layernorm_bwd_dropout.  g_bf16, colsum, dropout_p, seed as there. */
+int vitamd_layernorm_bwd_keep(const void* dy_bf16, const void* x_or_y, const float* mean, const float* rstd, const float* g_res,
+                              float* g_out, void* g_bf16, float* colsum, int B, int seq, int keep, int D, int use_xhat,
+                              float dropout_p, unsigned long long seed, void* stream);
 
 /* Affine LayerNorm (nn.LayerNorm weight/bias) for the `blocks.py` surface (blocks.py:43,48,179,184).
  * forward: y = bf16(LN(x) * gamma + beta).  backward: g_out = (g_res or 0) + dLN/dx; dgamma, dbeta are
@@ -150,6 +163,19 @@ int vitamd_attention_fwd_resid(const void* qkv, void* o, float* lse2, const floa
 int vitamd_attention_bwd(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv,
                          float* delta, float* dbias, int B, int N, int H, int head_dim, int causal, float dropout_p,
                          unsigned long long seed, void* stream);
+/* Kept-query forms (non-causal, no dropout), for the last layer of a stack whose caller keeps the first nq tokens (0 < nq <= N): the
+ * attention output and its gradient exist for the queries < nq only, K and V for every token.
+ *   o, d_o : COMPACT bf16 [B*nq, H*64], row b*nq + t.
+ *   lse2, delta : the usual fp32 [B, H, N] buffers; only the entries of queries < nq are written / read, the rest is left untouched.
+ *   dqkv : dense bf16 [B,N,3,H,64]; its Q rows >= nq are written as zeros; dbias as in vitamd_attention_bwd.
+ * The kept rows are bit-identical to vitamd_attention_fwd, and dqkv to vitamd_attention_bwd given d_o zero-padded to N rows (up to the
+ * sign of zeros).  vitamd_attention_keep_forms(N, nq) returns a bit mask of the shapes served: 1 = forward (129 <= N <= 256, the
+ * eight-wave kernel), 2 = backward (33 <= N <= 224 and nq <= 128, the pipelined kernels); the calls return VITAMD_ERR_SHAPE elsewhere and the caller
+ * runs the full-size forms (vitamd/functions.py does). */
+int vitamd_attention_keep_forms(int N, int nq);
+int vitamd_attention_fwd_keep(const void* qkv, void* o, float* lse2, int B, int N, int H, int head_dim, int nq, void* stream);
+int vitamd_attention_bwd_keep(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta,
+                              float* dbias, int B, int N, int H, int head_dim, int nq, void* stream);
 
 /* ---- KV-cached decoding (autoregressive generation on a causal stack) ---------------------------------
  * The reference has no cache: VideoGPT.generate (train_videogpt.py:56-65) re-runs the whole stack over the whole prefix for every new

@@ -240,6 +240,9 @@ struct AttnArgs {
   // (transformer.py:44 `x = x + attn(...)`), so the LayerNorm that follows reads x once instead of x and o and writing x
   const float* resid_in;
   float* resid_out;
+  // kept-query forms only (KEEP / LIM template arguments): queries >= nq are not computed (forward) / carry no gradient (backward).
+  // o and d_o are then COMPACT [B*nq, H*64] (row b*nq + t); lse2 and delta keep the [B, H, N] layout, entries of queries >= nq untouched.
+  int nq;
 };
 
 // keep-scale of probability (b, head, query, key): 1/(1-p) or 0
@@ -426,8 +429,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a
 // each - that share the staged K / V, and the softmax is ONLINE over a rolled key-tile loop, so a wave needs 102 registers: two workgroups
 // = 16 waves share a CU at the LDS footprint of the 4-wave kernel (2 x npad x 128 + 8 x 2 KiB).  93 against 103 us at B = 256, N = 197, H = 12.
 // Non-causal, no dropout; RES: also writes resid_out = resid_in + bf16(o) (the 4-wave kernel's fused residual form).
+// KEEP: only the queries < a.nq are wanted (the last layer of a stack whose caller keeps a prefix of the tokens).  Every wave still helps stage
+// K / V - all keys are needed - and the waves whose query block starts at or beyond nq stop there; o is written compact [B*nq, H*64], lse2 at
+// its usual [B, H, N] position.  A query's arithmetic does not depend on the other lanes of its block, so the kept rows are bit-identical.
 // ------------------------------------------------------------------------------------------
-template <int NKT, bool RES>
+template <int NKT, bool RES, bool KEEP = false>
 __global__ __launch_bounds__(512, 4) void attn_fwd_small8_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -442,7 +448,8 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_small8_kernel(const AttnArgs 
   stage_tile(qbase + D, D3, N, npad, ktile, wave, lane, 8);
   stage_tile(qbase + 2 * D, D3, N, npad, vtile, wave, lane, 8);
   const int qb = (wave + head) & 7;            // rotate which waves sit out when the head has fewer than 8 query blocks
-  const bool active = qb < nt;
+  bool active = qb < nt;
+  if constexpr (KEEP) active = qb * 32 < a.nq;
   bf16x8 qf[4];
   load_lane_frags(qbase, D3, N, (active ? qb : 0) * 32, lane, qf);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -504,6 +511,11 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_small8_kernel(const AttnArgs 
   l += __shfl_xor(l, 32, 64);
   const float mc = m * c;
   const float inv = 1.0f / l;
+  if constexpr (KEEP) {
+    store_rows_T_lds2k(a.o + (size_t)b * a.nq * D + hh * DH, D, a.nq, q0, lane, oacc, inv, oimg);
+    if (lane < 32 && qrow < a.nq) a.lse2[((size_t)b * a.H + hh) * N + qrow] = mc + log2f(l);
+    return;
+  }
   if constexpr (RES)
     store_rows_T_lds2k<true>(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg, a.resid_in + (size_t)b * N * D + hh * DH,
                              a.resid_out + (size_t)b * N * D + hh * DH, D);
@@ -602,7 +614,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
 //                 exp, dS of tile T on the VALU                                            } the independent MFMA and VALU streams
 //                 dQ += K^T.dS of tile T
 // Same arithmetic in the same order as attn_bwd_dq_kernel (bit-identical results); non-causal, no dropout.
-template <int NT>
+// LIM (kept-query form, NQT = ceil(nq / 32) <= NT): o and d_o are compact [B*nq, H*64] and the queries >= nq carry no gradient.  Query blocks
+// < NQT are computed as usual - a lane whose query is >= nq takes dO = 0 and lse = +1e30, so its P, delta, dS and dQ are exact zeros - and the
+// blocks >= NQT only write zero rows into the Q part of dqkv (the dense dgrad-qkv / dW-qkv GEMMs read them).  delta is written for queries < nq.
+template <int NT, int NQT = NT, bool LIM = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -616,8 +631,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
   const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   stage_tile(qbase + D, D3, N, npad, ktile, wave, lane);
   stage_tile(qbase + 2 * D, D3, N, npad, vtile, wave, lane);
-  const __bf16* obase = a.o + (size_t)b * N * D + hh * DH;
-  const __bf16* dobase = a.d_o + (size_t)b * N * D + hh * DH;
+  int nq = N;                      // rows of o / d_o per sequence
+  if constexpr (LIM) nq = a.nq;
+  const __bf16* obase = a.o + (size_t)b * nq * D + hh * DH;
+  const __bf16* dobase = a.d_o + (size_t)b * nq * D + hh * DH;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -628,22 +645,42 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
   for (int qb = (wave + head) & 3; qb < nt; qb += 4) {
     const int q0 = qb * 32;
     const int qrow = q0 + (lane & 31);
+    if constexpr (LIM) {
+      if (qb >= NQT) {               // no gradient reaches these queries: zero rows (8 lanes x 16 B = one 128-B head row)
+        __bf16* zp = a.dqkv + (size_t)b * N * D3 + hh * DH + 8 * (lane & 7);
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+          const int row = q0 + (lane >> 3) + 8 * it;
+          if (row < N) *(u32x4*)(zp + (size_t)row * D3) = (u32x4){0u, 0u, 0u, 0u};
+        }
+        continue;
+      }
+    }
     bf16x8 qf[4], dof[4];
     float delta = 0.f;
     {
       bf16x8 of[4];
       load_lane_frags(qbase, D3, N, q0, lane, qf);
-      load_lane_frags(dobase, D, N, q0, lane, dof);
-      load_lane_frags(obase, D, N, q0, lane, of);
+      load_lane_frags(dobase, D, nq, q0, lane, dof);
+      load_lane_frags(obase, D, nq, q0, lane, of);
+      if constexpr (LIM) {
+        if (qrow >= nq) {
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) dof[kk][j] = (__bf16)0.f;
+        }
+      }
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
         for (int j = 0; j < 8; ++j) delta += (float)dof[kk][j] * (float)of[kk][j];
     }
     delta += __shfl_xor(delta, 32, 64);
-    const size_t stat = ((size_t)b * a.H + hh) * N + min(qrow, N - 1);
-    const float lse2 = a.lse2[stat];
-    if (lane < 32 && qrow < N) a.delta[stat] = delta;
+    const size_t stat = ((size_t)b * a.H + hh) * N + min(qrow, nq - 1);
+    float lse2 = a.lse2[stat];
+    if constexpr (LIM) lse2 = qrow < nq ? lse2 : 1.0e30f;      // exp2(s - 1e30) = 0 exactly
+    if (lane < 32 && qrow < nq) a.delta[stat] = delta;
 
     f32x16 dq[2];
 #pragma unroll
@@ -801,26 +838,30 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
 // ahead, the S/dP products of query tile T+1 issued before the VALU work of tile T).  Padded query rows need no masking here:
 // their lse is staged as +1e30, so P and dS are exactly 0 for them; padded key lanes are never stored.  Bit-identical to
 // attn_bwd_dkv_kernel; non-causal, no dropout.
-template <int NT>
+// LIM (kept-query form): d_o is compact [B*nq, H*64]; only NQT = ceil(nq / 32) query tiles of Q and dO are staged and swept, the queries
+// nq .. 32 NQT - 1 of the last tile are padded queries in the sense above (lse +1e30).  The tiles left out would have added exact zeros.
+template <int NT, int NQT = NT, bool LIM = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int head = blockIdx.x;     // one workgroup per (batch, head); a persistent two-per-CU grid walking the heads is slower (backward 276 against 256 us)
   const int b = head / a.H, hh = head % a.H;
   const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
-  constexpr int nt = NT, npad = NT * 32;
+  constexpr int nt = NT, npad = NQT * 32;           // npad: staged QUERY rows
+  int nq = N;
+  if constexpr (LIM) nq = a.nq;
   char* qtile = smem;
   char* dotile = smem + npad * 128;
   float* lse_s = (float*)(smem + 2 * npad * 128);
   float* delta_s = lse_s + npad;
   char* oimg = smem + 2 * npad * 128 + 2 * npad * 4 + wave * 4096;
   const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
-  const __bf16* dobase = a.d_o + (size_t)b * N * D + hh * DH;
+  const __bf16* dobase = a.d_o + (size_t)b * nq * D + hh * DH;
   stage_tile(qbase, D3, N, npad, qtile, wave, lane);
-  stage_tile(dobase, D, N, npad, dotile, wave, lane);
+  stage_tile(dobase, D, nq, npad, dotile, wave, lane);
   for (int i = threadIdx.x; i < npad; i += 256) {
-    const size_t stat = ((size_t)b * a.H + hh) * N + min(i, N - 1);
-    lse_s[i] = i < N ? a.lse2[stat] : 1.0e30f;        // padded queries: exp2(s - 1e30) = 0 exactly
+    const size_t stat = ((size_t)b * a.H + hh) * N + min(i, nq - 1);
+    lse_s[i] = i < nq ? a.lse2[stat] : 1.0e30f;       // padded queries: exp2(s - 1e30) = 0 exactly
     delta_s[i] = a.delta[stat];
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -852,12 +893,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArg
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) { qr[kk] = row_frag(qtile, 0, kk, lane); dor[kk] = row_frag(dotile, 0, kk, lane); }
     products();
-    if (NT > 1) {
+    if (NQT > 1) {
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) { qr[kk] = row_frag(qtile, 1, kk, lane); dor[kk] = row_frag(dotile, 1, kk, lane); }
     }
 #pragma unroll
-    for (int T = 0; T < NT; ++T) {
+    for (int T = 0; T < NQT; ++T) {
       bf16x8 dotr[2][2], qtr[2][2];
       f32x4 lse4[4], del4[4];
 #pragma unroll
@@ -891,8 +932,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArg
           dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtr[sidx][dt], dsf, dk[dt], 0, 0, 0);
         }
       }
-      if (T + 1 < NT) products();     // S, dP of the next tile queue up behind this tile's dV, dK products
-      if (T + 2 < NT) {
+      if (T + 1 < NQT) products();     // S, dP of the next tile queue up behind this tile's dV, dK products
+      if (T + 2 < NQT) {
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) { qr[kk] = row_frag(qtile, T + 2, kk, lane); dor[kk] = row_frag(dotile, T + 2, kk, lane); }
       }
@@ -1328,5 +1369,83 @@ extern "C" int vitamd_attention_bwd(const void* qkv, const void* o, const float*
   if (a.drop_thresh) { if (a.causal) BWD_SMALL(true, true); else BWD_SMALL(true, false); }
   else { if (a.causal) BWD_SMALL(false, true); else BWD_SMALL(false, false); }
 #undef BWD_SMALL
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------ kept-query forms
+// The last layer of a stack whose caller keeps the first nq tokens of every sequence (functions.layer_forward, keep=): attention output
+// and its gradient exist for the queries < nq only, K and V for every token.  o and d_o are COMPACT [B*nq, H*64] (row b*nq + t); lse2 and
+// delta keep the [B, H, N] layout and only the entries of queries < nq are written / read.  Non-causal, no dropout.  Shapes: the forward
+// needs the eight-wave kernel (129 <= N <= 256), the backward the pipelined kernels (33 <= N <= 224) and nq <= 128;
+// vitamd_attention_keep_forms tells.
+extern "C" int vitamd_attention_keep_forms(int N, int nq) {
+  if (N <= 0 || nq <= 0 || nq > N) return 0;
+  const int nkt = (N + 31) / 32;
+  return (nkt >= 5 && nkt <= 8 ? 1 : 0) | (nkt >= 2 && nkt <= 7 && nq <= 128 ? 2 : 0);     // up to 4 query tiles are instantiated
+}
+
+extern "C" int vitamd_attention_fwd_keep(const void* qkv, void* o, float* lse2, int B, int N, int H, int head_dim, int nq, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (head_dim != DH) return VITAMD_ERR_SHAPE;
+  AttnArgs a{(const __bf16*)qkv, (__bf16*)o, lse2, nullptr, nullptr, nullptr, nullptr, B, N, H, 0, 0.125f * 1.4426950408889634f, 0.125f,
+             0u, 1.0f, 0u, 0u, nullptr, nullptr, nq};
+  if (int e = check(a)) return e;
+  if (!qkv || !o || !lse2) return VITAMD_ERR_ARG;
+  if (!(vitamd_attention_keep_forms(N, nq) & 1)) return VITAMD_ERR_SHAPE;
+  const int nkt = (N + 31) / 32, lds = 2 * nkt * 32 * 128 + 8 * 2048;
+  int e = VITAMD_OK;
+#define FWD_KEEP(K) case K: e = set_lds(attn_fwd_small8_kernel<K, false, true>, lds); \
+    if (!e) hipLaunchKernelGGL((attn_fwd_small8_kernel<K, false, true>), dim3(B * H), dim3(512), lds, stream, a); break;
+  switch (nkt) { FWD_KEEP(5) FWD_KEEP(6) FWD_KEEP(7) FWD_KEEP(8) }
+#undef FWD_KEEP
+  if (e) return e;
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+template <int NT, int NQT>
+static int launch_bwd_keep(const AttnArgs& a, hipStream_t stream) {
+  if constexpr (NQT > NT) return VITAMD_ERR_SHAPE;
+  else {
+    const int lds1 = 2 * NT * 32 * 128 + 4 * 4096, lds2 = 2 * NQT * 32 * 128 + 2 * NQT * 32 * 4 + 4 * 4096;
+    const dim3 grid(a.B * a.H), block(256);
+    if (int e = set_lds((attn_bwd_dq_pipe_kernel<NT, NQT, true>), lds1)) return e;
+    if (int e = set_lds((attn_bwd_dkv_pipe_kernel<NT, NQT, true>), lds2)) return e;
+    hipLaunchKernelGGL((attn_bwd_dq_pipe_kernel<NT, NQT, true>), grid, block, lds1, stream, a);    // also writes delta
+    hipLaunchKernelGGL((attn_bwd_dkv_pipe_kernel<NT, NQT, true>), grid, block, lds2, stream, a);
+    return VITAMD_OK;
+  }
+}
+
+template <int NT>
+static int launch_bwd_keep_nt(const AttnArgs& a, int nqt, hipStream_t stream) {
+  switch (nqt) {
+    case 1: return launch_bwd_keep<NT, 1>(a, stream);
+    case 2: return launch_bwd_keep<NT, 2>(a, stream);
+    case 3: return launch_bwd_keep<NT, 3>(a, stream);
+    case 4: return launch_bwd_keep<NT, 4>(a, stream);
+  }
+  return VITAMD_ERR_SHAPE;
+}
+
+extern "C" int vitamd_attention_bwd_keep(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta,
+                                         float* dbias, int B, int N, int H, int head_dim, int nq, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (head_dim != DH) return VITAMD_ERR_SHAPE;
+  AttnArgs a{(const __bf16*)qkv, (__bf16*)o, (float*)lse2, (const __bf16*)d_o, (__bf16*)dqkv, delta, dbias, B, N, H, 0,
+             0.125f * 1.4426950408889634f, 0.125f, 0u, 1.0f, 0u, 0u, nullptr, nullptr, nq};
+  if (int e = check(a)) return e;
+  if (!qkv || !o || !lse2 || !d_o || !dqkv || !delta) return VITAMD_ERR_ARG;
+  if (!(vitamd_attention_keep_forms(N, nq) & 2)) return VITAMD_ERR_SHAPE;
+  const int nkt = (N + 31) / 32, nqt = (nq + 31) / 32;
+  int e = VITAMD_ERR_SHAPE;
+  switch (nkt) {
+    case 2: e = launch_bwd_keep_nt<2>(a, nqt, stream); break;
+    case 3: e = launch_bwd_keep_nt<3>(a, nqt, stream); break;
+    case 4: e = launch_bwd_keep_nt<4>(a, nqt, stream); break;
+    case 5: e = launch_bwd_keep_nt<5>(a, nqt, stream); break;
+    case 6: e = launch_bwd_keep_nt<6>(a, nqt, stream); break;
+    case 7: e = launch_bwd_keep_nt<7>(a, nqt, stream); break;
+  }
+  if (e) return e;
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }

@@ -13,17 +13,22 @@ namespace {
 constexpr int ROWS_PER_BLOCK = 4;  // 4 waves, one row each per iteration
 constexpr int MAXV = 4;            // up to 4 float4 per lane: D <= 1024, D % 256 == 0
 
-template <int NV, bool HAS_ADD>
+// KEEP (kept-row form, M = B * keep): output row b*keep + t takes row b*seq + t of x_in and row b*keep + t of the addend (the compact
+// output of the kept-query attention); x_out, y, mean, rstd are compact.  The per-row arithmetic is the same code.
+template <int NV, bool HAS_ADD, bool KEEP = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x_in, const __bf16* __restrict__ addend,
                                                      float* __restrict__ x_out, __bf16* __restrict__ y,
-                                                     float* __restrict__ mean, float* __restrict__ rstd, int M, float eps) {
+                                                     float* __restrict__ mean, float* __restrict__ rstd, int M, float eps,
+                                                     int seq = 0, int keep = 0) {
   constexpr int D = NV * 256;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int row = blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += gridDim.x * ROWS_PER_BLOCK) {
     f32x4 v[NV];
     const size_t base = (size_t)row * D;
+    size_t base_in = base;
+    if constexpr (KEEP) base_in = ((size_t)(row / keep) * seq + row % keep) * D;
 #pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = *(const f32x4*)(x_in + base + j * 256 + lane * 4);
+    for (int j = 0; j < NV; ++j) v[j] = *(const f32x4*)(x_in + base_in + j * 256 + lane * 4);
     if constexpr (HAS_ADD) {
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
@@ -52,14 +57,16 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 }
 
 // generic-width fallback (D % 4 == 0): three passes over the row through L1/L2
-template <bool HAS_ADD>
+template <bool HAS_ADD, bool KEEP = false>
 __global__ __launch_bounds__(256) void ln_fwd_generic(const float* __restrict__ x_in, const __bf16* __restrict__ addend,
                                                       float* __restrict__ x_out, __bf16* __restrict__ y,
-                                                      float* __restrict__ mean, float* __restrict__ rstd, int M, int D, float eps) {
+                                                      float* __restrict__ mean, float* __restrict__ rstd, int M, int D, float eps,
+                                                      int seq = 0, int keep = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int row = blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += gridDim.x * ROWS_PER_BLOCK) {
     const size_t base = (size_t)row * D;
     const float* xr = x_in + base;
+    if constexpr (KEEP) xr = x_in + ((size_t)(row / keep) * seq + row % keep) * D;      // kept-row form: see ln_fwd_kernel
     float s = 0.f;
     for (int c = lane; c < D; c += 64) {
       float t = xr[c];
@@ -80,12 +87,15 @@ __global__ __launch_bounds__(256) void ln_fwd_generic(const float* __restrict__ 
 // weight-gradient operand of the following Linear) through the `x` pointer, instead of being recomputed from the fp32 input:
 // 2 B instead of 4 B per element of an HBM-bound kernel (16 -> 14 B/elem), `mean` unused.  The bf16 rounding of xhat only
 // touches the xhat * mean(dy * xhat) term (|.| ~ 0.1 |dy|): ~2e-4 relative on g, far below the bf16 roundings around it.
-template <int NV, bool XH = false>
+// GK: g_res is COMPACT [B*keep, D] - the gradient of a stack output of which only the first `keep` tokens of every `seq` were kept: row
+// b*seq + t adds g_res[b*keep + t] when t < keep and nothing otherwise (no read at all for the other rows).
+template <int NV, bool XH = false, bool GK = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ dy, const float* __restrict__ x,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ g_res, float* __restrict__ g_out,
                                                      __bf16* __restrict__ g_bf16, float* __restrict__ colsum, int M,
-                                                     unsigned dthresh, float dscale, unsigned dseed_lo, unsigned dseed_hi) {
+                                                     unsigned dthresh, float dscale, unsigned dseed_lo, unsigned dseed_hi,
+                                                     int seq = 0, int keep = 0) {
   constexpr int D = NV * 256;
   __shared__ float red[ROWS_PER_BLOCK][D];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -95,6 +105,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
   for (int row = blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += gridDim.x * ROWS_PER_BLOCK) {
     const size_t base = (size_t)row * D;
     const float mu = XH ? 0.f : mean[row], rs = rstd[row];
+    const float* gres_row = nullptr;            // GK: this row's compact g_res row, if it has one
+    if constexpr (GK) {
+      const int t = row % seq;
+      if (t < keep) gres_row = g_res + ((size_t)(row / seq) * keep + t) * D;
+    }
     f32x4 d[NV], xh[NV];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -121,7 +136,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
       f32x4 g;
 #pragma unroll
       for (int c = 0; c < 4; ++c) g[c] = rs * (d[j][c] - m1 - xh[j][c] * m2);
-      if (g_res) g += *(const f32x4*)(g_res + base + j * 256 + lane * 4);
+      if constexpr (GK) {
+        if (gres_row) g += *(const f32x4*)(gres_row + j * 256 + lane * 4);
+      } else {
+        if (g_res) g += *(const f32x4*)(g_res + base + j * 256 + lane * 4);
+      }
       *(f32x4*)(g_out + base + j * 256 + lane * 4) = g;
       if (g_bf16) {
         u32x2 o = {pack_bf16x2(g[0], g[1]), pack_bf16x2(g[2], g[3])};
@@ -152,15 +171,21 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
   }
 }
 
+template <bool GK = false>       // GK: compact g_res, see ln_bwd_kernel
 __global__ __launch_bounds__(256) void ln_bwd_generic(const __bf16* __restrict__ dy, const float* __restrict__ x,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                       const float* __restrict__ g_res, float* __restrict__ g_out,
                                                       __bf16* __restrict__ g_bf16, float* __restrict__ colsum, int M, int D,
-                                                      unsigned dthresh, float dscale, unsigned dseed_lo, unsigned dseed_hi) {
+                                                      unsigned dthresh, float dscale, unsigned dseed_lo, unsigned dseed_hi,
+                                                      int seq = 0, int keep = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int row = blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += gridDim.x * ROWS_PER_BLOCK) {
     const size_t base = (size_t)row * D;
     const float mu = mean[row], rs = rstd[row];
+    const float* gr = nullptr;                  // GK: this row's compact g_res row, if it has one
+    if constexpr (GK) {
+      if (row % seq < keep) gr = g_res + ((size_t)(row / seq) * keep + row % seq) * D;
+    }
     float s1 = 0.f, s2 = 0.f;
     for (int c = lane; c < D; c += 64) {
       const float d = bf2f(dy[base + c]);
@@ -171,7 +196,11 @@ __global__ __launch_bounds__(256) void ln_bwd_generic(const __bf16* __restrict__
     for (int c = lane; c < D; c += 64) {
       const float d = bf2f(dy[base + c]);
       float g = rs * (d - m1 - (x[base + c] - mu) * rs * m2);
-      if (g_res) g += g_res[base + c];
+      if constexpr (GK) {
+        if (gr) g += gr[c];
+      } else {
+        if (g_res) g += g_res[base + c];
+      }
       g_out[base + c] = g;
       if (g_bf16) {
         __bf16 gb = f2bf(g);
@@ -232,7 +261,7 @@ static int ln_bwd_launch(const void* dy_bf16, const float* x, const float* mean,
   else if (D == 512) { LN_BWD(2); }
   else if (D == 768) { LN_BWD(3); }
   else if (D == 1024) { LN_BWD(4); }
-  else hipLaunchKernelGGL(ln_bwd_generic, dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, D, dthresh, dscale, slo, shi);
+  else hipLaunchKernelGGL(ln_bwd_generic<>, dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, D, dthresh, dscale, slo, shi);
 #undef LN_BWD
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
@@ -273,5 +302,59 @@ extern "C" int vitamd_layernorm_bwd_xhat(const void* dy_bf16, const void* y_bf16
   else if (D == 768) { LN_BWDX(3); }
   else { LN_BWDX(4); }
 #undef LN_BWDX
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+// Kept-row forward: M = B * keep output rows; row b*keep + t = LN(x_in[b*seq + t] + addend[b*keep + t]).  x_out, y, mean, rstd are compact
+// [B*keep, ...].  addend (bf16 [B*keep, D], the kept-query attention output) and x_out are required.
+extern "C" int vitamd_layernorm_fwd_keep(const float* x_in, const void* addend_bf16, float* x_out, void* y_bf16, float* mean, float* rstd,
+                                         int B, int seq, int keep, int D, float eps, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0 || seq <= 0 || keep <= 0 || keep > seq || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
+  if ((long long)B * seq > 2147483647LL) return VITAMD_ERR_SHAPE;
+  if (!x_in || !y_bf16 || !mean || !rstd || !addend_bf16 || !x_out) return VITAMD_ERR_ARG;
+  const __bf16* add = (const __bf16*)addend_bf16;
+  __bf16* y = (__bf16*)y_bf16;
+  const int M = B * keep, grid = grid_for(M);
+#define LN_FWDK(NV) hipLaunchKernelGGL((ln_fwd_kernel<NV, true, true>), dim3(grid), dim3(256), 0, stream, x_in, add, x_out, y, mean, rstd, M, eps, seq, keep)
+  if (D == 256) { LN_FWDK(1); }
+  else if (D == 512) { LN_FWDK(2); }
+  else if (D == 768) { LN_FWDK(3); }
+  else if (D == 1024) { LN_FWDK(4); }
+  else hipLaunchKernelGGL((ln_fwd_generic<true, true>), dim3(grid), dim3(256), 0, stream, x_in, add, x_out, y, mean, rstd, M, D, eps, seq, keep);
+#undef LN_FWDK
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+// LayerNorm backward over M = B * seq rows with a COMPACT g_res [B*keep, D]: row b*seq + t adds g_res[b*keep + t] when t < keep, nothing
+// otherwise.  use_xhat != 0: x_or_y is the forward's bf16 output (vitamd_layernorm_bwd_xhat; D in {256, 512, 768, 1024}, mean unused);
+// else the fp32 input with mean / rstd (vitamd_layernorm_bwd_dropout).  g_bf16, colsum and the dropout arguments as there.
+extern "C" int vitamd_layernorm_bwd_keep(const void* dy_bf16, const void* x_or_y, const float* mean, const float* rstd, const float* g_res,
+                                         float* g_out, void* g_bf16, float* colsum, int B, int seq, int keep, int D, int use_xhat,
+                                         float dropout_p, unsigned long long seed, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0 || seq <= 0 || keep <= 0 || keep > seq || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
+  if ((long long)B * seq > 2147483647LL) return VITAMD_ERR_SHAPE;
+  const bool wide = D == 256 || D == 512 || D == 768 || D == 1024;
+  if (use_xhat && !wide) return VITAMD_ERR_SHAPE;
+  if (!dy_bf16 || !x_or_y || !rstd || !g_res || !g_out || (!use_xhat && !mean)) return VITAMD_ERR_ARG;
+  if (!(dropout_p >= 0.f) || dropout_p >= 1.f) return VITAMD_ERR_ARG;
+  unsigned dthresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
+  if (dropout_p > 0.f && dthresh == 0u) dthresh = 1u;
+  const float dscale = 1.0f / (1.0f - dropout_p);
+  const unsigned slo = (unsigned)seed, shi = (unsigned)(seed >> 32);
+  const __bf16* dy = (const __bf16*)dy_bf16;
+  const float* x = (const float*)x_or_y;
+  __bf16* gb = (__bf16*)g_bf16;
+  const int M = B * seq, grid = grid_for(M, colsum != nullptr && g_bf16 != nullptr);
+#define LN_BWDK(NV)                                                                                                                    \
+  if (use_xhat) hipLaunchKernelGGL((ln_bwd_kernel<NV, true, true>), dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, dthresh, dscale, slo, shi, seq, keep); \
+  else hipLaunchKernelGGL((ln_bwd_kernel<NV, false, true>), dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, dthresh, dscale, slo, shi, seq, keep)
+  if (D == 256) { LN_BWDK(1); }
+  else if (D == 512) { LN_BWDK(2); }
+  else if (D == 768) { LN_BWDK(3); }
+  else if (D == 1024) { LN_BWDK(4); }
+  else hipLaunchKernelGGL(ln_bwd_generic<true>, dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, D, dthresh, dscale, slo, shi, seq, keep);
+#undef LN_BWDK
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }

@@ -64,7 +64,7 @@ class TiTokEncoder(nn.Module):
         self.proj = HipLinear(titok_config.n_embd, titok_config.latent_dim)
 
     def forward(self, x):
-        return self.proj(self.vit(x)[:, :self.latent_tokens])   # latent tokens are the PREPENDED extra tokens
+        return self.proj(self.vit(x, keep=self.latent_tokens))   # latent tokens are the PREPENDED extra tokens: [:, :latent_tokens]
 
 
 class Quantizer(nn.Module):
@@ -97,7 +97,7 @@ class TiTokDecoder(nn.Module):
     def forward(self, z):
         z = self.quant_proj(z)                                   # [b, latents, n_embd]
         z = z.transpose(1, 2).unsqueeze(-1)                      # 'b h c -> b c h 1'
-        out_embd = self.vit(z)[:, :self.config.n_patches]        # mask tokens come first (extra tokens)
+        out_embd = self.vit(z, keep=self.config.n_patches)       # mask tokens come first (extra tokens): [:, :n_patches]
         return pixel_shuffle_tokens(self.embd_proj(out_embd), self.config.patch_dim, self.config.patch_size)
 
 

@@ -44,11 +44,12 @@ class ViT(nn.Module):
         self.extra_emb = nn.Embedding(args.extra_tokens, D)
         self.transformer = Transformer(args.trans_config)
 
-    def forward(self, x):
+    def forward(self, x, keep=None):
+        """keep=k: only the first k tokens are wanted -> [B, k, D] = forward(x)[:, :k] (Transformer.forward, keep=)"""
         # conv patchify + (h w) flatten + pos_emb + prepended extra tokens in one GEMM epilogue
         emb = PatchEmbedFn.apply(x, self.patch_proj.weight, self.patch_proj.bias, self.pos_emb.weight,
                                  self.extra_emb.weight, self.config.patch_size, self.config.n_patches)
-        return self.transformer(emb)
+        return self.transformer(emb, keep=keep)
 
 
 class ViTClassifier(nn.Module):
@@ -58,7 +59,8 @@ class ViTClassifier(nn.Module):
         self.head = nn.Linear(vit_config.trans_config.n_embd, num_classes)
 
     def forward(self, x):
-        return linear(self.vit(x)[:, 0], self.head.weight, self.head.bias)
+        # the head reads the class token alone (train_vit.py:53): the stack's last layer runs its MLP on that row only
+        return linear(self.vit(x, keep=1)[:, 0], self.head.weight, self.head.bias)
 
 
 def train_step(model, images, labels, optim, lr_sched=None, loss_fn=None):

@@ -96,11 +96,19 @@ class Transformer(nn.Module):
         _adopt(self, config)
         self.layers = nn.ModuleList([TransformerLayer(config) for _ in range(config.n_layers)])
 
-    def forward(self, x):
+    def forward(self, x, keep=None):
+        """keep=k (no reference counterpart): the caller uses the first k tokens of every sequence only; returns [B, min(k, N), D], equal
+        to forward(x)[:, :k].  With 0 < k < N on a non-causal stack without dropout the last layer then runs its attention queries and
+        its MLP on those tokens alone (vitamd.functions.KEEP_ROWS)."""
         _check_dropout(self.dropout)
+        if keep is not None:
+            if isinstance(keep, bool) or not isinstance(keep, int) or keep <= 0:
+                raise ValueError(f"keep must be a positive int (the number of leading tokens to return), got {keep!r}")
+            if keep >= x.shape[1]:
+                keep = None
         params = [p for layer in self.layers for p in layer._params()]
         p_mlp = float(self.dropout) if self.training else 0.0
-        return TransformerStackFn.apply(x, self.n_heads, bool(self.causal), float(self.dropout), p_mlp, *params)
+        return TransformerStackFn.apply(x, self.n_heads, bool(self.causal), float(self.dropout), p_mlp, keep, *params)
 
     # KV-cached inference (no reference counterpart: the reference re-runs forward over the whole prefix per token, train_videogpt.py:56-65)
     def new_cache(self, batch, max_len=None):

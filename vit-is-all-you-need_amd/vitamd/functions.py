@@ -127,16 +127,21 @@ def _tn_form(which):
     return ops.TN_FORM_EXCLUSIVE if which == "fc2" else ops.TN_FORM_SHARED
 
 
-def _tn_splits(dW):
+def _tn_splits(dW, R=None):
     """Split-K factor for a weight-gradient GEMM that runs on the side stream BESIDE the input-gradient chain: a little under one
     workgroup per CU (180 of 256) - fewer, longer workgroups write fewer fp32 partial tiles for the reduce pass, and the CUs they
     leave free are taken by the main stream's kernels anyway.  Whole-step A/B (tools/ab_splits.py): 5 splits instead of 7 on the
-    36-tile GEMMs of ViT-B: -0.2 ms/step; 3 or fewer lose (36.9 ms at 3, 46 ms at 2)."""
+    36-tile GEMMs of ViT-B: -0.2 ms/step; 3 or fewer lose (36.9 ms at 3, 46 ms at 2).
+    R: the number of reduction rows when it is short (the kept-row MLP of the last layer, R = B * keep): the kernel walks R in 64-row
+    steps and a split needs at least one, so the factor is capped at ceil(R / 64) - 4 at R = 256, where each split is one step."""
     target = tn_target_wgs()
     if not target or not SIDE.enabled:      # alone on the chip (no side stream) the kernel's own rule - every CU - is right
         return 0
     ntile = ((dW.shape[0] + 255) // 256) * ((dW.shape[1] + 255) // 256)
-    return max(1, round(target / ntile))
+    splits = max(1, round(target / ntile))
+    if R is not None:
+        splits = min(splits, max(1, (R + 63) // 64))
+    return splits
 
 
 def tn_target_wgs():
@@ -151,6 +156,18 @@ DEFER_RESID = True        # inside a stack: fc2 writes bf16 y and the NEXT layer
                           # fp32 + bf16 sum the fused epilogue formed: bit-identical).  The same HBM bytes in total, but they move from the GEMM's
                           # epilogue (40 fp32 loads + 40 fp32 stores per wave and tile on the CU's one path to L1, matrix pipes idle) into an
                           # HBM-bound LayerNorm kernel, and fc2 becomes a plain bias GEMM: whole-step A/B (tools/ab_flags.py) in DESIGN.md section 4.2
+
+KEEP_ROWS = True          # a stack called with keep=k (the caller uses the first k tokens of every sequence only: ViTClassifier's class token, TiTok's
+                          # latent / patch prefix) runs everything after the K / V projection of its LAST layer on the B*k kept rows: DESIGN.md section 4.8.
+                          # False: the full stack, then a slice (the old path; tests and A/B runs)
+
+
+def keep_rows(keep, N, causal, p_attn, p_mlp):
+    """The number of kept tokens the last layer of a stack works on, or None for the full-size path: keep None or >= N, a causal stack and
+    any dropout take the full path (the kept-query attention kernels are non-causal and mask-free)."""
+    if keep is None or not KEEP_ROWS or keep >= N or causal or p_attn > 0 or p_mlp > 0:
+        return None
+    return int(keep)
 
 
 def streams_overlap(device, side=None):
@@ -214,18 +231,43 @@ def new_seed():
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
-def layer_forward(x0, wqkv, bqkv, w1, b1, w2, b2, B, N, H, causal, need_grad, p_attn=0.0, p_mlp=0.0, pending=None, defer=False):
+def _keep_native(N, keep):
+    """True: the kept-query attention kernels serve this shape (forward AND backward: 129 <= N <= 224, keep <= 128 - the ViT shapes).
+    False (N = 5 of the 32-pixel ViTs, N <= 128 or N >= 225: TiTok, ViT-VQGAN): full-size attention, of which the kept rows are taken,
+    and in the backward a zero-padded dO - the one full-size pass the kept-row path keeps for such shapes."""
+    return ops.attention_keep_forms(N, keep) == (ops.KEEP_FWD | ops.KEEP_BWD)
+
+
+def layer_forward(x0, wqkv, bqkv, w1, b1, w2, b2, B, N, H, causal, need_grad, p_attn=0.0, p_mlp=0.0, pending=None, defer=False, keep=None):
     """x0 fp32 [M,D] -> x2 fp32 [M,D], the tensors backward needs, and the dropout record
     (p_attn, seed_attn, p_mlp, seed_mlp).  p_attn: SDPA dropout_p (transformer.py:28); p_mlp: the
     nn.Dropout after fc2 (transformer.py:40).
     pending: bf16 [M,D] MLP output of the layer below that has not been added to x0 yet (this layer's first LayerNorm adds it).
-    defer: return (x1, y) with y = bf16 fc2 output instead of x2 = x1 + y (the caller hands y to the next layer as `pending`)."""
+    defer: return (x1, y) with y = bf16 fc2 output instead of x2 = x1 + y (the caller hands y to the next layer as `pending`).
+    keep (last layer of a stack only; non-causal, no dropout, 0 < keep < N): the caller uses the first `keep` tokens of every sequence.
+    LN1 and the QKV GEMM run on all M rows (K and V need every token); attention is computed for the queries < keep, and LN2, fc1+GELU
+    and fc2 run on the Mk = B*keep kept rows.  x2 is then COMPACT fp32 [Mk, D] (row b*keep + t), and so are o, x1, mean2, rstd2, bln,
+    pre and h of the saved tuple (same length, same order; o stays full-size where _keep_native says no)."""
     drop = (p_attn, new_seed() if p_attn > 0 else 0, p_mlp, new_seed() if p_mlp > 0 else 0)
     wqkv_b, _ = WEIGHTS.get(wqkv, need_grad)
     w1_b, _ = WEIGHTS.get(w1, need_grad)
     w2_b, _ = WEIGHTS.get(w2, need_grad)
     x0, a, mean1, rstd1 = ops.layernorm_fwd(x0, addend=pending)                  # (residual of the layer below +) LN1   transformer.py:43-44
     qkv = ops.gemm_nt(a, wqkv_b, ops.EPI_BIAS_BF16, bias=bqkv)                   # fused QKV      transformer.py:27
+    if keep is not None:
+        if causal or p_attn > 0 or p_mlp > 0 or defer or not 0 < keep < N:
+            raise ops._lib.VitamdError("layer_forward: keep needs a non-causal layer without dropout, defer=False and 0 < keep < N")
+        if _keep_native(N, keep):
+            o, lse = ops.attention_fwd_keep(qkv, B, N, H, keep)                  # o compact [Mk, D]
+            o_k = o
+        else:
+            o, lse = ops.attention_fwd(qkv, B, N, H)                             # full size; the backward needs the full o for delta
+            o_k = o.view(B, N, -1)[:, :keep].reshape(B * keep, -1).contiguous()  # Mk rows copied
+        x1, bln, mean2, rstd2 = ops.layernorm_fwd_keep(x0, o_k, B, N, keep)      # gathers the kept rows of x0: all compact from here on
+        pre, h = ops.gemm_nt(bln, w1_b, ops.EPI_GELU_DG, bias=b1)
+        x2 = ops.gemm_nt(h, w2_b, ops.EPI_RESID_F32, bias=b2, aux=x1)
+        saved = (x0, mean1, rstd1, a, qkv, o, lse, x1, mean2, rstd2, bln, pre, h) if need_grad else None
+        return x2, saved, drop
     # (the residual add can also ride in the attention kernel's epilogue - ops.attention_fwd(resid=) - which measured equal: 34.47 vs 34.43 ms)
     o, lse = ops.attention_fwd(qkv, B, N, H, causal, dropout=drop[:2])           # SDPA           transformer.py:28-29
     x1, bln, mean2, rstd2 = ops.layernorm_fwd(x0, addend=o)                      # residual + LN2 transformer.py:43-44
@@ -342,14 +384,21 @@ def grad_arena(D, n_layers, device, params=None):
     return out, None
 
 
+KEEP_WGRAD_SIDE = True    # the kept-row layer's two MLP weight gradients (R = B*keep rows: a few microseconds each) go to the side stream like every other
+                          # weight gradient (True) or stay on the main stream (False).  Whole-step A/B in profiles/last_layer_keep/gpu_visit.md.
+
+
 def layer_backward(g2, saved, wqkv, w1, w2, B, N, H, causal, grads, dy2=None, have_db2=False, emit_bf16=False,
-                   emit_colsum=None, drop=(0.0, 0, 0.0, 0), emit_dropout=(0.0, 0)):
+                   emit_colsum=None, drop=(0.0, 0, 0.0, 0), emit_dropout=(0.0, 0), keep=None):
     """g2 fp32 [M,D] = dL/dx2.  Fills `grads` = (dWqkv, dbqkv, dW1, db1, dW2, db2) (zero-initialised
     fp32, accumulated into) and returns (g0, bf16(g0) or None).
     dy2: bf16(g2) if a previous kernel already produced it (then db2 is already in grads[5] when
     have_db2).  emit_bf16/emit_colsum: also produce bf16(g0) and add its column sums to emit_colsum
     (the fc2 bias gradient of the layer below); emit_dropout = that layer's fc2 dropout (p, seed), whose
-    mask the emitted copy must carry.  drop = this layer's dropout record from layer_forward."""
+    mask the emitted copy must carry.  drop = this layer's dropout record from layer_forward.
+    keep: the layer ran layer_forward(keep=): g2 is COMPACT fp32 [B*keep, D].  The MLP's gradients, LN2 backward and the attention's dO run
+    on the B*keep kept rows; gradients become dense in the attention backward (every key's dK / dV receives from the kept queries), and
+    the first LayerNorm's backward takes its residual gradient compact."""
     x0, mean1, rstd1, a, qkv, o, lse, x1, mean2, rstd2, bln, pre, h = saved
     dWqkv, dbqkv, dW1, db1, dW2, db2 = grads
     main = torch.cuda.current_stream()
@@ -372,6 +421,8 @@ def layer_backward(g2, saved, wqkv, w1, w2, B, N, H, causal, grads, dy2=None, ha
         # the GPU every step then needed fresh hipMallocs: 22 GiB of live data became 68 GiB reserved for ViT-B, 155 GiB for ViT-L.)
         _SIDE_KEEP.extend(tensors)
 
+    R_mlp = g2.shape[0] if keep is not None else None         # short reduction of the kept-row weight gradients (_tn_splits)
+    on_side_mlp = on_side if keep is None or KEEP_WGRAD_SIDE else (lambda fn, *tensors: fn())
     _, wqkv_t = WEIGHTS.get(wqkv, True)
     _, w1_t = WEIGHTS.get(w1, True)
     _, w2_t = WEIGHTS.get(w2, True)
@@ -379,23 +430,30 @@ def layer_backward(g2, saved, wqkv, w1, w2, B, N, H, causal, grads, dy2=None, ha
         dy2 = ops.cast_bf16_dropout(g2, drop[2:]) if drop[2] > 0 else ops.cast_bf16(g2)
     # ---- MLP
     def wgrad_fc2():
-        ops.gemm_tn(dy2, h, dW2, accumulate=False, splits=_tn_splits(dW2), form=_tn_form("fc2"))
+        ops.gemm_tn(dy2, h, dW2, accumulate=False, splits=_tn_splits(dW2, R_mlp), form=_tn_form("fc2"))
         if not have_db2:
             ops.colsum(dy2, db2)
     # the MLP weight gradients enter the side stream as soon as their inputs exist, beside the input-gradient GEMMs (holding them back until
     # after dgrad-fc1, beside LayerNorm / attention backward, measured equal or up to 0.4 ms slower: DESIGN.md section 4)
-    on_side(wgrad_fc2, dy2, h, dW2, db2)
+    on_side_mlp(wgrad_fc2, dy2, h, dW2, db2)
     dpre = ops.gemm_nt(dy2, w2_t, ops.EPI_DMUL, aux=pre, colsum=db1)             # dgrad fc2 . gelu' (stored by the forward in `pre`)
-    on_side(lambda: ops.gemm_tn(dpre, bln, dW1, accumulate=False, splits=_tn_splits(dW1), form=_tn_form("fc1")), dpre, bln, dW1)
+    on_side_mlp(lambda: ops.gemm_tn(dpre, bln, dW1, accumulate=False, splits=_tn_splits(dW1, R_mlp), form=_tn_form("fc1")), dpre, bln, dW1)
     dbln = ops.gemm_nt(dpre, w1_t, ops.EPI_BIAS_BF16)                            # dgrad fc1
     # LayerNorm backward reads xhat from the saved bf16 LN output instead of recomputing it from fp32 x
-    g1, d_o = ops.layernorm_bwd(dbln, x1, mean2, rstd2, g_res=g2, want_bf16=True, xhat=bln)
+    g1, d_o = ops.layernorm_bwd(dbln, x1, mean2, rstd2, g_res=g2, want_bf16=True, xhat=bln)       # (kept-row layer: B*keep rows, all compact)
     # ---- attention
-    dqkv = ops.attention_bwd(qkv, o, lse, d_o, B, N, H, causal, dbias=dbqkv, dropout=drop[:2])   # also adds the QKV bias gradient
+    if keep is None:
+        dqkv = ops.attention_bwd(qkv, o, lse, d_o, B, N, H, causal, dbias=dbqkv, dropout=drop[:2])   # also adds the QKV bias gradient
+    elif _keep_native(N, keep):
+        dqkv = ops.attention_bwd_keep(qkv, o, lse, d_o, B, N, H, keep, dbias=dbqkv)             # compact o / dO in, dense dqkv out
+    else:
+        d_o_full = torch.zeros((B, N, d_o.shape[1]), dtype=BF16, device=d_o.device)            # shapes without a kept-query kernel: zero-padded dO
+        d_o_full[:, :keep] = d_o.view(B, keep, -1)
+        dqkv = ops.attention_bwd(qkv, o, lse, d_o_full.view(B * N, -1), B, N, H, causal, dbias=dbqkv)
     on_side(lambda: ops.gemm_tn(dqkv, a, dWqkv, accumulate=False, splits=_tn_splits(dWqkv), form=_tn_form("qkv")), dqkv, a, dWqkv)
     da = ops.gemm_nt(dqkv, wqkv_t, ops.EPI_BIAS_BF16)                            # dgrad qkv
     g0, g0b = ops.layernorm_bwd(da, x0, mean1, rstd1, g_res=g1, want_bf16=emit_bf16, colsum=emit_colsum, dropout=emit_dropout,
-                                xhat=a)
+                                xhat=a, keep=None if keep is None else (N, keep))
     return g0, g0b
 
 
@@ -463,9 +521,15 @@ class TransformerStackFn(torch.autograd.Function):
 
     @staticmethod
     @_amp_fwd
-    def forward(ctx, x, n_heads, causal, p_attn, p_mlp, *params):
+    def forward(ctx, x, n_heads, causal, p_attn, p_mlp, keep, *params):
+        """keep: None, or the number of leading tokens of every sequence the caller uses: the result is then [B, keep, D] =
+        forward(..., keep=None)[:, :keep], and the LAST layer works on the kept rows only (layer_forward, keep=) unless keep_rows()
+        says the full path must run (KEEP_ROWS off, causal, dropout, keep >= N), after which the output is sliced."""
         B, N, D = x.shape
         L = len(params) // 6
+        if keep is not None and keep <= 0:
+            raise ValueError(f"keep must be a positive number of tokens, got {keep}")
+        k_last = keep_rows(keep, N, causal, p_attn, p_mlp)
         need_grad = any(ctx.needs_input_grad)
         cur = _f32c(x).view(B * N, D)
         saved_all, drops = [], []
@@ -475,7 +539,7 @@ class TransformerStackFn(torch.autograd.Function):
             wqkv, bqkv, w1, b1, w2, b2 = params[6 * i: 6 * i + 6]
             defer = DEFER_RESID and i + 1 < L and p_mlp == 0          # the last layer (no LayerNorm follows) and dropout keep the fused epilogue
             out, saved, drop = layer_forward(cur, wqkv, _f32c(bqkv), w1, _f32c(b1), w2, _f32c(b2), B, N, n_heads, causal, need_grad,
-                                             p_attn, p_mlp, pending=pending, defer=defer)
+                                             p_attn, p_mlp, pending=pending, defer=defer, keep=k_last if i + 1 == L else None)
             cur, pending = out if defer else (out, None)
             drops.append(drop)
             if need_grad:
@@ -484,17 +548,26 @@ class TransformerStackFn(torch.autograd.Function):
             ctx.save_for_backward(*saved_all)
             ctx.params = params
         ctx.drops = drops
-        ctx.meta = (B, N, D, n_heads, causal, L, x.dtype)
-        return cur.view(B, N, D).to(x.dtype)
+        n_out = N if k_last is None else k_last
+        slice_to = keep if k_last is None and keep is not None and keep < N else None      # the full path with a kept prefix: slice afterwards
+        ctx.meta = (B, N, D, n_heads, causal, L, x.dtype, k_last, slice_to)
+        out = cur.view(B, n_out, D)
+        if slice_to is not None:
+            out = out[:, :slice_to].contiguous()
+        return out.to(x.dtype)
 
     @staticmethod
     @_amp_bwd
     def backward(ctx, g):
-        B, N, D, H, causal, L, xdtype = ctx.meta
+        B, N, D, H, causal, L, xdtype, k_last, slice_to = ctx.meta
         saved_all = ctx.saved_tensors
         params = ctx.params
         n_saved = len(saved_all) // L
-        cur = _f32c(g).view(B * N, D)
+        if slice_to is not None:           # full path behind a kept prefix: the zero-filled gradient x[:, :keep]'s own backward would build
+            full = torch.zeros((B, N, D), dtype=F32, device=g.device)
+            full[:, :slice_to] = g
+            g = full
+        cur = _f32c(g).view(B * (N if k_last is None else k_last), D)
         arena, sink = grad_arena(D, L, cur.device, params)     # sink: the DDP wrapper whose buckets the arena lives in (or None)
         dy2 = None
         try:
@@ -503,7 +576,8 @@ class TransformerStackFn(torch.autograd.Function):
                 nxt_db2 = arena[i - 1][5] if i > 0 else None      # layer i's first LN backward feeds layer i-1's fc2 bias grad
                 cur, dy2 = layer_backward(cur, saved_all[n_saved * i: n_saved * (i + 1)], wqkv, w1, w2, B, N, H, causal, arena[i],
                                           dy2=dy2, have_db2=dy2 is not None, emit_bf16=i > 0, emit_colsum=nxt_db2,
-                                          drop=ctx.drops[i], emit_dropout=ctx.drops[i - 1][2:] if i > 0 else (0.0, 0))
+                                          drop=ctx.drops[i], emit_dropout=ctx.drops[i - 1][2:] if i > 0 else (0.0, 0),
+                                          keep=k_last if i + 1 == L else None)
                 if sink is not None:
                     # bucket i is complete now: five gradients from this call, and its fc2 bias gradient was
                     # added by layer i+1's LN1 backward (or by this call's own column sum for the top layer)
@@ -512,7 +586,7 @@ class TransformerStackFn(torch.autograd.Function):
         finally:
             join_side(cur.device)       # also on an exception: nothing stays pinned for the side stream
         grads = [t for layer in arena for t in layer]
-        return (cur.view(B, N, D).to(xdtype), None, None, None, None, *grads)
+        return (cur.view(B, N, D).to(xdtype), None, None, None, None, None, *grads)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -57,6 +57,11 @@ SIGNATURES = {
     "vitamd_gemm_skinny_ws_bytes": [_I, _I, _I],
     "vitamd_gemm_skinny_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
     "vitamd_sample_logits": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _U64, _P],
+    "vitamd_layernorm_fwd_keep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "vitamd_layernorm_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P],
+    "vitamd_attention_keep_forms": [_I, _I],
+    "vitamd_attention_fwd_keep": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vitamd_attention_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
 ERRORS = {1: "unsupported shape", 2: "bad argument", 3: "HIP launch failure", 4: "vitamd_init has not run for this device"}

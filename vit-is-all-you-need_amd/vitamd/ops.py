@@ -210,17 +210,46 @@ def layernorm_fwd(x, addend=None):
     return (x_out if addend is not None else x), y, mean, rstd
 
 
-def layernorm_bwd(dy, x, mean, rstd, g_res=None, want_bf16=False, colsum=None, dropout=(0.0, 0), xhat=None):
+def layernorm_fwd_keep(x, addend, B, seq, keep):
+    """Kept-row form: x fp32 [B*seq, D] (the full stream), addend bf16 [B*keep, D] (compact) -> compact (x_sum fp32 [B*keep, D], y bf16,
+    mean, rstd); output row b*keep + t = LN(x[b*seq + t] + addend[b*keep + t]), the same per-row arithmetic as layernorm_fwd."""
+    _need(x, F32, "x", 2); _need(addend, BF16, "addend", 2)
+    D = x.shape[1]
+    if x.shape[0] != B * seq or tuple(addend.shape) != (B * keep, D) or not 0 < keep <= seq:
+        raise _lib.VitamdError(f"layernorm_fwd_keep: x must be [B*seq, D], addend [B*keep, D], 0 < keep <= seq (B={B}, seq={seq}, keep={keep})")
+    Mk = B * keep
+    x_out = torch.empty((Mk, D), dtype=F32, device=x.device)
+    y = torch.empty((Mk, D), dtype=BF16, device=x.device)
+    mean = torch.empty((Mk,), dtype=F32, device=x.device)
+    rstd = torch.empty((Mk,), dtype=F32, device=x.device)
+    _lib.check(_L().vitamd_layernorm_fwd_keep(_p(x), _p(addend), _p(x_out), _p(y), _p(mean), _p(rstd), B, seq, keep, D, LN_EPS, _stream()),
+               f"layernorm_fwd_keep[B={B},seq={seq},keep={keep},D={D}]")
+    return x_out, y, mean, rstd
+
+
+def layernorm_bwd(dy, x, mean, rstd, g_res=None, want_bf16=False, colsum=None, dropout=(0.0, 0), xhat=None, keep=None):
     """g = (g_res or 0) + LN'(dy); returns (g fp32, bf16(g) or None).  dropout=(p, seed): the bf16 copy
     also gets that dropout mask (it is then the gradient of a dropped-out Linear output).
     xhat: the forward's bf16 output (= xhat for this non-affine LayerNorm); given, and D in {256,512,768,1024}, the kernel reads
-    it instead of recomputing xhat from the fp32 x (2 B instead of 4 B per element of an HBM-bound kernel)."""
+    it instead of recomputing xhat from the fp32 x (2 B instead of 4 B per element of an HBM-bound kernel).
+    keep=(seq, k): g_res is COMPACT fp32 [M/seq*k, D] - row b*seq + t adds g_res[b*k + t] when t < k, nothing otherwise."""
     _need(dy, BF16, "dy", 2); _need(x, F32, "x", 2)
     M, D = x.shape
     g = torch.empty_like(x)
     gb = torch.empty((M, D), dtype=BF16, device=x.device) if want_bf16 else None
     if g_res is not None:
         _need(g_res, F32, "g_res", 2)
+    if keep is not None:
+        seq, k = keep
+        if g_res is None or M % seq or not 0 < k <= seq or tuple(g_res.shape) != (M // seq * k, D):
+            raise _lib.VitamdError(f"layernorm_bwd: keep=({seq}, {k}) needs M % seq == 0 and g_res fp32 [M/seq*k, D]")
+        use_xhat = xhat is not None and D in (256, 512, 768, 1024)
+        if use_xhat:
+            _need(xhat, BF16, "xhat", 2)
+        code = _L().vitamd_layernorm_bwd_keep(_p(dy), _p(xhat if use_xhat else x), _p(mean), _p(rstd), _p(g_res), _p(g), _p(gb), _p(colsum),
+                                              M // seq, seq, k, D, int(use_xhat), float(dropout[0]), int(dropout[1]), _stream())
+        _lib.check(code, f"layernorm_bwd_keep[M={M},D={D},seq={seq},keep={k}]")
+        return g, gb
     if xhat is not None and D in (256, 512, 768, 1024):
         _need(xhat, BF16, "xhat", 2)
         code = _L().vitamd_layernorm_bwd_xhat(_p(dy), _p(xhat), _p(rstd), _p(g_res), _p(g), _p(gb), _p(colsum), M, D,
@@ -318,6 +347,43 @@ def attention_bwd(qkv, o, lse, d_o, B, N, H, causal=False, dbias=None, dropout=(
     code = _L().vitamd_attention_bwd(_p(qkv), _p(o), _p(lse), _p(d_o), _p(dqkv), _p(delta), _p(dbias), B, N, H, 64, int(causal),
                                      float(dropout[0]), int(dropout[1]), _stream())
     _lib.check(code, f"attention_bwd[B={B},N={N},H={H}]")
+    return dqkv
+
+
+KEEP_FWD, KEEP_BWD = 1, 2          # include/vitamd.h vitamd_attention_keep_forms
+
+
+def attention_keep_forms(N, nq):
+    """Which kept-query attention kernels serve (N, nq): a mask of KEEP_FWD (129 <= N <= 256) and KEEP_BWD (33 <= N <= 224, nq <= 128)."""
+    return int(_L().vitamd_attention_keep_forms(int(N), int(nq)))
+
+
+def attention_fwd_keep(qkv, B, N, H, nq):
+    """Kept-query forward (non-causal, no dropout): qkv bf16 [B*N, 3*H*64] -> o bf16 COMPACT [B*nq, H*64] (row b*nq + t) for the queries
+    t < nq, and lse2 fp32 [B, H, N] of which only [..., :nq] is written.  The kept rows are bit-identical to attention_fwd's."""
+    _need(qkv, BF16, "qkv", 2)
+    D = H * 64
+    if tuple(qkv.shape) != (B * N, 3 * D) or not 0 < nq <= N:
+        raise _lib.VitamdError("attention_fwd_keep: qkv must be [B*N, 3*H*64] (head_dim 64 only) and 0 < nq <= N")
+    o = torch.empty((B * nq, D), dtype=BF16, device=qkv.device)
+    lse = torch.empty((B, H, N), dtype=F32, device=qkv.device)
+    _lib.check(_L().vitamd_attention_fwd_keep(_p(qkv), _p(o), _p(lse), B, N, H, 64, nq, _stream()), f"attention_fwd_keep[B={B},N={N},H={H},nq={nq}]")
+    return o, lse
+
+
+def attention_bwd_keep(qkv, o, lse, d_o, B, N, H, nq, dbias=None):
+    """Kept-query backward: o, d_o bf16 COMPACT [B*nq, H*64]; lse fp32 [B, H, N] (entries [..., :nq] read) -> dense dqkv bf16 [B*N, 3*H*64]
+    whose Q rows >= nq are zeros; equal to attention_bwd given d_o zero-padded to N rows.  dbias as in attention_bwd."""
+    _need(qkv, BF16, "qkv", 2); _need(o, BF16, "o", 2); _need(d_o, BF16, "d_o", 2); _need(lse, F32, "lse")
+    D = H * 64
+    if tuple(qkv.shape) != (B * N, 3 * D) or tuple(o.shape) != (B * nq, D) or tuple(d_o.shape) != (B * nq, D) or lse.numel() != B * H * N:
+        raise _lib.VitamdError("attention_bwd_keep: qkv [B*N, 3*H*64], o and d_o compact [B*nq, H*64], lse [B, H, N]")
+    if dbias is not None:
+        _need(dbias, F32, "dbias", 1)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty_like(lse)
+    _lib.check(_L().vitamd_attention_bwd_keep(_p(qkv), _p(o), _p(lse), _p(d_o), _p(dqkv), _p(delta), _p(dbias), B, N, H, 64, nq, _stream()),
+               f"attention_bwd_keep[B={B},N={N},H={H},nq={nq}]")
     return dqkv
 
 
