@@ -278,6 +278,10 @@ int vitamd_conv3x3_bwd(const float* x, const float* w, const float* dy, float* d
  * parameters in place; m, v are the optimiser state.  replaces train_vit.py:82,105 (torch.optim.AdamW). */
 int vitamd_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                       float eps, float weight_decay, int step, void* stream);
+/* The same with beta1 / beta2 in double, as torch.optim.AdamW holds them: the coefficients beta and 1 - beta are each rounded to fp32 once
+ * (with fp32 betas, 1 - beta inherits the rounding of beta: 1.3e-5 relative on exp_avg_sq at beta2 = 0.999).  vitamd.optim.AdamW calls this one. */
+int vitamd_adamw_step_d(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2,
+                        float eps, float weight_decay, int step, void* stream);
 
 #ifdef __cplusplus
 }

@@ -448,7 +448,7 @@ def test_gemm_tn_overwrite_mode_without_workspace_is_refused(hip):
 
 
 # ------------------------------------------------------------------------------------------ layernorm
-@pytest.mark.parametrize("M,D", [(1, 768), (777, 768), (320, 512), (111, 128), (50, 1024), (33, 200)])
+@pytest.mark.parametrize("M,D", [(1, 768), (777, 768), (320, 512), (111, 128), (50, 1024), (33, 200), (777, 256), (5, 256)])
 def test_layernorm_fwd_bwd(hip, M, D):
     from vitamd import ops
     x = randn((M, D), 21, 2.0) + 0.5

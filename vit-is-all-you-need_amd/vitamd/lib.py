@@ -15,7 +15,7 @@ CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 ABI_VERSION = 9
 
 _c = ctypes
-_P, _I, _F, _L, _U64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_long, _c.c_ulonglong
+_P, _I, _F, _L, _U64, _D = _c.c_void_p, _c.c_int, _c.c_float, _c.c_long, _c.c_ulonglong, _c.c_double
 
 # name -> argtypes ; every function returns int (VITAMD_OK == 0)
 SIGNATURES = {
@@ -51,6 +51,7 @@ SIGNATURES = {
     "vitamd_conv3x3_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_conv3x3_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_adamw_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P],
+    "vitamd_adamw_step_d": [_P, _P, _P, _P, _L, _F, _D, _D, _F, _F, _I, _P],
     "vitamd_kv_append": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_decode_attention_ws_bytes": [_I, _I, _I],
     "vitamd_decode_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],

@@ -36,9 +36,9 @@ class AdamW(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p)
                 st["step"] += 1
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                code = L.vitamd_adamw_step(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                           p.numel(), float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], st["step"],
-                                           stream)
+                code = L.vitamd_adamw_step_d(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                                             p.numel(), float(group["lr"]), float(b1), float(b2), group["eps"], group["weight_decay"], st["step"],
+                                             stream)
                 _lib.check(code, "adamw_step")
         from .functions import WEIGHTS
         WEIGHTS.clear()   # the kernel updated the weights behind torch's version counters: drop the bf16 copies
