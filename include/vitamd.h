@@ -179,7 +179,7 @@ int vitamd_attention_bwd_keep(const void* qkv, const void* o, const float* lse2,
 
 /* ---- KV-cached decoding (autoregressive generation on a causal stack) ---------------------------------
  * The reference has no cache: VideoGPT.generate (train_videogpt.py:56-65) re-runs the whole stack over the whole prefix for every new
- * token.  These three entry points run one token per sequence per call against a per-layer cache instead.
+ * token.  These entry points run one token per sequence per call against a per-layer cache instead.
  * Cache layout (per layer): k_cache, v_cache bf16 [B][H][Lmax][64].  `len` is a DEVICE int32: the number of positions already held
  * (the grids are sized from Lmax, work past the length exits early, so a decode step needs no host synchronisation).
  * head_dim must be 64 and 1 <= Lmax <= 16384, else VITAMD_ERR_SHAPE.  The caller advances *len after a token's layers have run.
@@ -208,6 +208,21 @@ int vitamd_decode_attention(const void* qkv, const void* k_cache, const void* v_
 long vitamd_gemm_skinny_ws_bytes(int M, int N, int K);
 int vitamd_gemm_skinny_bf16(const void* A, const void* W, void* out, void* out2, const float* bias, const float* aux, int M, int N,
                             int K, int epi, float* ws, long ws_bytes, void* stream);
+
+/* The QKV Linear of a decode step with the K/V append in its epilogue: qkv bf16 [M, 3*H*64] = bf16(A[M,K] . W[3*H*64,K]^T + bias), bit-equal
+ * to vitamd_gemm_skinny_bf16(..., VITAMD_EPI_BIAS_BF16) (same plan, K split and summation order; ws of vitamd_gemm_skinny_ws_bytes(M, 3*H*64, K)),
+ * and the store step of the K and V column ranges also writes the same packed values to row *len of k_cache / v_cache bf16 [M][H][Lmax][64]
+ * (row m of the GEMM is sequence m): the caches end up bit-equal to vitamd_kv_append(T = 1) on that output, one launch fewer per layer.
+ * Nothing is written to the caches when *len is outside [0, Lmax).  head_dim must be 64, 1 <= M <= 64, 1 <= Lmax <= 16384, K % 64 == 0. */
+int vitamd_gemm_skinny_qkv_append(const void* A, const void* W, void* qkv, const float* bias, void* k_cache, void* v_cache, const int* len,
+                                  int M, int H, int K, int head_dim, int Lmax, float* ws, long ws_bytes, void* stream);
+/* Embedding of one decoded token per sequence at the device-resident position: x fp32 [B, D] with x[b, :] = tok_table[token[b], :] +
+ * pos_table[*len, :] (one fp32 add: bit-equal to the framework's gather-and-add).  Tables fp32 [tok_rows, D] / [pos_rows, D], token int64 [B]
+ * on the device, len the DEVICE int32 the cache kernels read, D % 4 == 0.  A token outside [0, tok_rows) or a *len outside [0, pos_rows)
+ * leaves that row of x untouched; no table is ever read out of bounds.  With it a decode step holds no host value and can be captured
+ * into a graph.  replaces train_videogpt.py:59 (tok_embed + pos_embed) for the one new position of a cached step. */
+int vitamd_decode_embed(const float* tok_table, const float* pos_table, const long long* token, const int* len, float* x, int B, int D,
+                        int tok_rows, int pos_rows, void* stream);
 
 /* Sampled generation: one token per row of fp32 logits [B, V] (row stride ld >= V elements, 2 <= V <= 65536, else VITAMD_ERR_SHAPE), in one
  * launch, one workgroup per row, in the order of the usual logits processors:

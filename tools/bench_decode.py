@@ -4,6 +4,9 @@
   cached      - one whole VideoGPT.generate_frames call (prefill of 513 positions + 511 decode steps), ms per generated token and tokens/s
   sampled     - the same call with temperature=1.0, top_k=100, top_p=0.95 (one sampling kernel + one counter add per token in place of the
                 argmax), timed in rounds interleaved with the greedy ones
+  graph       - the same two calls with graph=True (vitamd.graph.GraphedDecoder: every token after the first is one graph launch plus one
+                copy of the picked tokens), greedy and sampled, in the same interleaved rounds; min / median / max over the reps and the
+                launches per token of each path (counted, not timed: every C-ABI call and every torch device op of one decode step)
   uncached    - the reference's loop (the whole prefix through the stack per token, on the HIP stack), timed for single steps at prefix
                 lengths spread over the run (513 .. 1024) and averaged: ms per generated token
   kernels     - hipEvent time of each decode kernel at the shapes of one decode step, against its HBM byte floor (skinny GEMMs: the weight
@@ -36,6 +39,63 @@ def _events_ms(fn, reps):
     return s.elapsed_time(e) / reps
 
 
+_NO_LAUNCH = {"view", "_unsafe_view", "select", "slice", "reshape", "_reshape_alias", "unsqueeze", "squeeze", "expand", "permute", "transpose", "t",
+              "detach", "alias", "as_strided", "empty", "empty_like", "empty_strided", "new_empty", "lift_fresh", "unbind", "split", "narrow"}
+
+
+class _HostCalls:
+    """Counts what the host issues inside a `with`: C-ABI calls of libvitamd (one or two kernels each: a split-K GEMM or a split attention
+    has a second, reducing launch), torch device ops (views and allocations left out) and graph replays."""
+
+    def __init__(self):
+        from torch.utils._python_dispatch import TorchDispatchMode
+        from vitamd import lib
+        self.n, self.lib = 0, lib.load()
+        outer = self
+
+        class Mode(TorchDispatchMode):
+            def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+                if func.overloadpacket.__name__ not in _NO_LAUNCH:
+                    outer.n += 1
+                return func(*args, **(kwargs or {}))
+        self.mode = Mode()
+
+    def __enter__(self):
+        from vitamd import lib
+        self.saved = {}
+        for name in lib.SIGNATURES:
+            fn = getattr(self.lib, name)
+            if name.endswith("_bytes") or name in ("vitamd_abi_version", "vitamd_gemm_nt_plan", "vitamd_attention_keep_forms"):
+                continue
+            self.saved[name] = fn
+
+            def counted(*a, _fn=fn):
+                self.n += 1
+                return _fn(*a)
+            setattr(self.lib, name, counted)
+        self.replay = torch.cuda.CUDAGraph.replay
+
+        def replay(g):
+            self.n += 1
+            return self.replay(g)
+        torch.cuda.CUDAGraph.replay = replay
+        self.mode.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        self.mode.__exit__(*exc)
+        torch.cuda.CUDAGraph.replay = self.replay
+        for name, fn in self.saved.items():
+            setattr(self.lib, name, fn)
+
+
+def _host_calls(fn):
+    with _HostCalls() as c:
+        fn()
+        torch.cuda.synchronize()
+    return c.n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -57,20 +117,52 @@ def main():
     SAMPLING = dict(temperature=1.0, top_k=100, top_p=0.95)
     model.generate_frames(video, n=FRAMES - COND, seed=0, **SAMPLING)
     torch.cuda.synchronize()
-    times, times_s = [], []
-    for r in range(args.reps):                                     # greedy and sampled rounds interleaved: one process, one clock state
+    out_g = model.generate_frames(video, n=FRAMES - COND, graph=True)      # the capture happens here, outside the timed rounds
+    torch.cuda.synchronize()
+    assert torch.equal(out_g, out), "graph=True must give the eager cached tokens"
+
+    def timed(**kw):
         t0 = time.perf_counter()
-        out = model.generate_frames(video, n=FRAMES - COND)
+        o = model.generate_frames(video, n=FRAMES - COND, **kw)
         torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-        t0 = time.perf_counter()
-        model.generate_frames(video, n=FRAMES - COND, seed=r, **SAMPLING)
-        torch.cuda.synchronize()
-        times_s.append(time.perf_counter() - t0)
-    t_cached = sorted(times)[len(times) // 2]
-    t_sampled = sorted(times_s)[len(times_s) // 2]
+        return time.perf_counter() - t0, o
+    times, times_s, times_g, times_gs = [], [], [], []
+    # Eager and graph rounds interleaved: one process, one clock state.  The model keeps ONE decoder, so alternating greedy and sampled
+    # graph rounds would capture every time: the sampled graph rounds follow in a second loop, each beside an eager sampled round, with
+    # one seed throughout (the seed is part of the decoder's key).
+    for r in range(args.reps):
+        t, out = timed()
+        times.append(t)
+        times_s.append(timed(seed=0, **SAMPLING)[0])
+        times_g.append(timed(graph=True)[0])
+    model.generate_frames(video, n=FRAMES - COND, graph=True, seed=0, **SAMPLING)      # capture of the sampled decoder, untimed
+    torch.cuda.synchronize()
+    for r in range(args.reps):
+        times_s.append(timed(seed=0, **SAMPLING)[0])
+        times_gs.append(timed(graph=True, seed=0, **SAMPLING)[0])
+    med = lambda ts: sorted(ts)[len(ts) // 2]
+    t_cached, t_sampled = med(times), med(times_s)
     cached_ms_tok = t_cached * 1e3 / n_gen
     sampled_ms_tok = t_sampled * 1e3 / n_gen
+
+    def spread(ts):
+        return {"ms_per_token": round(med(ts) * 1e3 / n_gen, 4), "min": round(min(ts) * 1e3 / n_gen, 4), "max": round(max(ts) * 1e3 / n_gen, 4),
+                "reps": len(ts)}
+    # launches per token: the host's calls of one whole generation minus those of the prefill and first pick, over the remaining tokens
+    tokens0 = video.reshape(B, -1)
+    first = _host_calls(lambda: model.generate(tokens0, n=1))
+    first_s = _host_calls(lambda: model.generate(tokens0, n=1, seed=0, **SAMPLING))
+    calls = {"eager_greedy": (_host_calls(lambda: model.generate_frames(video, n=FRAMES - COND)) - first) / (n_gen - 1),
+             "eager_sampled": (_host_calls(lambda: model.generate_frames(video, n=FRAMES - COND, seed=0, **SAMPLING)) - first_s) / (n_gen - 1),
+             "graph_sampled": (_host_calls(lambda: model.generate_frames(video, n=FRAMES - COND, graph=True, seed=0, **SAMPLING)) - first_s) / (n_gen - 1)}
+    model.generate_frames(video, n=FRAMES - COND, graph=True)              # back to the greedy decoder (a capture, not counted)
+    calls["graph_greedy"] = (_host_calls(lambda: model.generate_frames(video, n=FRAMES - COND, graph=True)) - first) / (n_gen - 1)
+    graph = {"greedy": dict(spread(times_g), eager=spread(times), host_calls_per_token=round(calls["graph_greedy"], 2),
+                            eager_host_calls_per_token=round(calls["eager_greedy"], 2),
+                            eager_over_graph=round(med(times) / med(times_g), 3)),
+             "sampled": dict(spread(times_gs), eager=spread(times_s), host_calls_per_token=round(calls["graph_sampled"], 2),
+                             eager_host_calls_per_token=round(calls["eager_sampled"], 2),
+                             eager_over_graph=round(med(times_s) / med(times_gs), 3))}
 
     # ---- uncached: single steps of the reference loop at prefix lengths spread over the run
     toks = out[:, : S0 + n_gen - 1]
@@ -127,6 +219,7 @@ def main():
                    "tokens_per_s": round(B * n_gen / t_cached, 1)},
         "sampled": dict(SAMPLING, generate_frames_s=round(t_sampled, 4), ms_per_token=round(sampled_ms_tok, 4),
                         tokens_per_s=round(B * n_gen / t_sampled, 1), over_cached=round(sampled_ms_tok / cached_ms_tok, 4)),
+        "graph": graph,
         "uncached": {"ms_per_token": round(uncached_ms_tok, 3), "step_ms_by_length": step_ms,
                      "generate_frames_s_estimate": round(uncached_ms_tok * n_gen / 1e3, 3)},
         "speedup": round(uncached_ms_tok / cached_ms_tok, 2),

@@ -1,5 +1,6 @@
 // Kernels of KV-cached autoregressive decoding: the K/V append, single-query attention over the cache
-// (flash-decoding split + deterministic combine) and the skinny-M GEMM that streams a Linear's weights once across the chip.
+// (flash-decoding split + deterministic combine), the skinny-M GEMM that streams a Linear's weights once across the chip, its QKV form
+// that appends K/V from the epilogue, and the embedding of a decoded token at the device-resident position.
 // The current length is read from a device int32 (never a host integer), so a decode step enqueues without host synchronisation;
 // grids are sized from the cache capacity Lmax and work past the length exits early.
 #include "common.h"
@@ -193,6 +194,23 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(__bf16* __restr
   o[(size_t)b * H * DH + h * DH + d] = f2bf(A / L);
 }
 
+// ------------------------------------------------------------------------------------------------ a2. decoded-token embedding
+// x[b, :] = tok[token[b], :] + pos[*len, :], one thread per 4 columns.  A token or a position outside its table: the row is left alone.
+__global__ __launch_bounds__(256) void decode_embed_kernel(const float* __restrict__ tok, const float* __restrict__ pos,
+                                                          const long long* __restrict__ token, const int* __restrict__ len,
+                                                          float* __restrict__ x, int B, int D, int tok_rows, int pos_rows) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int dq = D / 4;
+  if (i >= B * dq) return;
+  const int b = i / dq, c = (i - b * dq) * 4;
+  const long long t = token[b];
+  const int l = *len;
+  if (t < 0 || t >= tok_rows || l < 0 || l >= pos_rows) return;
+  const f32x4 a = *(const f32x4*)(tok + (size_t)t * D + c);
+  const f32x4 e = *(const f32x4*)(pos + (size_t)l * D + c);
+  *(f32x4*)(x + (size_t)b * D + c) = a + e;
+}
+
 // ------------------------------------------------------------------------------------------------ c. skinny-M GEMM
 // out = epi(A[M,K] . W[N,K]^T), 1 <= M <= 64.  Workgroup = 64 output columns (4 waves x 16) x one K range of `ks`; the A slice is staged
 // in LDS once per workgroup (rows padded with zeros to 16*MT, 16-B row pad), each wave streams its 16 weight rows straight into VGPRs
@@ -209,7 +227,12 @@ struct SkinnyArgs {
   float* ws;                 // [splits][M][N] fp32 partials (splits > 1)
   const unsigned* gelu_tab;
   int M, N, K, ks, splits;
+  __bf16* kc;                // EPI_QKV_APPEND only: k / v cache [M][H][Lmax][64], the device length, H and Lmax
+  __bf16* vc;
+  const int* len;
+  int H, Lmax;
 };
+constexpr int EPI_QKV_APPEND = 100;     // internal: EPI_BIAS_BF16 whose K and V column ranges also go to row *len of the caches
 struct SkinnyPlan { int splits, ks; };
 // split K until the N tiles cover the CUs, keeping >= 128 K per split and the LDS image of A under ~65 KiB (ks <= 512)
 SkinnyPlan skinny_plan(int M, int N, int K) {
@@ -235,6 +258,15 @@ __device__ __forceinline__ void skinny_store(const SkinnyArgs& p, int m, int n, 
   const size_t at = (size_t)m * p.N + n;
   if constexpr (EPI == EPI_BIAS_BF16) {
     *(u32x2*)((__bf16*)p.out + at) = (u32x2){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+  } else if constexpr (EPI == EPI_QKV_APPEND) {
+    const u32x2 pk = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+    *(u32x2*)((__bf16*)p.out + at) = pk;
+    const int D = p.H * DH, which = n / D;              // 0 = q, 1 = k, 2 = v; n % 4 == 0 and D % 64 == 0: the 4 columns share a head
+    const int pos = *p.len;
+    if (which >= 1 && pos >= 0 && pos < p.Lmax) {       // kv_append_kernel's guard: never write outside the cache
+      const int c = n - which * D, h = c / DH, d = c - h * DH;
+      *(u32x2*)((which == 1 ? p.kc : p.vc) + (((size_t)m * p.H + h) * p.Lmax + pos) * DH + d) = pk;
+    }
   } else if constexpr (EPI == EPI_GELU) {
     const u32x2 pz = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
     u32x2 g, unused = pz;
@@ -405,7 +437,7 @@ extern "C" int vitamd_gemm_skinny_bf16(const void* A, const void* W, void* out, 
   const SkinnyPlan pl = skinny_plan(M, N, K);
   const long need = skinny_ws_bytes(pl, M, N);
   if (need > 0 && (!ws || ws_bytes < need)) return VITAMD_ERR_ARG;
-  SkinnyArgs p{(const __bf16*)A, (const __bf16*)W, out, out2, bias, aux, ws, nullptr, M, N, K, pl.ks, pl.splits};
+  SkinnyArgs p{(const __bf16*)A, (const __bf16*)W, out, out2, bias, aux, ws, nullptr, M, N, K, pl.ks, pl.splits, nullptr, nullptr, nullptr, 0, 0};
   if (epi == EPI_GELU) {
     p.gelu_tab = vitamd_gelu_table();
     if (!p.gelu_tab) return VITAMD_ERR_INIT;
@@ -417,4 +449,29 @@ extern "C" int vitamd_gemm_skinny_bf16(const void* A, const void* W, void* out, 
     case EPI_RESID_F32: return launch_skinny_mt<EPI_RESID_F32>(p, s);
     default: return launch_skinny_mt<EPI_F32>(p, s);
   }
+}
+
+extern "C" int vitamd_gemm_skinny_qkv_append(const void* A, const void* W, void* qkv, const float* bias, void* k_cache, void* v_cache,
+                                             const int* len, int M, int H, int K, int head_dim, int Lmax, float* ws, long ws_bytes,
+                                             void* stream) {
+  if (!A || !W || !qkv || !k_cache || !v_cache || !len) return VITAMD_ERR_ARG;
+  if (head_dim != DH || H <= 0 || H > 1024 || Lmax <= 0 || Lmax > MAX_LEN) return VITAMD_ERR_SHAPE;
+  const int N = 3 * H * DH;
+  if (!skinny_shape_ok(M, N, K)) return VITAMD_ERR_SHAPE;
+  const SkinnyPlan pl = skinny_plan(M, N, K);
+  const long need = skinny_ws_bytes(pl, M, N);
+  if (need > 0 && (!ws || ws_bytes < need)) return VITAMD_ERR_ARG;
+  const SkinnyArgs p{(const __bf16*)A, (const __bf16*)W, qkv, nullptr, bias, nullptr, ws, nullptr, M, N, K, pl.ks, pl.splits,
+                     (__bf16*)k_cache, (__bf16*)v_cache, len, H, Lmax};
+  return launch_skinny_mt<EPI_QKV_APPEND>(p, (hipStream_t)stream);
+}
+
+extern "C" int vitamd_decode_embed(const float* tok_table, const float* pos_table, const long long* token, const int* len, float* x, int B,
+                                   int D, int tok_rows, int pos_rows, void* stream) {
+  if (!tok_table || !pos_table || !token || !len || !x) return VITAMD_ERR_ARG;
+  if (B <= 0 || D < 4 || D % 4 != 0 || tok_rows <= 0 || pos_rows <= 0 || (long)B * (D / 4) > 0x7fffffffL) return VITAMD_ERR_SHAPE;
+  const long threads = (long)B * (D / 4);
+  hipLaunchKernelGGL(decode_embed_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tok_table, pos_table,
+                     token, len, x, B, D, tok_rows, pos_rows);
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }

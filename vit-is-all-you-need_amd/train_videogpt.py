@@ -6,7 +6,8 @@ The causal stack runs on the HIP kernels (transformer.Transformer -> Transformer
 (functions.linear in forward, the skinny-M GEMM with fp32 logits in generate); the embedding gathers, the cross-entropy and the greedy
 argmax are torch device ops (as the loss is in train_vit.train_step); sampled generation (temperature / top-k / top-p) draws each token
 in one HIP kernel (csrc/sample.hip).  `generate` adds a KV cache (vitamd/decode.py): the prompt is prefilled
-once and every further token costs one single-row pass through the stack.  The reference's training loop and its external TiTok
+once and every further token costs one single-row pass through the stack - with graph=True one graph launch (vitamd/graph.py
+GraphedDecoder).  The reference's training loop and its external TiTok
 video tokenizer (train_videogpt.py:68-150) are not part of this module."""
 from dataclasses import dataclass
 
@@ -43,6 +44,7 @@ class VideoGPT(nn.Module):
         self.pos_embed = nn.Embedding(config.max_tokens, config.n_embd)
         self.transformer = Transformer(config.trans_config)
         self.proj = nn.Linear(config.n_embd, config.codebook_size)
+        self._graph_key, self._graph_decoder = None, None      # generate(graph=True): the most recent captured decoder and what it was built for
 
     def _embed(self, ids, pos0=0):
         """token + position embeddings of ids [B, S] at positions pos0 .. pos0+S-1 (train_videogpt.py:49,59), fp32"""
@@ -93,20 +95,43 @@ class VideoGPT(nn.Module):
         _ops.check_sampling(sampler.temperature, sampler.top_k, sampler.top_p, self.config.codebook_size)
         return sampler
 
+    def _decoder(self, B, max_len, sampling, device):
+        """the captured decode step for this key, reused when the last call had the same one (its sampler then starts again at position 0)"""
+        key = (B, max_len, sampling, str(device))
+        if self._graph_key != key or self._graph_decoder is None:
+            self._graph_key = self._graph_decoder = None         # the old graph's memory goes before the new capture
+            sampler = None if sampling is None else self._sampler(*sampling)
+            dec = self.transformer.graphed_decoder(B, max_len, embed=(self.tok_embed.weight, self.pos_embed.weight), head=self._head,
+                                                   sampler=sampler, head_weights=[self.proj.weight, self.proj.bias])
+            self._graph_key, self._graph_decoder = key, dec
+        self._graph_decoder.reset()                              # empty cache: prefill() then checks the graph against the current operands
+        return self._graph_decoder
+
     @torch.no_grad()
-    def generate(self, tokens, n=1, use_cache=None, *, temperature=None, top_k=None, top_p=None, seed=0):
+    def generate(self, tokens, n=1, use_cache=None, *, temperature=None, top_k=None, top_p=None, seed=0, graph=False):
         """Continuation of tokens [B, S] by n tokens -> [B, S + n] (train_videogpt.py:54-63).  use_cache: None = cached when
         dropout == 0; False = the reference's loop (the whole prefix through the stack per token) on the HIP stack.
         temperature / top_k / top_p all None: greedy (the reference's argmax).  Any of them given: sampled on the device, one kernel
         launch per token (vitamd.sampling.Sampler: temperature -> top-k -> top-p -> draw; the others default to 1.0 / 0 / 1.0 = off),
-        token t of the continuation drawn at position t of the Philox stream of `seed` on either loop: one seed, one continuation."""
+        token t of the continuation drawn at position t of the Philox stream of `seed` on either loop: one seed, one continuation.
+        graph=True (implies the cached loop; dropout must be 0): the prefill and the first pick run eagerly, every further token is one
+        replay of a captured decode step (vitamd.graph.GraphedDecoder: embedding, stack, head and pick in one graph launch), never
+        synchronising with the host - the same tokens as graph=False, bit for bit.  The model keeps its most recent decoder and reuses it
+        for the same (batch, S + n, sampling parameters and seed, device); another key captures again."""
         B, S = tokens.shape
+        if graph:
+            if use_cache is not None and not use_cache:
+                raise ValueError("generate(graph=True) replays the KV-cached decode step; it cannot be combined with use_cache=False")
+            if self.config.dropout > 0:
+                raise ValueError(f"generate(graph=True) needs dropout == 0 (got {self.config.dropout}): it runs the KV-cached loop")
         if n < 1:
             return tokens
         if S + n > self.config.max_tokens:
             raise ValueError(f"generate: {S} + {n} tokens need {S + n} positions, the model has max_tokens = {self.config.max_tokens}")
         cached = self._use_cache(use_cache)
         sampler = self._sampler(temperature, top_k, top_p, seed)
+        if graph:
+            return self._generate_graphed(tokens, n, sampler)
 
         def pick(logits):
             if sampler is None:
@@ -129,8 +154,24 @@ class VideoGPT(nn.Module):
                 h = self.transformer.forward_cached(self._embed(nxt, pos0=cache.len), cache)
         return torch.cat(out, dim=-1)
 
-    def generate_frames(self, video_tokens, n=1, use_cache=None, *, temperature=None, top_k=None, top_p=None, seed=0):
+    def _generate_graphed(self, tokens, n, sampler):
+        B, S = tokens.shape
+        sampling = None if sampler is None else (sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed)
+        dec = self._decoder(B, S + n, sampling, tokens.device)           # the eager cached path's max_len: the same attention chunking
+        out = torch.empty((B, S + n), dtype=tokens.dtype, device=tokens.device)
+        out[:, :S] = tokens
+        h = dec.prefill(self._embed(torch.cat([self._sos(B, tokens.device), tokens], dim=-1)))
+        logits = self._head(h[:, -1])
+        first = torch.argmax(logits, dim=-1) if dec.sampler is None else dec.sampler(logits)        # position 0 of the sampler's stream
+        dec.tokens.copy_(first)
+        out[:, S] = first
+        for t in range(1, n):
+            dec.step()                                                    # one graph launch: embed, stack, head, pick -> dec.tokens
+            out[:, S + t] = dec.tokens                                    # the one eager device op per token
+        return out
+
+    def generate_frames(self, video_tokens, n=1, use_cache=None, *, temperature=None, top_k=None, top_p=None, seed=0, graph=False):
         """video_tokens [B, T, N] -> [B, T*N + n*frame_size] (train_videogpt.py:64-66)"""
         B, T, N = video_tokens.shape
         return self.generate(video_tokens.reshape(B, T * N), n * self.config.frame_size, use_cache=use_cache, temperature=temperature,
-                             top_k=top_k, top_p=top_p, seed=seed)
+                             top_k=top_k, top_p=top_p, seed=seed, graph=graph)

@@ -115,6 +115,12 @@ class Transformer(nn.Module):
         """A KV cache for `batch` sequences of up to `max_len` (default block_size) positions on this module's device.  causal=True only."""
         return decode.new_cache(self, batch, max_len)
 
+    def graphed_decoder(self, batch, max_len=None, **stages):
+        """A vitamd.graph.GraphedDecoder: one decode step of this stack captured as a graph, with its own cache for `batch` sequences of up
+        to `max_len` (default block_size) positions.  stages: embed=, head=, sampler=, head_weights= (see GraphedDecoder).  causal=True only."""
+        from vitamd.graph import GraphedDecoder
+        return GraphedDecoder(self, batch, max_len, **stages)
+
     def forward_cached(self, x, cache):
         """Hidden states of positions cache.len .. cache.len+T-1 given x [B, T, D] of those positions; appends their K/V to `cache`.
         T > 1 prefills an empty cache with the full causal path, T == 1 decodes one token per sequence.  No-grad; dropout must be 0."""

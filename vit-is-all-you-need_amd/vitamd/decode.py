@@ -3,7 +3,7 @@
 The reference samples its causal Transformer without a cache (train_videogpt.py:56-65): every new token re-runs the whole stack over
 the whole prefix.  Here each layer keeps its K and V rows; a decode step runs LN1 -> QKV -> K/V append -> single-query attention
 over the cache -> residual + LN2 -> fc1 + GELU -> fc2 + residual per layer, with the skinny-M GEMM (weights streamed once) for the
-Linears.  The prefill is the existing full causal path (the same kernels as Transformer.forward) plus the append.
+Linears; the QKV GEMM's epilogue writes the K/V rows itself.  The prefill is the existing full causal path (the same kernels as Transformer.forward) plus the append.
 
 Same dtype flow as the training path (vitamd/functions.py): fp32 residual stream and LayerNorm statistics, bf16 GEMM / attention
 operands, the bf16 weights of functions.WEIGHTS.  A no-grad forward; autocast neither changes nor is needed by it.
@@ -78,6 +78,15 @@ def _skinny(a, w, epi, bias, aux=None):
     return torch.cat(parts)
 
 
+def _qkv_append(a, w, bias, k_cache, v_cache, cache, H):
+    """the QKV Linear with the K/V append in its epilogue, over row blocks of at most 64 sequences (each block owns its rows of the caches)"""
+    M, S = a.shape[0], ops.SKINNY_MAX_M
+    if M <= S:
+        return ops.gemm_skinny_qkv_append(a, w, bias, k_cache, v_cache, cache.len_dev, H, host_len=cache.len)
+    return torch.cat([ops.gemm_skinny_qkv_append(a[i:i + S], w, bias, k_cache[i:i + S], v_cache[i:i + S], cache.len_dev, H, host_len=cache.len)
+                      for i in range(0, M, S)])
+
+
 def forward_cached(model, x, cache: KVCache):
     """x fp32 / bf16 [B, T, D]: positions cache.len .. cache.len+T-1 -> their hidden states (x's dtype), cache advanced by T.
     T > 1 (prefill) needs an empty cache."""
@@ -107,8 +116,7 @@ def forward_cached(model, x, cache: KVCache):
             k_cache, v_cache = cache.k[i], cache.v[i]
             _, a, _, _ = ops.layernorm_fwd(cur)                                          # LN1            transformer.py:43
             if T == 1:
-                qkv = _skinny(a, wqkv_b, ops.EPI_BIAS_BF16, bqkv)                        # fused QKV      transformer.py:27
-                ops.kv_append(qkv, k_cache, v_cache, cache.len_dev, B, 1, H, host_len=cache.len)
+                qkv = _qkv_append(a, wqkv_b, bqkv, k_cache, v_cache, cache, H)           # fused QKV + K/V append   transformer.py:27
                 o = ops.decode_attention(qkv, k_cache, v_cache, cache.len_dev, B, H, host_len=cache.len)   # SDPA, last row   transformer.py:28-29
                 x1, bln, _, _ = ops.layernorm_fwd(cur, addend=o)                         # residual + LN2 transformer.py:43-44
                 _, h = _skinny(bln, w1_b, ops.EPI_GELU, b1)                              # fc1 + GELU     transformer.py:37-38

@@ -16,12 +16,18 @@ Shapes and dtypes are frozen at capture.  Not for dropout > 0 (the mask seed is 
 captured launches) and not under vitamd.ddp.DataParallel: its per-parameter hooks and the per-layer `layer_ready` calls are Python
 that runs DURING backward and decides, from bucket state, what to enqueue (and torch.distributed work handles are waited for on the
 host in finish()); none of that replays from a graph.  A DataParallel model is refused at construction.
+
+GraphedDecoder is the other captured form: one decode step of KV-cached generation (vitamd/decode.py) as one graph launch.  Every value
+a decode step depends on lives on the device - the cache length, the sampler's stream position, the token just picked - so a replay
+needs no host value and generation never synchronises.
 """
 from __future__ import annotations
 
 import torch
 
+from . import decode as _decode
 from . import functions as F
+from . import ops as _ops
 
 
 class GraphedStep:
@@ -74,3 +80,139 @@ class GraphedStep:
         for p, g in zip(self.params, self.grads):
             p.grad = g
         return self.loss
+
+
+class GraphedDecoder:
+    """One captured call of decode.forward_cached(x_static, cache), its length advance included, on a single stream (no fork or join).
+
+        dec = model.graphed_decoder(batch, max_len)     # model: a causal transformer.Transformer
+        h = dec.prefill(x_prompt)                       # eager, into the decoder's own cache
+        h = dec.step(x_t)                               # [B, 1, D] -> the static output [B, 1, D]: read it before the next step
+
+    Two optional stages are recorded in the same graph.  embed=(tok_table, pos_table) (fp32 parameters): x_static is computed by
+    ops.decode_embed from the static token buffer `tokens` (int64 [B]) at the cache's device length, before the stack.  head=callable
+    ([B, D] hidden states -> fp32 logits [B, V]): after the stack the logits are picked - torch.argmax, or `sampler` (a
+    vitamd.sampling.Sampler, whose device counter add is then part of the capture) - and the pick is written back into `tokens`, so
+    step() after step() generates.  head_weights: the fp32 parameters `head` reads (matrices through functions.WEIGHTS, biases directly).
+
+    The graph bakes in addresses: the cache, the static buffers, the capture stream's workspace, the bf16 weight copies of
+    functions.WEIGHTS (kept across refreshes) and the fp32 biases / tables.  begin() - called before every generation - refreshes the
+    weight copies eagerly and compares every such address with the captured ones; when one moved it captures again (`captures`
+    counts), so a stale graph is never replayed."""
+
+    def __init__(self, model, batch, max_len=None, *, embed=None, head=None, sampler=None, head_weights=(), warmup=2):
+        _decode.check_decodable(model)
+        self.model, self.batch, self.head, self.sampler = model, int(batch), head, sampler
+        self.embed = None if embed is None else tuple(embed)
+        self.head_weights = list(head_weights)
+        if sampler is not None and head is None:
+            raise ValueError("GraphedDecoder: a sampler needs a head (logits to draw from)")
+        self.cache = _decode.new_cache(model, batch, max_len)
+        device, D = self.cache.device, model.n_embd
+        if self.embed is not None:
+            tok, pos = self.embed
+            if pos.shape[0] < self.cache.max_len:
+                raise ValueError(f"GraphedDecoder: the position table holds {pos.shape[0]} rows, the cache {self.cache.max_len}")
+            if tok.shape[1] != D or pos.shape[1] != D:
+                raise ValueError(f"GraphedDecoder: the embedding tables must be [rows, {D}]")
+        self.x = torch.zeros((batch, 1, D), dtype=torch.float32, device=device)
+        self.tokens = torch.zeros((batch,), dtype=torch.int64, device=device)
+        self.stream = torch.cuda.Stream(device=device)
+        self.warmup = max(1, int(warmup))
+        self.graph, self.out, self.captures, self._baked, self._ws = None, None, 0, None, None
+        with torch.cuda.device(device):
+            self._capture()
+
+    # ---- what the capture records
+    def _body(self):
+        with torch.no_grad():
+            if self.embed is not None:
+                _ops.decode_embed(self.embed[0].detach(), self.embed[1].detach(), self.tokens, self.cache.len_dev, out=self.x.view(self.batch, -1))
+            h = _decode.forward_cached(self.model, self.x, self.cache)
+            if self.head is not None:
+                logits = self.head(h[:, 0])
+                nxt = torch.argmax(logits, dim=-1) if self.sampler is None else self.sampler(logits)
+                self.tokens.copy_(nxt.view(self.batch))
+        return h
+
+    def _weights(self):
+        return [p[j] for layer in self.model.layers for p in (layer._params(),) for j in (0, 2, 4)]
+
+    def _refresh(self):
+        """bf16 weight copies made fresh eagerly (inside the capture WEIGHTS.prepare / get are then no-ops) -> every baked address"""
+        F.WEIGHTS.prepare(self._weights(), False)
+        ptrs = [F.WEIGHTS.get(w, False)[0].data_ptr() for w in self._weights() + [w for w in self.head_weights if w.dim() >= 2]]
+        ptrs += [t.data_ptr() for layer in self.model.layers for t in layer._params()]
+        ptrs += [t.data_ptr() for t in self.head_weights]
+        if self.embed is not None:
+            ptrs += [t.data_ptr() for t in self.embed]
+        return tuple(ptrs)
+
+    def _capture(self):
+        cache, sampler, s = self.cache, self.sampler, self.stream
+        self.graph = self.out = None                    # a graph being replaced is never replayed again
+        self.reset()
+        baked = self._refresh()
+        # warm up ON THE CAPTURE STREAM (as GraphedStep does): vitamd_init, code-object loading, the first hipFuncSetAttribute of each skinny GEMM form, the
+        # allocator and that stream's split-K / attention workspace all happen here, none of them inside the capture
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            _ops.init(cache.device)
+            for _ in range(min(self.warmup, cache.max_len)):
+                self._body()
+            self.reset()                                # length and sampler position back; stale K/V rows past the length are harmless
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self._ws = _ops._WORKSPACES.get((cache.device, s.cuda_stream))      # kept alive: its address is in the graph
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=s):
+            out = self._body()
+        # the capture ran nothing on the device, but the host mirrors moved
+        cache.len = 0
+        if sampler is not None:
+            sampler.step = 0
+        if self._refresh() != baked:
+            raise F.ops._lib.VitamdError("GraphedDecoder: an operand moved during the capture")
+        self.graph, self.out, self._baked = graph, out, baked
+        self.captures += 1
+
+    # ---- interface
+    def begin(self):
+        """Before every generation (prefill() calls it on an empty cache): fresh weight copies, a graph that matches them (captured again when an operand moved), an empty cache and
+        the sampler at position 0."""
+        with torch.cuda.device(self.cache.device):
+            if self.graph is None or self._refresh() != self._baked:
+                self._capture()
+            self.reset()
+        return self
+
+    def reset(self):
+        """Empty cache, sampler at position 0: device fills only."""
+        self.cache.reset()
+        if self.sampler is not None:
+            self.sampler.reset(0)
+
+    def prefill(self, x):
+        """x [B, T, D]: the prompt's positions, run eagerly (the full causal path) into the decoder's cache -> hidden states [B, T, D]"""
+        if self.cache.len == 0:                         # the start of a generation: the graph must match the operands it is about to meet
+            self.begin()
+        return _decode.forward_cached(self.model, x, self.cache)
+
+    def step(self, x=None):
+        """One replay: position cache.len.  x [B, 1, D] is copied into the static input (leave it out with an embed stage: the input then
+        comes from `tokens`).  -> the static hidden states [B, 1, D], overwritten by the next step."""
+        if self.cache.len + 1 > self.cache.max_len:
+            raise ValueError(f"GraphedDecoder.step: {self.cache.len} cached + 1 new position exceed the cache length {self.cache.max_len}")
+        if self.graph is None:
+            raise F.ops._lib.VitamdError("GraphedDecoder.step: no captured graph (a capture failed); call begin()")
+        if x is not None:
+            if self.embed is not None:
+                raise ValueError("GraphedDecoder.step: this decoder embeds its own token buffer; write `tokens` instead of passing x")
+            if tuple(x.shape) != tuple(self.x.shape) or not x.is_cuda:
+                raise F.ops._lib.VitamdError(f"GraphedDecoder was captured for a device input of {tuple(self.x.shape)}, got {tuple(x.shape)}")
+            self.x.copy_(x, non_blocking=True)
+        self.graph.replay()
+        self.cache.len += 1
+        if self.sampler is not None:
+            self.sampler.step += 1
+        return self.out

@@ -57,6 +57,8 @@ SIGNATURES = {
     "vitamd_decode_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
     "vitamd_gemm_skinny_ws_bytes": [_I, _I, _I],
     "vitamd_gemm_skinny_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
+    "vitamd_gemm_skinny_qkv_append": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
+    "vitamd_decode_embed": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vitamd_sample_logits": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _U64, _P],
     "vitamd_layernorm_fwd_keep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "vitamd_layernorm_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P],

@@ -598,6 +598,55 @@ def gemm_skinny(a, w, epi, *, bias=None, aux=None, out=None):
     return (out, out2) if epi == EPI_GELU else out
 
 
+def gemm_skinny_qkv_append(a, w, bias, k_cache, v_cache, length, H, host_len=None):
+    """The QKV Linear of a decode step with the K/V append in its store step: qkv bf16 [M, 3*H*64] = gemm_skinny(a, w, EPI_BIAS_BF16,
+    bias) (the same bits), and its K / V column ranges also written to row len of k_cache / v_cache bf16 [M, H, Lmax, 64] (the bits
+    kv_append(T=1) copies).  1 <= M <= 64; length: device int32 [1]; host_len: the caller's copy, checked (len + 1 <= Lmax) when given."""
+    _need(a, BF16, "a", 2); _need(w, BF16, "w", 2); _need_len(length)
+    M, K = a.shape
+    N, K2 = w.shape
+    Lmax = _need_cache(k_cache, v_cache, M, H)
+    if K != K2:
+        raise _lib.VitamdError(f"gemm_skinny_qkv_append: K mismatch {K} vs {K2}")
+    if N != 3 * H * 64:
+        raise _lib.VitamdError(f"gemm_skinny_qkv_append: w must be [3*H*64, K] = [{3 * H * 64}, {K}], got {tuple(w.shape)}")
+    if not 1 <= M <= SKINNY_MAX_M or K % 64 != 0:
+        raise _lib.VitamdError(f"gemm_skinny_qkv_append[M={M},N={N},K={K}]: needs 1 <= M <= {SKINNY_MAX_M}, K % 64 == 0")
+    if bias is not None:
+        _need(bias, F32, "bias", 1)
+        if bias.numel() != N:
+            raise _lib.VitamdError(f"gemm_skinny_qkv_append: bias must have {N} elements")
+    if host_len is not None and host_len + 1 > Lmax:
+        raise _lib.VitamdError(f"gemm_skinny_qkv_append: len {host_len} + 1 exceeds the cache length {Lmax}")
+    qkv = torch.empty((M, N), dtype=BF16, device=a.device)
+    nbytes = _L().vitamd_gemm_skinny_ws_bytes(M, N, K)
+    ws = _workspace(a.device, nbytes) if nbytes > 0 else None
+    code = _L().vitamd_gemm_skinny_qkv_append(_p(a), _p(w), _p(qkv), _p(bias), _p(k_cache), _p(v_cache), _p(length), M, H, K, 64, Lmax,
+                                              _p(ws), 0 if ws is None else ws.numel() * 4, _stream())
+    _lib.check(code, f"gemm_skinny_qkv_append[M={M},H={H},K={K},Lmax={Lmax}]")
+    return qkv
+
+
+def decode_embed(tok_table, pos_table, tokens, length, out=None):
+    """x fp32 [B, D] = tok_table[tokens] + pos_table[len] (a single fp32 add, the bits of the torch gather-and-add) with the position read
+    from the device: tables fp32 [rows, D], tokens int64 [B] on the device, length device int32 [1].  A token or position outside its
+    table leaves that row of `out` as it was (the kernel never reads outside a table)."""
+    _need(tok_table, F32, "tok_table", 2); _need(pos_table, F32, "pos_table", 2); _need(tokens, torch.int64, "tokens", 1); _need_len(length)
+    B, D = tokens.shape[0], tok_table.shape[1]
+    if pos_table.shape[1] != D or D % 4 != 0 or D < 4:
+        raise _lib.VitamdError(f"decode_embed: tables must share D with D % 4 == 0, got {tuple(tok_table.shape)} / {tuple(pos_table.shape)}")
+    if B < 1:
+        raise _lib.VitamdError("decode_embed: expected at least one token")
+    if out is None:
+        out = torch.empty((B, D), dtype=F32, device=tokens.device)
+    _need(out, F32, "out", 2)
+    if tuple(out.shape) != (B, D):
+        raise _lib.VitamdError(f"decode_embed: out must be [{B}, {D}], got {tuple(out.shape)}")
+    _lib.check(_L().vitamd_decode_embed(_p(tok_table), _p(pos_table), _p(tokens), _p(length), _p(out), B, D, tok_table.shape[0],
+                                        pos_table.shape[0], _stream()), f"decode_embed[B={B},D={D}]")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ sampled generation
 SAMPLE_MAX_V = 65536      # include/vitamd.h vitamd_sample_logits
 
