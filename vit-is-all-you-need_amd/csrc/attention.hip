@@ -16,7 +16,13 @@
 //   bwd dQ  : lane = query.  S^T = K.Q^T ; dP^T = V.dO^T ; dS^T = P^T o (dP^T - delta) ; dQ^T += K^T.dS^T
 //   bwd dKV : lane = key.    S = Q.K^T ; dP = dO.V^T ; dV^T += dO^T.P ; dK^T += Q^T.dS
 // Scores are recomputed from Q, K and the forward's log-sum-exp (flash-attention backward).
+//
+// Shared pieces: the staged output store store_rows_T_img (4-KiB / 2-KiB image, residual add, column sums), zero(), head_addr / stat_index, and on
+// the host make_args, launch and with_tiles / with_flag.  NOT shared, marked TWIN where they stand: the tile bodies of the plain kernels and their
+// *_long_kernel forms and the lane-side set-up of dQ (as __forceinline__ functions they changed registers and waits of those kernels), and the
+// local zeroing loops / addressing lines of the kernels whose code the helpers changed (profiles/attention_shared_source/README.md).
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -71,6 +77,16 @@ __device__ __forceinline__ bf16x8 acc_to_frag(const f32x16& x, int s) {
   return f;
 }
 
+// clear one accumulator tile / a 64x32 pair (three kernels keep their own loops, noted there: the call changed their code)
+__device__ __forceinline__ void zero(f32x16& x) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) x[r] = 0.f;
+}
+__device__ __forceinline__ void zero(f32x16 (&x)[2]) {
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) zero(x[dt]);
+}
+
 // lane-side fragments of a 32-row block: element j = X[r0 + (lane&31)][16kk + 8(lane>>5) + j]
 __device__ __forceinline__ void load_lane_frags(const __bf16* __restrict__ g, int ld, int N, int r0, int lane, bf16x8 (&f)[4]) {
   const int row = min(r0 + (lane & 31), N - 1);
@@ -102,109 +118,48 @@ __device__ __forceinline__ void store_rows_T(__bf16* __restrict__ g, int ld, int
     }
 }
 
-// Same, but transposed through a wave-private 4-KiB LDS image first so that every lane stores 16 B
-// and a wave-instruction covers 8 whole 128-B head rows (4 store instructions instead of 16
-// scattered 8-B ones: the output tail was store-issue bound).
-__device__ __forceinline__ void store_rows_T_lds(__bf16* __restrict__ g, int ld, int N, int r0, int lane, const f32x16 (&acc)[2],
-                                                 float scale, char* img, float* colacc = nullptr) {
+// Same, but transposed through a wave-private LDS image first so that every lane stores 16 B and a wave-instruction covers 8 whole
+// 128-B head rows (4 store instructions instead of 16 scattered 8-B ones: the output tail was store-issue bound).
+//   ROWS = 32: a 4-KiB image, one pass.  colacc: the column sums of the stored bf16 rows are added to it (lane = column).
+//   ROWS = 16: a 2-KiB image, 16 rows per pass, two passes: the 8-wave kernels keep the LDS of a workgroup at 2 x npad x 128 + 8 x 2 KiB,
+//              the footprint of the 4-wave ones, so that two workgroups - now 16 waves - still share a CU.
+//   RES: plus the residual add of the fp32 stream, xo[row][d] = xi[row][d] + bf16(acc) for the same 32 rows x 64 columns (row stride ldx).
+template <int ROWS = 32, bool RES = false>
+__device__ __forceinline__ void store_rows_T_img(__bf16* __restrict__ g, int ld, int N, int r0, int lane, const f32x16 (&acc)[2], float scale, char* img,
+                                                 float* colacc = nullptr, const float* __restrict__ xi = nullptr, float* __restrict__ xo = nullptr,
+                                                 int ldx = 0) {
   const int rr = lane & 31, h = lane >> 5;
+  constexpr int ITS = ROWS / 8;
+  int pass = 0;
 #pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      u32x2 o = {pack_bf16x2(acc[dt][4 * u] * scale, acc[dt][4 * u + 1] * scale),
-                 pack_bf16x2(acc[dt][4 * u + 2] * scale, acc[dt][4 * u + 3] * scale)};
-      // element columns 32dt + 8u + 4h .. +3  -> 16-B chunk 4dt + u, half h ; chunk XOR (row & 7)
-      *(u32x2*)(img + rr * 128 + (((4 * dt + u) ^ (rr & 7)) << 4) + h * 8) = o;
-    }
-  // wave-private image: the same wave reads it back (the compiler orders LDS accesses of one wave)
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = (lane >> 3) + 8 * it, pc = lane & 7;
-    const u32x4 v = *(const u32x4*)(img + row * 128 + pc * 16);
-    if (r0 + row < N) *(u32x4*)(g + (size_t)(r0 + row) * ld + 8 * (pc ^ (row & 7))) = v;
-  }
-  if (colacc) {
-    // column sums of the stored bf16 rows (the bias gradient of the QKV Linear): lane = column
-    const int chunk = lane >> 3, within = (lane & 7) * 2;
-    const int nrows = min(32, N - r0);
-    float sacc = 0.f;
-    for (int row = 0; row < nrows; ++row)
-      sacc += bf2f(*(const __bf16*)(img + row * 128 + ((chunk ^ (row & 7)) << 4) + within));
-    *colacc += sacc;
-  }
-}
-
-// store_rows_T_lds + the residual add of the fp32 stream: xo[row][d] = xi[row][d] + bf16(acc) for the same 32 rows x 64 columns
-__device__ __forceinline__ void store_rows_T_lds_resid(__bf16* __restrict__ g, int ld, int N, int r0, int lane, const f32x16 (&acc)[2],
-                                                       float scale, char* img, const float* __restrict__ xi, float* __restrict__ xo, int ldx) {
-  const int rr = lane & 31, h = lane >> 5;
-  // residual loads first: their latency overlaps the LDS round trip
-  f32x4 r[4][2];
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = (lane >> 3) + 8 * it, pc = lane & 7;
-    const float* px = xi + (size_t)min(r0 + row, N - 1) * ldx + 8 * (pc ^ (row & 7));
-    r[it][0] = *(const f32x4*)px;
-    r[it][1] = *(const f32x4*)(px + 4);
-  }
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      u32x2 o = {pack_bf16x2(acc[dt][4 * u] * scale, acc[dt][4 * u + 1] * scale),
-                 pack_bf16x2(acc[dt][4 * u + 2] * scale, acc[dt][4 * u + 3] * scale)};
-      *(u32x2*)(img + rr * 128 + (((4 * dt + u) ^ (rr & 7)) << 4) + h * 8) = o;
-    }
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = (lane >> 3) + 8 * it, pc = lane & 7;
-    const u32x4 v = *(const u32x4*)(img + row * 128 + pc * 16);
-    if (r0 + row < N) {
-      const int col = 8 * (pc ^ (row & 7));
-      *(u32x4*)(g + (size_t)(r0 + row) * ld + col) = v;
-      f32x4 o0 = {r[it][0][0] + bf16lo(v[0]), r[it][0][1] + bf16hi(v[0]), r[it][0][2] + bf16lo(v[1]), r[it][0][3] + bf16hi(v[1])};
-      f32x4 o1 = {r[it][1][0] + bf16lo(v[2]), r[it][1][1] + bf16hi(v[2]), r[it][1][2] + bf16lo(v[3]), r[it][1][3] + bf16hi(v[3])};
-      float* po = xo + (size_t)(r0 + row) * ldx + col;
-      *(f32x4*)po = o0;
-      *(f32x4*)(po + 4) = o1;
-    }
-  }
-}
-
-// Same through a 2-KiB image (16 rows per pass, two passes): the 8-wave kernels keep the LDS of a workgroup at 2 x npad x 128 + 8 x 2 KiB,
-// the footprint of the 4-wave ones, so that two workgroups - now 16 waves - still share a CU.
-template <bool RES = false>
-__device__ __forceinline__ void store_rows_T_lds2k(__bf16* __restrict__ g, int ld, int N, int r0, int lane, const f32x16 (&acc)[2], float scale, char* img,
-                                                   const float* __restrict__ xi = nullptr, float* __restrict__ xo = nullptr, int ldx = 0) {
-  const int rr = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    f32x4 r[2][2];
+  do {                                         // a do-while: around the single pass of ROWS = 32 it leaves no loop at all (a one-trip for loop changes how hipcc schedules the callers)
+    f32x4 r[ITS][2];
     if constexpr (RES) {                       // residual loads first: their latency overlaps the LDS round trip
 #pragma unroll
-      for (int it = 0; it < 2; ++it) {
+      for (int it = 0; it < ITS; ++it) {
         const int row = (lane >> 3) + 8 * it, pc = lane & 7;
-        const float* px = xi + (size_t)min(r0 + 16 * pass + row, N - 1) * ldx + 8 * (pc ^ (row & 7));
+        const float* px = xi + (size_t)min(r0 + ROWS * pass + row, N - 1) * ldx + 8 * (pc ^ (row & 7));
         r[it][0] = *(const f32x4*)px;
         r[it][1] = *(const f32x4*)(px + 4);
       }
     }
-    if ((rr >> 4) == pass) {
+    if (ROWS == 32 || (rr >> 4) == pass) {
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           u32x2 o = {pack_bf16x2(acc[dt][4 * u] * scale, acc[dt][4 * u + 1] * scale),
                      pack_bf16x2(acc[dt][4 * u + 2] * scale, acc[dt][4 * u + 3] * scale)};
-          *(u32x2*)(img + (rr & 15) * 128 + (((4 * dt + u) ^ (rr & 7)) << 4) + h * 8) = o;
+          // element columns 32dt + 8u + 4h .. +3  -> 16-B chunk 4dt + u, half h ; chunk XOR (row & 7)
+          *(u32x2*)(img + (rr & (ROWS - 1)) * 128 + (((4 * dt + u) ^ (rr & 7)) << 4) + h * 8) = o;
         }
     }
+    // wave-private image: the same wave reads it back (the compiler orders LDS accesses of one wave)
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int row = (lane >> 3) + 8 * it, pc = lane & 7;                  // image row 0..15 = query row 16 pass + row
+    for (int it = 0; it < ITS; ++it) {
+      const int row = (lane >> 3) + 8 * it, pc = lane & 7;                  // image row = block row ROWS pass + row
       const u32x4 v = *(const u32x4*)(img + row * 128 + pc * 16);
-      const int grow = r0 + 16 * pass + row;
+      const int grow = r0 + ROWS * pass + row;
       if (grow < N) {
         const int col = 8 * (pc ^ (row & 7));
         *(u32x4*)(g + (size_t)grow * ld + col) = v;
@@ -216,6 +171,17 @@ __device__ __forceinline__ void store_rows_T_lds2k(__bf16* __restrict__ g, int l
           *(f32x4*)(po + 4) = o1;
         }
       }
+    }
+  } while (ROWS == 16 && ++pass < 2);
+  if constexpr (ROWS == 32) {
+    if (colacc) {
+      // column sums of the stored bf16 rows (the bias gradient of the QKV Linear): lane = column
+      const int chunk = lane >> 3, within = (lane & 7) * 2;
+      const int nrows = min(32, N - r0);
+      float sacc = 0.f;
+      for (int row = 0; row < nrows; ++row)
+        sacc += bf2f(*(const __bf16*)(img + row * 128 + ((chunk ^ (row & 7)) << 4) + within));
+      *colacc += sacc;
     }
   }
 }
@@ -245,6 +211,20 @@ struct AttnArgs {
   int nq;
 };
 
+// Per-head addressing, the same in every kernel: batch b, head hh, sequence length N, the row strides D3 (qkv, dqkv) and D (o, d_o, the residual
+// stream) and the head's Q rows (its K rows at + D, its V rows at + 2 D).  Arguments by value: the kernels read AttnArgs themselves.
+struct HeadAddr {
+  int b, hh, N, D3, D;
+  const __bf16* qbase;
+};
+template <typename Idx>   // the index type of the caller's own division: blockIdx.x is unsigned, the unrolled kernels divide their int head
+__device__ __forceinline__ HeadAddr head_addr(const __bf16* qkv, int N, int H, Idx head) {
+  const int b = head / H, hh = head % H, D3 = 3 * H * DH, D = H * DH;
+  return {b, hh, N, D3, D, qkv + (size_t)b * N * D3 + hh * DH};
+}
+// index of (b, hh, row) in the [B, H, N] statistics lse2 and delta
+__device__ __forceinline__ size_t stat_index(int b, int H, int hh, int N, int row) { return ((size_t)b * H + hh) * N + row; }
+
 // keep-scale of probability (b, head, query, key): 1/(1-p) or 0
 __device__ __forceinline__ float attn_keep(const AttnArgs& a, int bh, int query, int key) {
   const unsigned long long idx = ((unsigned long long)bh * a.N + query) * a.N + key;
@@ -256,12 +236,10 @@ template <bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / a.H, hh = blockIdx.x % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, blockIdx.x);
   const int nt = (N + 31) / 32, npad = nt * 32;
   char* ktile = smem;
   char* vtile = smem + npad * 128;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   stage_tile(qbase + D, D3, N, npad, ktile, wave, lane);
   stage_tile(qbase + 2 * D, D3, N, npad, vtile, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -274,16 +252,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) {
     bf16x8 qf[4];
     load_lane_frags(qbase, D3, N, q0, lane, qf);
     f32x16 oacc[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
+    zero(oacc);
     float m = NEG_BIG, l = 0.f;
     const int t_end = a.causal ? min(nt, qb + 1) : nt;  // key tiles above the diagonal contribute nothing
-    for (int T = 0; T < t_end; ++T) {
+    for (int T = 0; T < t_end; ++T) {     // TWIN of the key-tile body of attn_fwd_long_kernel (there: key0 for 32 * T): a change to one belongs in the other
       f32x16 s;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = 0.f;
+      zero(s);
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(ktile, T, kk, lane), qf[kk], s, 0, 0, 0);
       if (32 * T + 32 > N || (a.causal && T == qb)) {
@@ -321,7 +295,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) {
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;
     store_rows_T(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv);
-    if (lane < 32 && qrow < N) a.lse2[((size_t)b * a.H + hh) * N + qrow] = m + log2f(l);
+    if (lane < 32 && qrow < N) a.lse2[stat_index(b, a.H, hh, N, qrow)] = m + log2f(l);
   }
 }
 
@@ -334,13 +308,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int head = blockIdx.x;     // one workgroup per (batch, head); a persistent two-per-CU grid walking the heads is slower (backward 276 against 256 us)
-  const int b = head / a.H, hh = head % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, head);
   constexpr int nt = NKT, npad = NKT * 32;
   char* ktile = smem;
   char* vtile = smem + npad * 128;
   char* oimg = smem + 2 * npad * 128 + wave * 4096;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   stage_tile(qbase + D, D3, N, npad, ktile, wave, lane);
   stage_tile(qbase + 2 * D, D3, N, npad, vtile, wave, lane);
   const int wrot = (wave + head) & 3;   // rotate which wave gets the short list of query blocks
@@ -372,7 +344,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a
     for (int T = 0; T < NKT; ++T) {
       if (T < t_end) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s[T][r] = 0.f;
+        for (int r = 0; r < 16; ++r) s[T][r] = 0.f;      // (zeroing loops local in this kernel: with zero() the NKT = 1 dropout form changes its waits)
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) s[T] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(ktile, T, kk, lane), qf[kk], s[T], 0, 0, 0);
         if (32 * T + 32 > N || (CAUSAL && T == qb)) {   // only boundary tiles need masking (wave-uniform)
@@ -415,11 +387,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_small_kernel(const AttnArgs a
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;
     if constexpr (RES)
-      store_rows_T_lds_resid(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg, a.resid_in + (size_t)b * N * D + hh * DH,
-                             a.resid_out + (size_t)b * N * D + hh * DH, D);
+      store_rows_T_img<32, true>(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg, nullptr, a.resid_in + (size_t)b * N * D + hh * DH,
+                                 a.resid_out + (size_t)b * N * D + hh * DH, D);
     else
-      store_rows_T_lds(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg);
-    if (lane < 32 && qrow < N) a.lse2[((size_t)b * a.H + hh) * N + qrow] = mc + log2f(l);
+      store_rows_T_img(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg);
+    if (lane < 32 && qrow < N) a.lse2[stat_index(b, a.H, hh, N, qrow)] = mc + log2f(l);
   }
 }
 
@@ -438,13 +410,11 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_small8_kernel(const AttnArgs 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int head = blockIdx.x;
-  const int b = head / a.H, hh = head % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, head);
   constexpr int nt = NKT, npad = NKT * 32;
   char* ktile = smem;
   char* vtile = smem + npad * 128;
   char* oimg = smem + 2 * npad * 128 + wave * 2048;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   stage_tile(qbase + D, D3, N, npad, ktile, wave, lane, 8);
   stage_tile(qbase + 2 * D, D3, N, npad, vtile, wave, lane, 8);
   const int qb = (wave + head) & 7;            // rotate which waves sit out when the head has fewer than 8 query blocks
@@ -464,15 +434,11 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_small8_kernel(const AttnArgs 
   // does not fit the 128 registers that 16 waves per CU leave a wave
   float m = NEG_BIG, l = 0.f;
   f32x16 oacc[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
+  zero(oacc);
 #pragma unroll 1
   for (int T = 0; T < NKT; ++T) {
     f32x16 st;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) st[r] = 0.f;
+    zero(st);
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(ktile, T, kk, lane), qf[kk], st, 0, 0, 0);
     if (32 * T + 32 > N) {
@@ -512,16 +478,16 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_small8_kernel(const AttnArgs 
   const float mc = m * c;
   const float inv = 1.0f / l;
   if constexpr (KEEP) {
-    store_rows_T_lds2k(a.o + (size_t)b * a.nq * D + hh * DH, D, a.nq, q0, lane, oacc, inv, oimg);
-    if (lane < 32 && qrow < a.nq) a.lse2[((size_t)b * a.H + hh) * N + qrow] = mc + log2f(l);
+    store_rows_T_img<16>(a.o + (size_t)b * a.nq * D + hh * DH, D, a.nq, q0, lane, oacc, inv, oimg);
+    if (lane < 32 && qrow < a.nq) a.lse2[stat_index(b, a.H, hh, N, qrow)] = mc + log2f(l);
     return;
   }
   if constexpr (RES)
-    store_rows_T_lds2k<true>(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg, a.resid_in + (size_t)b * N * D + hh * DH,
-                             a.resid_out + (size_t)b * N * D + hh * DH, D);
+    store_rows_T_img<16, true>(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg, nullptr, a.resid_in + (size_t)b * N * D + hh * DH,
+                               a.resid_out + (size_t)b * N * D + hh * DH, D);
   else
-    store_rows_T_lds2k(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg);
-  if (lane < 32 && qrow < N) a.lse2[((size_t)b * a.H + hh) * N + qrow] = mc + log2f(l);
+    store_rows_T_img<16>(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv, oimg);
+  if (lane < 32 && qrow < N) a.lse2[stat_index(b, a.H, hh, N, qrow)] = mc + log2f(l);
 }
 
 // ------------------------------------------------------------------------------------------ backward, dQ
@@ -529,13 +495,11 @@ template <bool DROP, bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / a.H, hh = blockIdx.x % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, blockIdx.x);
   const int nt = (N + 31) / 32, npad = nt * 32;
   char* ktile = smem;
   char* vtile = smem + npad * 128;
   char* oimg = smem + 2 * npad * 128 + wave * 4096;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   stage_tile(qbase + D, D3, N, npad, ktile, wave, lane);
   stage_tile(qbase + 2 * D, D3, N, npad, vtile, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -548,7 +512,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
   for (int qb = (wave + blockIdx.x) & 3; qb < nt; qb += 4) {
     const int q0 = qb * 32;
     const int qrow = q0 + (lane & 31);
-    bf16x8 qf[4], dof[4], of[4];
+    bf16x8 qf[4], dof[4], of[4];           // TWIN (to "write delta") of the set-up in attn_bwd_dq_long_kernel and, with the LIM changes, attn_bwd_dq_pipe_kernel
     load_lane_frags(qbase, D3, N, q0, lane, qf);
     load_lane_frags(dobase, D, N, q0, lane, dof);
     load_lane_frags(obase, D, N, q0, lane, of);
@@ -558,20 +522,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) delta += (float)dof[kk][j] * (float)of[kk][j];
     delta += __shfl_xor(delta, 32, 64);
-    const size_t stat = ((size_t)b * a.H + hh) * N + min(qrow, N - 1);
+    const size_t stat = stat_index(b, a.H, hh, N, min(qrow, N - 1));
     const float lse2 = a.lse2[stat];
     if (lane < 32 && qrow < N) a.delta[stat] = delta;
 
     f32x16 dq[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+    zero(dq);
     const int t_end = CAUSAL ? min(nt, qb + 1) : nt;
-    for (int T = 0; T < t_end; ++T) {
+    for (int T = 0; T < t_end; ++T) {     // TWIN of the key-tile body of attn_bwd_dq_long_kernel (there: key0 for 32 * T, a.causal for CAUSAL)
       f32x16 s, dp;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+      zero(s);
+      zero(dp);
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(ktile, T, kk, lane), qf[kk], s, 0, 0, 0);
@@ -599,7 +560,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs a) {
           dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(ktile, T, sidx, dt, lane), dsf, dq[dt], 0, 0, 0);
       }
     }
-    store_rows_T_lds(a.dqkv + (size_t)b * N * D3 + hh * DH, D3, N, q0, lane, dq, a.scale, oimg, a.dbias ? &csum_q : nullptr);
+    store_rows_T_img(a.dqkv + (size_t)b * N * D3 + hh * DH, D3, N, q0, lane, dq, a.scale, oimg, a.dbias ? &csum_q : nullptr);
   }
   if (a.dbias) atomicAdd(a.dbias + hh * DH + lane, csum_q);   // 256 contiguous bytes per wave
 }
@@ -622,13 +583,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int head = blockIdx.x;     // one workgroup per (batch, head); a persistent two-per-CU grid walking the heads is slower (backward 276 against 256 us)
-  const int b = head / a.H, hh = head % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, head);
   constexpr int nt = NT, npad = NT * 32;
   char* ktile = smem;
   char* vtile = smem + npad * 128;
   char* oimg = smem + 2 * npad * 128 + wave * 4096;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   stage_tile(qbase + D, D3, N, npad, ktile, wave, lane);
   stage_tile(qbase + 2 * D, D3, N, npad, vtile, wave, lane);
   int nq = N;                      // rows of o / d_o per sequence
@@ -677,7 +636,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
         for (int j = 0; j < 8; ++j) delta += (float)dof[kk][j] * (float)of[kk][j];
     }
     delta += __shfl_xor(delta, 32, 64);
-    const size_t stat = ((size_t)b * a.H + hh) * N + min(qrow, nq - 1);
+    const size_t stat = stat_index(b, a.H, hh, N, min(qrow, nq - 1));
     float lse2 = a.lse2[stat];
     if constexpr (LIM) lse2 = qrow < nq ? lse2 : 1.0e30f;      // exp2(s - 1e30) = 0 exactly
     if (lane < 32 && qrow < nq) a.delta[stat] = delta;
@@ -691,7 +650,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
     f32x16 sb[2], dpb[2];           // S^T and dP^T of the tile on the VALU and of the next one in the matrix pipe
     auto products = [&](int buf) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { sb[buf][r] = 0.f; dpb[buf][r] = 0.f; }
+      for (int r = 0; r < 16; ++r) { sb[buf][r] = 0.f; dpb[buf][r] = 0.f; }     // (zeroing loops local in this kernel: with zero() hipcc packs its dS arithmetic differently)
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         sb[buf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[buf][kk], qf[kk], sb[buf], 0, 0, 0);
@@ -736,7 +695,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(const AttnArgs
         for (int dt = 0; dt < 2; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktr[sidx][dt], dsf, dq[dt], 0, 0, 0);
       }
     }
-    store_rows_T_lds(a.dqkv + (size_t)b * N * D3 + hh * DH, D3, N, q0, lane, dq, a.scale, oimg, a.dbias ? &csum_q : nullptr);
+    store_rows_T_img(a.dqkv + (size_t)b * N * D3 + hh * DH, D3, N, q0, lane, dq, a.scale, oimg, a.dbias ? &csum_q : nullptr);
   }
   if (a.dbias) atomicAdd(a.dbias + hh * DH + lane, csum_q);   // 256 contiguous bytes per wave
 }
@@ -746,20 +705,18 @@ template <bool DROP, bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / a.H, hh = blockIdx.x % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, blockIdx.x);
   const int nt = (N + 31) / 32, npad = nt * 32;
   char* qtile = smem;
   char* dotile = smem + npad * 128;
   float* lse_s = (float*)(smem + 2 * npad * 128);
   float* delta_s = lse_s + npad;
   char* oimg = smem + 2 * npad * 128 + 2 * npad * 4 + wave * 4096;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   const __bf16* dobase = a.d_o + (size_t)b * N * D + hh * DH;
   stage_tile(qbase, D3, N, npad, qtile, wave, lane);
   stage_tile(dobase, D, N, npad, dotile, wave, lane);
   for (int i = threadIdx.x; i < npad; i += 256) {
-    const size_t stat = ((size_t)b * a.H + hh) * N + min(i, N - 1);
+    const size_t stat = stat_index(b, a.H, hh, N, min(i, N - 1));
     lse_s[i] = a.lse2[stat];
     delta_s[i] = a.delta[stat];
   }
@@ -775,15 +732,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
     load_lane_frags(qbase + D, D3, N, k0, lane, kf);
     load_lane_frags(qbase + 2 * D, D3, N, k0, lane, vf);
     f32x16 dk[2], dv[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
+    zero(dk);
+    zero(dv);
     const int t_beg = CAUSAL ? kb : 0;  // queries before the key block never attend to it
-    for (int T = t_beg; T < nt; ++T) {
+    for (int T = t_beg; T < nt; ++T) {    // TWIN of the query-tile body of attn_bwd_dkv_long_kernel (there: rows r0 + ... of the staged chunk, a.causal for CAUSAL)
       f32x16 s, dp;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+      zero(s);
+      zero(dp);
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(qtile, T, kk, lane), kf[kk], s, 0, 0, 0);
@@ -824,8 +779,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs a) 
       }
     }
     __bf16* dbase = a.dqkv + (size_t)b * N * D3 + hh * DH;
-    store_rows_T_lds(dbase + D, D3, N, k0, lane, dk, a.scale, oimg, a.dbias ? &csum_k : nullptr);
-    store_rows_T_lds(dbase + 2 * D, D3, N, k0, lane, dv, 1.0f, oimg, a.dbias ? &csum_v : nullptr);
+    store_rows_T_img(dbase + D, D3, N, k0, lane, dk, a.scale, oimg, a.dbias ? &csum_k : nullptr);
+    store_rows_T_img(dbase + 2 * D, D3, N, k0, lane, dv, 1.0f, oimg, a.dbias ? &csum_v : nullptr);
   }
   if (a.dbias) {
     atomicAdd(a.dbias + D + hh * DH + lane, csum_k);
@@ -845,6 +800,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArg
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int head = blockIdx.x;     // one workgroup per (batch, head); a persistent two-per-CU grid walking the heads is slower (backward 276 against 256 us)
+  // (head_addr() spelled out in this kernel: through the helper NT = 7 spills 80 instead of 84 bytes and reorders its waits - not the parent's code)
   const int b = head / a.H, hh = head % a.H;
   const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
   constexpr int nt = NT, npad = NQT * 32;           // npad: staged QUERY rows
@@ -875,15 +831,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArg
     load_lane_frags(qbase + D, D3, N, k0, lane, kf);
     load_lane_frags(qbase + 2 * D, D3, N, k0, lane, vf);
     f32x16 dk[2], dv[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
+    zero(dk);
+    zero(dv);
     bf16x8 qr[4], dor[4];           // row fragments of Q and dO of the tile whose products are issued next
     f32x16 sb, dpb;                 // (one set: 256 registers do not hold a second one next to dK, dV and the fragments)
     auto products = [&]() {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { sb[r] = 0.f; dpb[r] = 0.f; }
+      zero(sb);
+      zero(dpb);
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         sb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qr[kk], kf[kk], sb, 0, 0, 0);
@@ -939,8 +893,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_pipe_kernel(const AttnArg
       }
     }
     __bf16* dbase = a.dqkv + (size_t)b * N * D3 + hh * DH;
-    store_rows_T_lds(dbase + D, D3, N, k0, lane, dk, a.scale, oimg, a.dbias ? &csum_k : nullptr);
-    store_rows_T_lds(dbase + 2 * D, D3, N, k0, lane, dv, 1.0f, oimg, a.dbias ? &csum_v : nullptr);
+    store_rows_T_img(dbase + D, D3, N, k0, lane, dk, a.scale, oimg, a.dbias ? &csum_k : nullptr);
+    store_rows_T_img(dbase + 2 * D, D3, N, k0, lane, dv, 1.0f, oimg, a.dbias ? &csum_v : nullptr);
   }
   if (a.dbias) {
     atomicAdd(a.dbias + D + hh * DH + lane, csum_k);
@@ -960,12 +914,10 @@ template <bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / a.H, hh = blockIdx.x % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, blockIdx.x);
   const int nt = (N + 31) / 32;
   char* ktile = smem;
   char* vtile = smem + CH * 128;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   const int qb = blockIdx.y * 4 + wave;
   const bool active = qb < nt;                       // idle waves still stage and synchronise
   const int q0 = qb * 32, qrow = q0 + (lane & 31);
@@ -973,10 +925,7 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
   bf16x8 qf[4];
   if (active) load_lane_frags(qbase, D3, N, q0, lane, qf);
   f32x16 oacc[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
+  zero(oacc);
   float m = NEG_BIG, l = 0.f;
   const int t_end = a.causal ? min(nt, qb + 1) : nt;  // global key-tile bound
   for (int k0 = 0; k0 < N; k0 += CH) {
@@ -988,10 +937,9 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
     __syncthreads();
     if (!active) continue;
     for (int T = 0; T < ntc && k0 / 32 + T < t_end; ++T) {
-      const int key0 = k0 + 32 * T;
+      const int key0 = k0 + 32 * T;        // TWIN of the key-tile body of attn_fwd_kernel
       f32x16 s;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = 0.f;
+      zero(s);
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(ktile, T, kk, lane), qf[kk], s, 0, 0, 0);
       if (key0 + 32 > N || (a.causal && key0 / 32 == qb)) {
@@ -1031,20 +979,18 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
   l += __shfl_xor(l, 32, 64);
   const float inv = 1.0f / l;
   store_rows_T(a.o + (size_t)b * N * D + hh * DH, D, N, q0, lane, oacc, inv);
-  if (lane < 32 && qrow < N) a.lse2[((size_t)b * a.H + hh) * N + qrow] = m + log2f(l);
+  if (lane < 32 && qrow < N) a.lse2[stat_index(b, a.H, hh, N, qrow)] = m + log2f(l);
 }
 
 template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dq_long_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / a.H, hh = blockIdx.x % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, blockIdx.x);
   const int nt = (N + 31) / 32;
   char* ktile = smem;
   char* vtile = smem + CH * 128;
   char* oimg = smem + 2 * CH * 128 + wave * 4096;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   const __bf16* obase = a.o + (size_t)b * N * D + hh * DH;
   const __bf16* dobase = a.d_o + (size_t)b * N * D + hh * DH;
   const int qb = blockIdx.y * 4 + wave;
@@ -1063,15 +1009,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_long_kernel(const AttnArgs a)
 #pragma unroll
       for (int j = 0; j < 8; ++j) delta += (float)dof[kk][j] * (float)of[kk][j];
     delta += __shfl_xor(delta, 32, 64);
-    const size_t stat = ((size_t)b * a.H + hh) * N + min(qrow, N - 1);
+    const size_t stat = stat_index(b, a.H, hh, N, min(qrow, N - 1));
     lse2 = a.lse2[stat];
     if (lane < 32 && qrow < N) a.delta[stat] = delta;
   }
   f32x16 dq[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+  zero(dq);
   const int t_end = a.causal ? min(nt, qb + 1) : nt;
   for (int k0 = 0; k0 < N; k0 += CH) {
     const int rows = min(CH, N - k0), ntc = (rows + 31) / 32;
@@ -1082,10 +1025,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_long_kernel(const AttnArgs a)
     __syncthreads();
     if (!active) continue;
     for (int T = 0; T < ntc && k0 / 32 + T < t_end; ++T) {
-      const int key0 = k0 + 32 * T;
+      const int key0 = k0 + 32 * T;        // TWIN of the key-tile body of attn_bwd_dq_kernel
       f32x16 s, dp;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+      zero(s);
+      zero(dp);
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(ktile, T, kk, lane), qf[kk], s, 0, 0, 0);
@@ -1115,7 +1058,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_long_kernel(const AttnArgs a)
     }
   }
   float csum_q = 0.f;
-  if (active) store_rows_T_lds(a.dqkv + (size_t)b * N * D3 + hh * DH, D3, N, q0, lane, dq, a.scale, oimg, a.dbias ? &csum_q : nullptr);
+  if (active) store_rows_T_img(a.dqkv + (size_t)b * N * D3 + hh * DH, D3, N, q0, lane, dq, a.scale, oimg, a.dbias ? &csum_q : nullptr);
   if (a.dbias && active) atomicAdd(a.dbias + hh * DH + lane, csum_q);
 }
 
@@ -1123,15 +1066,13 @@ template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_long_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / a.H, hh = blockIdx.x % a.H;
-  const int N = a.N, D3 = 3 * a.H * DH, D = a.H * DH;
+  const auto [b, hh, N, D3, D, qbase] = head_addr(a.qkv, a.N, a.H, blockIdx.x);
   const int nt = (N + 31) / 32;
   char* qtile = smem;
   char* dotile = smem + CH * 128;
   float* lse_s = (float*)(smem + 2 * CH * 128);
   float* delta_s = lse_s + CH;
   char* oimg = smem + 2 * CH * 128 + 2 * CH * 4 + wave * 4096;
-  const __bf16* qbase = a.qkv + (size_t)b * N * D3 + hh * DH;
   const __bf16* dobase = a.d_o + (size_t)b * N * D + hh * DH;
   const int kb = blockIdx.y * 4 + wave;
   const bool active = kb < nt;
@@ -1154,7 +1095,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_long_kernel(const AttnArgs a
     stage_tile(qbase + (size_t)r0 * D3, D3, rows, ntc * 32, qtile, wave, lane);
     stage_tile(dobase + (size_t)r0 * D, D, rows, ntc * 32, dotile, wave, lane);
     for (int i = threadIdx.x; i < ntc * 32; i += 256) {
-      const size_t stat = ((size_t)b * a.H + hh) * N + min(r0 + i, N - 1);
+      const size_t stat = stat_index(b, a.H, hh, N, min(r0 + i, N - 1));
       lse_s[i] = a.lse2[stat];
       delta_s[i] = a.delta[stat];
     }
@@ -1163,7 +1104,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_long_kernel(const AttnArgs a
     if (!active) continue;
     for (int T = 0; T < ntc; ++T) {
       const int Tg = r0 / 32 + T;
-      if (Tg < t_beg) continue;
+      if (Tg < t_beg) continue;            // TWIN of the query-tile body of attn_bwd_dkv_kernel; zeroing loops local (zero() costs this kernel 16 v_mov fewer: not the parent's code)
       f32x16 s, dp;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
@@ -1210,49 +1151,113 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_long_kernel(const AttnArgs a
   if (!active) return;
   float csum_k = 0.f, csum_v = 0.f;
   __bf16* dbase = a.dqkv + (size_t)b * N * D3 + hh * DH;
-  store_rows_T_lds(dbase + D, D3, N, k0, lane, dk, a.scale, oimg, a.dbias ? &csum_k : nullptr);
-  store_rows_T_lds(dbase + 2 * D, D3, N, k0, lane, dv, 1.0f, oimg, a.dbias ? &csum_v : nullptr);
+  store_rows_T_img(dbase + D, D3, N, k0, lane, dk, a.scale, oimg, a.dbias ? &csum_k : nullptr);
+  store_rows_T_img(dbase + 2 * D, D3, N, k0, lane, dv, 1.0f, oimg, a.dbias ? &csum_v : nullptr);
   if (a.dbias) {
     atomicAdd(a.dbias + D + hh * DH + lane, csum_k);
     atomicAdd(a.dbias + 2 * D + hh * DH + lane, csum_v);
   }
 }
 
-int check(const AttnArgs& a) {
-  if (a.B <= 0 || a.N <= 0 || a.H <= 0 || a.N > MAX_N_LONG) return VITAMD_ERR_SHAPE;
-  return VITAMD_OK;
-}
-
-}  // namespace
-
-static bool attn_dropout(AttnArgs& a, float p, unsigned long long seed) {
-  if (!(p >= 0.f) || p >= 1.f) return false;
+// ------------------------------------------------------------------------------------------ host side
+// Fills AttnArgs and validates what every entry point validates, in this order: head_dim and the shape -> VITAMD_ERR_SHAPE, then a null
+// pointer or a dropout probability outside [0, 1) -> VITAMD_ERR_ARG.  bwd: d_o, dqkv and delta are required as well.
+int make_args(AttnArgs& out, bool bwd, const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta, float* dbias, int B,
+              int N, int H, int head_dim, int causal, float p, unsigned long long seed, int nq = 0) {
+  if (head_dim != DH || B <= 0 || N <= 0 || H <= 0 || N > MAX_N_LONG) return VITAMD_ERR_SHAPE;
+  if (!qkv || !o || !lse2 || (bwd && (!d_o || !dqkv || !delta))) return VITAMD_ERR_ARG;
+  if (!(p >= 0.f) || p >= 1.f) return VITAMD_ERR_ARG;
+  AttnArgs a{};
+  a.qkv = (const __bf16*)qkv;
+  a.o = (__bf16*)o;
+  a.lse2 = (float*)lse2;
+  a.d_o = (const __bf16*)d_o;
+  a.dqkv = (__bf16*)dqkv;
+  a.delta = delta;
+  a.dbias = dbias;
+  a.B = B;
+  a.N = N;
+  a.H = H;
+  a.causal = causal;
+  a.scale = 0.125f;                                  // 1 / sqrt(64)
+  a.scale_log2e = 0.125f * 1.4426950408889634f;
   a.drop_thresh = p > 0.f ? (unsigned)((double)p * 4294967296.0) : 0u;
   if (p > 0.f && a.drop_thresh == 0u) a.drop_thresh = 1u;
   a.drop_scale = 1.0f / (1.0f - p);
   a.seed_lo = (unsigned)seed;
   a.seed_hi = (unsigned)(seed >> 32);
-  return true;
-}
-
-template <int K, bool DROP, bool CAUSAL>
-static int launch_fwd_small_c(const AttnArgs& a, int lds, hipStream_t stream) {
-  if (a.resid_in) {
-    if (int e = set_lds((attn_fwd_small_kernel<K, DROP, CAUSAL, true>), lds)) return e;
-    hipLaunchKernelGGL((attn_fwd_small_kernel<K, DROP, CAUSAL, true>), dim3(a.B * a.H), dim3(256), lds, stream, a);
-    return VITAMD_OK;
-  }
-  if (int e = set_lds((attn_fwd_small_kernel<K, DROP, CAUSAL>), lds)) return e;
-  hipLaunchKernelGGL((attn_fwd_small_kernel<K, DROP, CAUSAL>), dim3(a.B * a.H), dim3(256), lds, stream, a);
+  a.nq = nq;
+  out = a;
   return VITAMD_OK;
 }
-template <int K, bool DROP>
-static int launch_fwd_small(const AttnArgs& a, int lds, hipStream_t stream) {      // causal / not: compile-time (fewer scalar registers: no runtime mask branches per tile)
-  return a.causal ? launch_fwd_small_c<K, DROP, true>(a, lds, stream) : launch_fwd_small_c<K, DROP, false>(a, lds, stream);
+
+// dynamic-LDS opt-in + launch of one kernel instantiation
+template <auto Kernel>
+int launch(dim3 grid, dim3 block, int lds, hipStream_t stream, const AttnArgs& a) {
+  if (int e = set_lds(Kernel, lds)) return e;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, a);
+  return VITAMD_OK;
+}
+int launched(int e) { return e ? e : hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH; }
+
+// A runtime value as a template argument: f is a generic lambda that gets a std::integral_constant and reads decltype(arg)::value.
+// with_tiles: v in [LO, HI], VITAMD_ERR_SHAPE outside (only the listed counts are instantiated).
+template <int LO, int HI, typename F>
+int with_tiles(int v, F f) {
+  if constexpr (LO > HI) return VITAMD_ERR_SHAPE;
+  else return v == LO ? f(std::integral_constant<int, LO>{}) : with_tiles<LO + 1, HI>(v, f);
+}
+template <typename F>
+int with_flag(bool v, F f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+#define CONST_OF(arg) decltype(arg)::value
+
+// the two pipelined backward kernels (dQ also writes delta); NQT <= NT query tiles; LIM: the kept-query form
+template <int NT, int NQT, bool LIM>
+int launch_bwd_pipe(const AttnArgs& a, hipStream_t stream) {
+  if constexpr (NQT > NT) return VITAMD_ERR_SHAPE;
+  else {
+    const dim3 grid(a.B * a.H), block(256);
+    if (int e = launch<attn_bwd_dq_pipe_kernel<NT, NQT, LIM>>(grid, block, 2 * NT * 32 * 128 + 4 * 4096, stream, a)) return e;
+    return launch<attn_bwd_dkv_pipe_kernel<NT, NQT, LIM>>(grid, block, 2 * NQT * 32 * 128 + 2 * NQT * 32 * 4 + 4 * 4096, stream, a);
+  }
 }
 
-static int attention_fwd_impl(const void* qkv, void* o, float* lse2, const float* resid_in, float* resid_out, int B, int N, int H,
-                              int head_dim, int causal, float dropout_p, unsigned long long seed, void* stream_);
+int attention_fwd_impl(const void* qkv, void* o, float* lse2, const float* resid_in, float* resid_out, int B, int N, int H, int head_dim, int causal,
+                       float dropout_p, unsigned long long seed, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AttnArgs a;
+  if (int e = make_args(a, false, qkv, o, lse2, nullptr, nullptr, nullptr, nullptr, B, N, H, head_dim, causal, dropout_p, seed)) return e;
+  a.resid_in = resid_in;
+  a.resid_out = resid_out;
+  const bool drop = a.drop_thresh != 0u, res = resid_in != nullptr;
+  const int nkt = (N + 31) / 32, npad = nkt * 32;
+  const dim3 heads(B * H);
+  int e;
+  if (N > MAX_N)
+    e = with_flag(drop, [&](auto DR) { return launch<attn_fwd_long_kernel<CONST_OF(DR)>>(dim3(B * H, (nkt + 3) / 4), dim3(256), 2 * CH * 128, stream, a); });
+  else if (nkt >= 5 && nkt <= 8 && !drop && !causal)      // eight waves, one query block each
+    e = with_tiles<5, 8>(nkt, [&](auto K) {
+      return with_flag(res, [&](auto RES) {
+        return launch<attn_fwd_small8_kernel<CONST_OF(K), CONST_OF(RES)>>(heads, dim3(512), 2 * npad * 128 + 8 * 2048, stream, a);
+      });
+    });
+  else if (nkt <= 8)                                      // causal / not: compile-time (fewer scalar registers: no runtime mask branches per tile)
+    e = with_tiles<1, 8>(nkt, [&](auto K) {
+      return with_flag(drop, [&](auto DR) {
+        return with_flag(causal != 0, [&](auto CAUSAL) {
+          return with_flag(res, [&](auto RES) {
+            return launch<attn_fwd_small_kernel<CONST_OF(K), CONST_OF(DR), CONST_OF(CAUSAL), CONST_OF(RES)>>(heads, dim3(256), 2 * npad * 128 + 4 * 4096,
+                                                                                                         stream, a);
+          });
+        });
+      });
+    });
+  else
+    e = with_flag(drop, [&](auto DR) { return launch<attn_fwd_kernel<CONST_OF(DR)>>(heads, dim3(256), 2 * npad * 128, stream, a); });
+  return launched(e);
+}
+
+}  // namespace
 
 extern "C" int vitamd_attention_fwd(const void* qkv, void* o, float* lse2, int B, int N, int H, int head_dim, int causal,
                                     float dropout_p, unsigned long long seed, void* stream_) {
@@ -1267,109 +1272,33 @@ extern "C" int vitamd_attention_fwd_resid(const void* qkv, void* o, float* lse2,
   return attention_fwd_impl(qkv, o, lse2, resid_in, resid_out, B, N, H, head_dim, causal, dropout_p, seed, stream_);
 }
 
-static int attention_fwd_impl(const void* qkv, void* o, float* lse2, const float* resid_in, float* resid_out, int B, int N, int H,
-                              int head_dim, int causal, float dropout_p, unsigned long long seed, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (head_dim != DH) return VITAMD_ERR_SHAPE;
-  AttnArgs a{(const __bf16*)qkv, (__bf16*)o, lse2, nullptr, nullptr, nullptr, nullptr, B, N, H, causal, 0.125f * 1.4426950408889634f, 0.125f,
-             0u, 1.0f, 0u, 0u, resid_in, resid_out};
-  if (int e = check(a)) return e;
-  if (!qkv || !o || !lse2 || !attn_dropout(a, dropout_p, seed)) return VITAMD_ERR_ARG;
-  const bool drop = a.drop_thresh != 0u;
-  const int nkt = (N + 31) / 32, npad = nkt * 32;
-  if (N > MAX_N) {
-    const int lds = 2 * CH * 128;
-    const dim3 grid(B * H, (nkt + 3) / 4);
-    if (drop) {
-      if (int e = set_lds(attn_fwd_long_kernel<true>, lds)) return e;
-      hipLaunchKernelGGL(attn_fwd_long_kernel<true>, grid, dim3(256), lds, stream, a);
-    } else {
-      if (int e = set_lds(attn_fwd_long_kernel<false>, lds)) return e;
-      hipLaunchKernelGGL(attn_fwd_long_kernel<false>, grid, dim3(256), lds, stream, a);
-    }
-    return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
-  }
-  if (nkt >= 5 && nkt <= 8 && !drop && !causal) {      // eight waves, one query block each
-    const int lds = 2 * npad * 128 + 8 * 2048;
-    int e = VITAMD_OK;
-#define FWD_SMALL8(K) case K: \
-      if (a.resid_in) { e = set_lds(attn_fwd_small8_kernel<K, true>, lds); if (!e) hipLaunchKernelGGL((attn_fwd_small8_kernel<K, true>), dim3(B * H), dim3(512), lds, stream, a); } \
-      else { e = set_lds(attn_fwd_small8_kernel<K, false>, lds); if (!e) hipLaunchKernelGGL((attn_fwd_small8_kernel<K, false>), dim3(B * H), dim3(512), lds, stream, a); } break;
-    switch (nkt) { FWD_SMALL8(5) FWD_SMALL8(6) FWD_SMALL8(7) FWD_SMALL8(8) }
-#undef FWD_SMALL8
-    if (e) return e;
-  } else if (nkt <= 8) {
-    const int lds = 2 * npad * 128 + 4 * 4096;
-    int e = VITAMD_OK;
-#define FWD_SMALL(K) case K: e = drop ? launch_fwd_small<K, true>(a, lds, stream) : launch_fwd_small<K, false>(a, lds, stream); break;
-    switch (nkt) { FWD_SMALL(1) FWD_SMALL(2) FWD_SMALL(3) FWD_SMALL(4) FWD_SMALL(5) FWD_SMALL(6) FWD_SMALL(7) FWD_SMALL(8) }
-#undef FWD_SMALL
-    if (e) return e;
-  } else {
-    const int lds = 2 * npad * 128;
-    if (drop) {
-      if (int e = set_lds(attn_fwd_kernel<true>, lds)) return e;
-      hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(B * H), dim3(256), lds, stream, a);
-    } else {
-      if (int e = set_lds(attn_fwd_kernel<false>, lds)) return e;
-      hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(B * H), dim3(256), lds, stream, a);
-    }
-  }
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
-}
-
 extern "C" int vitamd_attention_bwd(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta,
                                     float* dbias, int B, int N, int H, int head_dim, int causal, float dropout_p,
                                     unsigned long long seed, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (head_dim != DH) return VITAMD_ERR_SHAPE;
-  AttnArgs a{(const __bf16*)qkv, (__bf16*)o, (float*)lse2, (const __bf16*)d_o, (__bf16*)dqkv, delta, dbias, B, N, H, causal,
-             0.125f * 1.4426950408889634f, 0.125f, 0u, 1.0f, 0u, 0u, nullptr, nullptr};
-  if (int e = check(a)) return e;
-  if (!qkv || !o || !lse2 || !d_o || !dqkv || !delta || !attn_dropout(a, dropout_p, seed)) return VITAMD_ERR_ARG;
-  if (N > MAX_N) {
-    const int ldsq = 2 * CH * 128 + 4 * 4096, ldsk = 2 * CH * 128 + 2 * CH * 4 + 4 * 4096;
-    const dim3 grid(B * H, ((N + 31) / 32 + 3) / 4);
-    if (a.drop_thresh) {
-      if (int e = set_lds(attn_bwd_dq_long_kernel<true>, ldsq)) return e;
-      if (int e = set_lds(attn_bwd_dkv_long_kernel<true>, ldsk)) return e;
-      hipLaunchKernelGGL(attn_bwd_dq_long_kernel<true>, grid, dim3(256), ldsq, stream, a);   // also writes delta
-      hipLaunchKernelGGL(attn_bwd_dkv_long_kernel<true>, grid, dim3(256), ldsk, stream, a);
-    } else {
-      if (int e = set_lds(attn_bwd_dq_long_kernel<false>, ldsq)) return e;
-      if (int e = set_lds(attn_bwd_dkv_long_kernel<false>, ldsk)) return e;
-      hipLaunchKernelGGL(attn_bwd_dq_long_kernel<false>, grid, dim3(256), ldsq, stream, a);
-      hipLaunchKernelGGL(attn_bwd_dkv_long_kernel<false>, grid, dim3(256), ldsk, stream, a);
-    }
-    return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
-  }
-  const int npad = (N + 31) / 32 * 32;
-  const int lds1 = 2 * npad * 128 + 4 * 4096, lds2 = 2 * npad * 128 + 2 * npad * 4 + 4 * 4096;
-  const dim3 grid(B * H), block(256);
-  const int nkt = npad / 32;
-  if (!a.drop_thresh && !a.causal && nkt >= 2 && nkt <= 7) {      // the ViT shapes: pipelined forms.  (Round 4, DESIGN.md section 8: with 8 / 9 key tiles - 256 tokens: ViT-VQGAN, 288: TiTok - the fully unrolled kernels LOSE to the plain loops, 604 against 402 us at B 256, N 256, H 12 and 597 against 440 at N 288; 2-7 tiles: equal to 13 % faster)
-    int e = VITAMD_OK;
-#define DQ_PIPE(K) case K: e = set_lds(attn_bwd_dq_pipe_kernel<K>, lds1); if (!e) hipLaunchKernelGGL(attn_bwd_dq_pipe_kernel<K>, grid, block, lds1, stream, a); break;
-    switch (nkt) { DQ_PIPE(2) DQ_PIPE(3) DQ_PIPE(4) DQ_PIPE(5) DQ_PIPE(6) DQ_PIPE(7) }
-#undef DQ_PIPE
-    if (e) return e;
-#define DKV_PIPE(K) case K: e = set_lds(attn_bwd_dkv_pipe_kernel<K>, lds2); if (!e) hipLaunchKernelGGL(attn_bwd_dkv_pipe_kernel<K>, grid, block, lds2, stream, a); break;
-    switch (nkt) { DKV_PIPE(2) DKV_PIPE(3) DKV_PIPE(4) DKV_PIPE(5) DKV_PIPE(6) DKV_PIPE(7) }
-#undef DKV_PIPE
-    if (e) return e;
-    return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
-  }
-#define BWD_SMALL(DROP, CAUSAL)                                                                      \
-  do {                                                                                               \
-    if (int e = set_lds((attn_bwd_dq_kernel<DROP, CAUSAL>), lds1)) return e;                         \
-    if (int e = set_lds((attn_bwd_dkv_kernel<DROP, CAUSAL>), lds2)) return e;                        \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DROP, CAUSAL>), grid, block, lds1, stream, a); /* also writes delta */ \
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DROP, CAUSAL>), grid, block, lds2, stream, a);          \
-  } while (0)
-  if (a.drop_thresh) { if (a.causal) BWD_SMALL(true, true); else BWD_SMALL(true, false); }
-  else { if (a.causal) BWD_SMALL(false, true); else BWD_SMALL(false, false); }
-#undef BWD_SMALL
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  AttnArgs a;
+  if (int e = make_args(a, true, qkv, o, lse2, d_o, dqkv, delta, dbias, B, N, H, head_dim, causal, dropout_p, seed)) return e;
+  const bool drop = a.drop_thresh != 0u;
+  const int nkt = (N + 31) / 32, npad = nkt * 32;
+  const dim3 block(256);
+  int e;
+  if (N > MAX_N)
+    e = with_flag(drop, [&](auto DR) {
+      const dim3 grid(B * H, (nkt + 3) / 4);
+      if (int el = launch<attn_bwd_dq_long_kernel<CONST_OF(DR)>>(grid, block, 2 * CH * 128 + 4 * 4096, stream, a)) return el;   // also writes delta
+      return launch<attn_bwd_dkv_long_kernel<CONST_OF(DR)>>(grid, block, 2 * CH * 128 + 2 * CH * 4 + 4 * 4096, stream, a);
+    });
+  else if (!drop && !causal && nkt >= 2 && nkt <= 7)      // the ViT shapes: pipelined forms.  (Round 4, DESIGN.md section 8: with 8 / 9 key tiles - 256 tokens: ViT-VQGAN, 288: TiTok - the fully unrolled kernels LOSE to the plain loops, 604 against 402 us at B 256, N 256, H 12 and 597 against 440 at N 288; 2-7 tiles: equal to 13 % faster)
+    e = with_tiles<2, 7>(nkt, [&](auto K) { return launch_bwd_pipe<CONST_OF(K), CONST_OF(K), false>(a, stream); });
+  else
+    e = with_flag(drop, [&](auto DR) {
+      return with_flag(causal != 0, [&](auto CAUSAL) {
+        const dim3 grid(B * H);
+        if (int el = launch<attn_bwd_dq_kernel<CONST_OF(DR), CONST_OF(CAUSAL)>>(grid, block, 2 * npad * 128 + 4 * 4096, stream, a)) return el;   // also writes delta
+        return launch<attn_bwd_dkv_kernel<CONST_OF(DR), CONST_OF(CAUSAL)>>(grid, block, 2 * npad * 128 + 2 * npad * 4 + 4 * 4096, stream, a);
+      });
+    });
+  return launched(e);
 }
 
 // ------------------------------------------------------------------------------------------ kept-query forms
@@ -1386,66 +1315,22 @@ extern "C" int vitamd_attention_keep_forms(int N, int nq) {
 
 extern "C" int vitamd_attention_fwd_keep(const void* qkv, void* o, float* lse2, int B, int N, int H, int head_dim, int nq, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (head_dim != DH) return VITAMD_ERR_SHAPE;
-  AttnArgs a{(const __bf16*)qkv, (__bf16*)o, lse2, nullptr, nullptr, nullptr, nullptr, B, N, H, 0, 0.125f * 1.4426950408889634f, 0.125f,
-             0u, 1.0f, 0u, 0u, nullptr, nullptr, nq};
-  if (int e = check(a)) return e;
-  if (!qkv || !o || !lse2) return VITAMD_ERR_ARG;
+  AttnArgs a;
+  if (int e = make_args(a, false, qkv, o, lse2, nullptr, nullptr, nullptr, nullptr, B, N, H, head_dim, 0, 0.f, 0ull, nq)) return e;
   if (!(vitamd_attention_keep_forms(N, nq) & 1)) return VITAMD_ERR_SHAPE;
-  const int nkt = (N + 31) / 32, lds = 2 * nkt * 32 * 128 + 8 * 2048;
-  int e = VITAMD_OK;
-#define FWD_KEEP(K) case K: e = set_lds(attn_fwd_small8_kernel<K, false, true>, lds); \
-    if (!e) hipLaunchKernelGGL((attn_fwd_small8_kernel<K, false, true>), dim3(B * H), dim3(512), lds, stream, a); break;
-  switch (nkt) { FWD_KEEP(5) FWD_KEEP(6) FWD_KEEP(7) FWD_KEEP(8) }
-#undef FWD_KEEP
-  if (e) return e;
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
-}
-
-template <int NT, int NQT>
-static int launch_bwd_keep(const AttnArgs& a, hipStream_t stream) {
-  if constexpr (NQT > NT) return VITAMD_ERR_SHAPE;
-  else {
-    const int lds1 = 2 * NT * 32 * 128 + 4 * 4096, lds2 = 2 * NQT * 32 * 128 + 2 * NQT * 32 * 4 + 4 * 4096;
-    const dim3 grid(a.B * a.H), block(256);
-    if (int e = set_lds((attn_bwd_dq_pipe_kernel<NT, NQT, true>), lds1)) return e;
-    if (int e = set_lds((attn_bwd_dkv_pipe_kernel<NT, NQT, true>), lds2)) return e;
-    hipLaunchKernelGGL((attn_bwd_dq_pipe_kernel<NT, NQT, true>), grid, block, lds1, stream, a);    // also writes delta
-    hipLaunchKernelGGL((attn_bwd_dkv_pipe_kernel<NT, NQT, true>), grid, block, lds2, stream, a);
-    return VITAMD_OK;
-  }
-}
-
-template <int NT>
-static int launch_bwd_keep_nt(const AttnArgs& a, int nqt, hipStream_t stream) {
-  switch (nqt) {
-    case 1: return launch_bwd_keep<NT, 1>(a, stream);
-    case 2: return launch_bwd_keep<NT, 2>(a, stream);
-    case 3: return launch_bwd_keep<NT, 3>(a, stream);
-    case 4: return launch_bwd_keep<NT, 4>(a, stream);
-  }
-  return VITAMD_ERR_SHAPE;
+  const int nkt = (N + 31) / 32;
+  return launched(with_tiles<5, 8>(nkt, [&](auto K) {
+    return launch<attn_fwd_small8_kernel<CONST_OF(K), false, true>>(dim3(B * H), dim3(512), 2 * nkt * 32 * 128 + 8 * 2048, stream, a);
+  }));
 }
 
 extern "C" int vitamd_attention_bwd_keep(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta,
                                          float* dbias, int B, int N, int H, int head_dim, int nq, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (head_dim != DH) return VITAMD_ERR_SHAPE;
-  AttnArgs a{(const __bf16*)qkv, (__bf16*)o, (float*)lse2, (const __bf16*)d_o, (__bf16*)dqkv, delta, dbias, B, N, H, 0,
-             0.125f * 1.4426950408889634f, 0.125f, 0u, 1.0f, 0u, 0u, nullptr, nullptr, nq};
-  if (int e = check(a)) return e;
-  if (!qkv || !o || !lse2 || !d_o || !dqkv || !delta) return VITAMD_ERR_ARG;
+  AttnArgs a;
+  if (int e = make_args(a, true, qkv, o, lse2, d_o, dqkv, delta, dbias, B, N, H, head_dim, 0, 0.f, 0ull, nq)) return e;
   if (!(vitamd_attention_keep_forms(N, nq) & 2)) return VITAMD_ERR_SHAPE;
-  const int nkt = (N + 31) / 32, nqt = (nq + 31) / 32;
-  int e = VITAMD_ERR_SHAPE;
-  switch (nkt) {
-    case 2: e = launch_bwd_keep_nt<2>(a, nqt, stream); break;
-    case 3: e = launch_bwd_keep_nt<3>(a, nqt, stream); break;
-    case 4: e = launch_bwd_keep_nt<4>(a, nqt, stream); break;
-    case 5: e = launch_bwd_keep_nt<5>(a, nqt, stream); break;
-    case 6: e = launch_bwd_keep_nt<6>(a, nqt, stream); break;
-    case 7: e = launch_bwd_keep_nt<7>(a, nqt, stream); break;
-  }
-  if (e) return e;
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return launched(with_tiles<2, 7>((N + 31) / 32, [&](auto K) {
+    return with_tiles<1, 4>((nq + 31) / 32, [&](auto Q) { return launch_bwd_pipe<CONST_OF(K), CONST_OF(Q), true>(a, stream); });
+  }));
 }
