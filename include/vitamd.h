@@ -1,5 +1,5 @@
 /* vitamd.h — C ABI of libvitamd.so, the MI355X (gfx950) kernels behind the ViT training hot path
- * (and the KV-cached decoding of the causal stack).
+ * (the KV-cached decoding of the causal stack, and the loss and embedding kernels of its training step).
  *
  * The reference (SnakeOnex/vit-is-all-you-need) has no FFI layer: its hot path is a handful of
  * PyTorch ATen calls made from transformer.py and train_vit.py.  Each entry point below replaces
@@ -32,7 +32,8 @@ extern "C" {
 #define VITAMD_ERR_LAUNCH 3  /* HIP reported a launch error */
 #define VITAMD_ERR_INIT 4    /* vitamd_init has not run for the current device (GELU epilogues need its table) */
 
-/* ABI version of this header (bumped on any signature change): 9 (the KV-cached decoding entry points). */
+/* ABI version of this header (bumped on any signature change): 9 (the KV-cached decoding entry points; the cross-entropy and token-embedding
+ * entry points were added to 9 without changing an existing signature). */
 int vitamd_abi_version(void);
 
 /* Per-device set-up, once per device and process (idempotent; device < 0 = the current device; never inside a stream capture): builds the
@@ -242,6 +243,41 @@ int vitamd_decode_embed(const float* tok_table, const float* pos_table, const lo
  * replaces the `torch.argmax` of train_videogpt.py:63 where a sampled continuation is wanted (the reference has no sampler). */
 int vitamd_sample_logits(const float* logits, long long* token, float* info, const float* u, const unsigned long long* step, int B, int V,
                          int ld, float temperature, int top_k, float top_p, unsigned long long seed, void* stream);
+
+/* ---- Training the causal stack: cross-entropy over the vocabulary and the token + position embedding ----
+ * Mean cross-entropy over the rows whose target != ignore_index: F.cross_entropy(logits.float(), target) with mean reduction, all
+ * arithmetic in fp32 on the logits as stored.  logits fp32 or bf16 (logits_bf16 != 0) [M, V], row stride ld >= V elements; target
+ * int64 [M].  Writes loss_row fp32 [M] (0 for ignored rows), lse fp32 [M] (natural log, every row), stats fp32 [2] = {mean loss, 1 / count}.
+ * -inf logits are legal (zero probability, zero gradient); a row holds at least one finite logit.  Every row ignored: stats[0] is NaN.
+ * A target outside [0, V) that is not ignore_index is the caller's error: nothing is read for it, its loss_row is NaN (so the mean is
+ * NaN and the error shows without a host synchronise) and its gradient row is zeros.  Two launches: the rows (16-byte loads where the
+ * base is 16-byte aligned and ld % 8 == 0 (bf16) / ld % 4 == 0 (fp32), element loads otherwise), then one workgroup that sums loss_row
+ * in a fixed order and counts with an integer: no float atomics, every result is bit-reproducible.
+ * M >= 1, 2 <= V <= 65536, ld >= V, else VITAMD_ERR_SHAPE; a missing pointer VITAMD_ERR_ARG (after the shape check).
+ * replaces train_videogpt.py:52-53 and train_vit.py:101-103 (F.cross_entropy under autocast). */
+int vitamd_cross_entropy_fwd(const void* logits, int logits_bf16, const long long* target, float* loss_row, float* lse, float* stats,
+                             int M, int V, int ld, long long ignore_index, void* stream);
+/* The rows one sweep of the (capped) cross-entropy grid covers at this V; an M above it makes workgroups loop over further rows.  For
+ * tests that have to cross the cap.  V outside 2 .. 65536: -VITAMD_ERR_SHAPE. */
+int vitamd_cross_entropy_grid_rows(int V);
+/* dlogits[m, v] = (exp(x[m,v] - lse[m]) - [v == target[m]]) * (*grad_out) * stats[1]; ignored rows (and rows with a target outside
+ * [0, V)) are written as zeros, never multiplied.  grad_out: DEVICE fp32 scalar (NULL = 1).  dlogits fp32 or bf16 (round to nearest even
+ * of the fp32 value), row stride ldo >= V; columns V .. ldo-1 are not touched.  dlogits == logits (same type and stride, else
+ * VITAMD_ERR_ARG) is allowed: every element is read once and written once by the same lane.
+ * replaces the autograd backward of the same lines. */
+int vitamd_cross_entropy_bwd(const void* logits, int logits_bf16, const long long* target, const float* lse, const float* stats,
+                             const float* grad_out, void* dlogits, int dlogits_bf16, int M, int V, int ld, int ldo,
+                             long long ignore_index, void* stream);
+/* x fp32 [B*S, D]: x[b*S+s, :] = tok_table[ids[b*S+s], :] + pos_table[s, :] (one fp32 add: bit-equal to the framework's gather-and-add).
+ * D % 4 == 0, 1 <= S <= pos_rows, else VITAMD_ERR_SHAPE.  An id outside [0, tok_rows) leaves that row of x untouched; no table is read
+ * out of bounds.  replaces train_videogpt.py:49 (tok_embed(x) + pos_embed(arange)). */
+int vitamd_embed_tokens_fwd(const float* tok_table, const float* pos_table, const long long* ids, float* x, int B, int S, int D,
+                            int tok_rows, int pos_rows, void* stream);
+/* Its backward.  g fp32 [B*S, D] is read ONCE.  dpos fp32 [S, D] += sum over b in ascending order, by the one workgroup that owns
+ * (position s, column block): no atomics, reproducible.  dtok fp32 [tok_rows, D] += the g rows by fp32 atomics (order-dependent in the
+ * last bits, as vitamd_embed_bwd's outputs are), each wave-instruction adding 64 contiguous floats of one row.  Both are ACCUMULATED
+ * into: zero them for a fresh gradient.  Ids out of range add nothing to dtok.  D % 4 == 0. */
+int vitamd_embed_tokens_bwd(const float* g, const long long* ids, float* dtok, float* dpos, int B, int S, int D, int tok_rows, void* stream);
 
 /* ---- helpers around the GEMMs ---------------------------------------------------------------- */
 /* fp32 -> bf16 (autocast's per-step weight / activation cast, train_vit.py:100). */

@@ -1,14 +1,19 @@
-"""MI355X-native drop-in for the model half of the reference's `train_videogpt` module (reference train_videogpt.py:18-66):
-VideoGPTConfig and VideoGPT with the same constructor signatures, attributes and state_dict keys (`tok_embed.weight`,
+"""MI355X-native drop-in for the reference's `train_videogpt` module (reference train_videogpt.py:18-66 and the body of its training
+loop, :130-136): VideoGPTConfig and VideoGPT with the same constructor signatures, attributes and state_dict keys (`tok_embed.weight`,
 `pos_embed.weight`, `transformer.layers.*` including the causal `mask` buffers, `proj.{weight,bias}`), so reference checkpoints load.
 
-The causal stack runs on the HIP kernels (transformer.Transformer -> TransformerStackFn), the output projection on the MFMA GEMMs
-(functions.linear in forward, the skinny-M GEMM with fp32 logits in generate); the embedding gathers, the cross-entropy and the greedy
-argmax are torch device ops (as the loss is in train_vit.train_step); sampled generation (temperature / top-k / top-p) draws each token
-in one HIP kernel (csrc/sample.hip).  `generate` adds a KV cache (vitamd/decode.py): the prompt is prefilled
+The causal stack runs on the HIP kernels (transformer.Transformer -> TransformerStackFn), the output projection on the MFMA GEMMs.
+Two routes lead to the loss.  `forward` is the reference's: it returns the fp32 logits (functions.linear) and the loss, with the embedding
+gathers and the cross-entropy as torch device ops.  `loss` is the training route (vitamd/lm.py, csrc/loss.hip): the token + position
+embedding, the head GEMM with bf16 logits and the cross-entropy, forward and backward, are all kernels of the library - no logits in
+fp32, no padding, nothing left to the framework's ops.  `train_step` is one iteration of the reference loop on that route and `main()`
+runs it on seeded random tokens.  The greedy argmax of generation is a torch device op; sampled generation (temperature / top-k /
+top-p) draws each token in one HIP kernel (csrc/sample.hip).  `generate` adds a KV cache (vitamd/decode.py): the prompt is prefilled
 once and every further token costs one single-row pass through the stack - with graph=True one graph launch (vitamd/graph.py
-GraphedDecoder).  The reference's training loop and its external TiTok
-video tokenizer (train_videogpt.py:68-150) are not part of this module."""
+GraphedDecoder).  The reference's data loading and its external TiTok video tokenizer (train_videogpt.py:92-128) are not part of this
+module."""
+import argparse
+import time
 from dataclasses import dataclass
 
 import torch
@@ -16,7 +21,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from transformer import Transformer, transformer_configs
-from vitamd import ops
+from utils import get_lr_scheduler
+from vitamd import lm, ops
 from vitamd.functions import WEIGHTS, linear
 
 
@@ -63,6 +69,15 @@ class VideoGPT(nn.Module):
         logits = linear(h, self.proj.weight, self.proj.bias)
         loss = F.cross_entropy(logits.reshape(B * T * N, -1), y.reshape(B * T * N))
         return logits, loss
+
+    def loss(self, x):
+        """x [B, T, N] token ids -> the scalar cross-entropy of `forward`, by the training route: lm.token_embed, the stack,
+        lm.linear_cross_entropy (bf16 logits that live from the head GEMM to their own gradient; no logits are returned)"""
+        B, T, N = x.shape
+        y = x.reshape(B, T * N)
+        inp = torch.cat([self._sos(B, x.device), y[:, :-1]], dim=-1)
+        h = self.transformer(lm.token_embed(inp, self.tok_embed.weight, self.pos_embed.weight))
+        return lm.linear_cross_entropy(h, self.proj.weight, self.proj.bias, y.reshape(B * T * N))
 
     def _head(self, h_last):
         """fp32 logits [B, codebook_size] of hidden states [B, D]: the skinny-M GEMM (one row per sequence) where its shape rules hold,
@@ -175,3 +190,45 @@ class VideoGPT(nn.Module):
         B, T, N = video_tokens.shape
         return self.generate(video_tokens.reshape(B, T * N), n * self.config.frame_size, use_cache=use_cache, temperature=temperature,
                              top_k=top_k, top_p=top_p, seed=seed, graph=graph)
+
+
+def train_step(model, tokens, optim, lr_sched=None):
+    """One iteration of the reference hot loop (train_videogpt.py:130-136) without the fp16 scaler, on VideoGPT.loss."""
+    optim.zero_grad(set_to_none=True)
+    loss = model.loss(tokens)
+    loss.backward()
+    optim.step()
+    if lr_sched is not None:
+        lr_sched.step()
+    return loss
+
+
+def main():
+    p = argparse.ArgumentParser(description="VideoGPT training on synthetic tokens (MI355X-native path)")
+    p.add_argument("--frame_size", type=int, default=64)
+    p.add_argument("--codebook_size", type=int, default=1024)
+    p.add_argument("--transformer", type=str, default="B")
+    p.add_argument("--max_frames", type=int, default=16)
+    p.add_argument("--dropout", type=float, default=0.0)
+    p.add_argument("--bs", type=int, default=32)
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--weight_decay", type=float, default=1e-4)
+    p.add_argument("--warmup_steps", type=int, default=5000)
+    p.add_argument("--train_steps", type=int, default=50)
+    args = p.parse_args()
+    dev = torch.device("cuda")
+    cfg = VideoGPTConfig(args.frame_size, args.codebook_size, args.transformer, args.max_frames, args.dropout)
+    model = VideoGPT(cfg).to(dev)
+    optim = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    tokens = torch.randint(0, args.codebook_size, (args.bs, args.max_frames, args.frame_size), generator=g).to(dev)
+    for step in range(args.train_steps):
+        t0 = time.time()
+        loss = train_step(model, tokens, optim, sched)
+        torch.cuda.synchronize()
+        print(f"step {step} loss {loss.item():.4f} {tokens.numel() / (time.time() - t0):.0f} tokens/s")
+
+
+if __name__ == "__main__":
+    main()

@@ -15,7 +15,7 @@ CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 ABI_VERSION = 9
 
 _c = ctypes
-_P, _I, _F, _L, _U64, _D = _c.c_void_p, _c.c_int, _c.c_float, _c.c_long, _c.c_ulonglong, _c.c_double
+_P, _I, _F, _L, _U64, _D, _LL = _c.c_void_p, _c.c_int, _c.c_float, _c.c_long, _c.c_ulonglong, _c.c_double, _c.c_longlong
 
 # name -> argtypes ; every function returns int (VITAMD_OK == 0)
 SIGNATURES = {
@@ -65,6 +65,11 @@ SIGNATURES = {
     "vitamd_attention_keep_forms": [_I, _I],
     "vitamd_attention_fwd_keep": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_attention_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vitamd_cross_entropy_grid_rows": [_I],
+    "vitamd_cross_entropy_fwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _LL, _P],
+    "vitamd_cross_entropy_bwd": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _P],
+    "vitamd_embed_tokens_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vitamd_embed_tokens_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
 }
 
 ERRORS = {1: "unsupported shape", 2: "bad argument", 3: "HIP launch failure", 4: "vitamd_init has not run for this device"}

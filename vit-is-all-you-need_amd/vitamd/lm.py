@@ -1,0 +1,154 @@
+"""Training a next-token model on the HIP kernels: the cross-entropy over the vocabulary, the output head fused with it, and the
+token + position embedding (csrc/loss.hip).
+
+    loss = lm.cross_entropy(logits, target)                       # F.cross_entropy(logits.float(), target), mean, on the device
+    loss = lm.linear_cross_entropy(h, proj.weight, proj.bias, y)  # head GEMM -> bf16 logits -> loss, nothing in fp32 in between
+    x = lm.token_embed(ids, tok_embed.weight, pos_embed.weight)   # tok[ids] + pos[:S], fp32
+
+Every value the backward needs stays on the device (the upstream gradient is read by the kernel), so a step built from these records
+into a graph (vitamd.graph.GraphedStep) like the rest of the path.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from .functions import WEIGHTS, _amp_bwd, _amp_fwd, _f32c, linear
+
+BF16, F32 = torch.bfloat16, torch.float32
+
+
+def _rows(logits):
+    """logits of any leading shape as [M, V] with unit inner stride (a copy only when the layout demands one)"""
+    x = logits.detach()
+    x = x.reshape(-1, x.shape[-1])
+    return x if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else x.contiguous()
+
+
+def _target(target, M):
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.int64:
+        raise ops._lib.VitamdError(f"target: expected an int64 tensor, got {getattr(target, 'dtype', type(target))}")
+    t = target.reshape(-1).contiguous()
+    if t.numel() != M:
+        raise ops._lib.VitamdError(f"target: expected {M} elements (one per row of logits), got {t.numel()}")
+    return t
+
+
+def _scalar(g):
+    """the upstream gradient of a 0-dim loss as a device fp32 scalar the kernel reads (never .item())"""
+    return g.detach().to(F32).contiguous()
+
+
+class CrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index):
+        if not isinstance(logits, torch.Tensor) or logits.dim() < 1:
+            raise ops._lib.VitamdError("logits: expected a tensor [..., V]")
+        x = _rows(logits)
+        t = _target(target, x.shape[0])
+        _, lse, stats = ops.cross_entropy_fwd(x, t, ignore_index)
+        ctx.save_for_backward(x, t, lse, stats)
+        ctx.meta = (tuple(logits.shape), int(ignore_index))
+        return stats[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, lse, stats = ctx.saved_tensors
+        shape, ignore_index = ctx.meta
+        d = ops.cross_entropy_bwd(x, t, lse, stats, _scalar(g), ignore_index)        # dense, the logits' dtype
+        return d.view(shape), None, None
+
+
+def cross_entropy(logits, target, ignore_index=-100):
+    """Mean cross-entropy of logits [..., V] (fp32 or bf16, device) against target int64 [...] over the targets != ignore_index, computed
+    in fp32 on the logits as stored: the 0-dim fp32 loss.  Its gradient comes back in the logits' dtype.  A drop-in `loss_fn` for
+    train_vit.train_step and vitamd.graph.GraphedStep."""
+    return CrossEntropyFn.apply(logits, target, ignore_index)
+
+
+def fused_head_applies(V, D):
+    """the shapes linear_cross_entropy runs unpadded on the MFMA GEMMs (their own rules); others take functions.linear + cross_entropy"""
+    return V % 64 == 0 and D % 64 == 0
+
+
+class LinearCrossEntropyFn(torch.autograd.Function):
+    """loss = cross_entropy(h W^T + b, target) with bf16 logits that exist once: written by the head GEMM, read by the loss, overwritten
+    in place by their own gradient in the backward, which then feeds the two gradient GEMMs and the bias column sum."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, h, weight, bias, target, ignore_index):
+        M, D = h.shape
+        hb = ops.cast_bf16(_f32c(h))
+        wb, _ = WEIGHTS.get(weight, True)
+        logits = ops.gemm_nt(hb, wb, ops.EPI_BIAS_BF16, bias=None if bias is None else _f32c(bias))
+        t = _target(target, M)
+        _, lse, stats = ops.cross_entropy_fwd(logits, t, ignore_index)
+        ctx.save_for_backward(hb, logits, t, lse, stats)
+        ctx.weight = weight
+        ctx.meta = (h.dtype, bias is not None, int(ignore_index))
+        ctx.consumed = False
+        return stats[0]
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g):
+        if ctx.consumed:
+            raise RuntimeError("linear_cross_entropy: the logits were overwritten by their gradient in the first backward; "
+                               "a second backward through the same loss needs a new forward")
+        ctx.consumed = True
+        hb, logits, t, lse, stats = ctx.saved_tensors
+        hdtype, has_bias, ignore_index = ctx.meta
+        weight = ctx.weight
+        _, wbt = WEIGHTS.get(weight, True)
+        dl = ops.cross_entropy_bwd(logits, t, lse, stats, _scalar(g), ignore_index, out=logits)     # in place
+        dx = ops.gemm_nt(dl, wbt, ops.EPI_BIAS_BF16).to(hdtype) if ctx.needs_input_grad[0] else None
+        dW = torch.empty(tuple(weight.shape), dtype=F32, device=dl.device)
+        ops.gemm_tn(dl, hb, dW, accumulate=False)
+        db = ops.colsum(dl) if has_bias else None
+        return dx, dW, db, None, None
+
+
+def linear_cross_entropy(h, weight, bias, target, ignore_index=-100):
+    """cross_entropy(nn.Linear(h), target) for h [..., D], weight fp32 [V, D], bias fp32 [V] or None, target int64 [...]: the 0-dim fp32
+    mean loss.  V % 64 == 0 and D % 64 == 0: the fused head (LinearCrossEntropyFn; its backward consumes the logits, so a second
+    backward through the same loss raises RuntimeError).  Other shapes: functions.linear followed by cross_entropy."""
+    if not isinstance(h, torch.Tensor) or not isinstance(weight, torch.Tensor) or h.dim() < 1 or weight.dim() != 2 or h.shape[-1] != weight.shape[1]:
+        raise ops._lib.VitamdError("linear_cross_entropy: expected h [..., D] and weight [V, D]")
+    V, D = weight.shape
+    if not 2 <= V <= ops.CE_MAX_V:
+        raise ValueError(f"cross_entropy: the vocabulary must hold 2 .. {ops.CE_MAX_V} entries, got {V}")
+    if not h.is_cuda or not weight.is_cuda:
+        raise ops._lib.VitamdError("linear_cross_entropy: expected ROCm device tensors (the HIP kernels are the only implementation)")
+    if not fused_head_applies(V, D):
+        return cross_entropy(linear(h, weight, bias), target, ignore_index)
+    return LinearCrossEntropyFn.apply(h.reshape(-1, D), weight, bias, target, ignore_index)
+
+
+class TokenEmbedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ids, tok_weight, pos_weight):
+        if not isinstance(ids, torch.Tensor) or ids.dim() != 2:
+            raise ops._lib.VitamdError("token_embed: ids must be int64 [B, S]")
+        B, S = ids.shape
+        tok, pos = tok_weight.detach(), pos_weight.detach()
+        x = ops.embed_tokens_fwd(ids.contiguous(), tok, pos)
+        ctx.save_for_backward(ids)
+        ctx.meta = (tuple(tok.shape), tuple(pos.shape))
+        return x.view(B, S, tok.shape[1])
+
+    @staticmethod
+    def backward(ctx, g):
+        (ids,) = ctx.saved_tensors
+        tok_shape, pos_shape = ctx.meta
+        B, S = ids.shape
+        dtok = torch.zeros(tok_shape, dtype=F32, device=g.device)
+        dpos = torch.zeros(pos_shape, dtype=F32, device=g.device)          # the full table: rows >= S stay zero
+        ops.embed_tokens_bwd(_f32c(g).view(B * S, tok_shape[1]), ids.contiguous(), dtok, dpos)
+        return None, dtok, dpos
+
+
+def token_embed(ids, tok_weight, pos_weight):
+    """tok_weight[ids] + pos_weight[:S] for ids int64 [B, S] -> fp32 [B, S, D] (the bits of the torch gather-and-add), with the gradients
+    of both tables from one pass over the incoming gradient."""
+    return TokenEmbedFn.apply(ids, tok_weight, pos_weight)

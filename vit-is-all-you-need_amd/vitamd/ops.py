@@ -693,3 +693,107 @@ def sample_logits(logits, temperature=1.0, top_k=0, top_p=1.0, *, u=None, seed=0
     _lib.check(_L().vitamd_sample_logits(_p(logits), _p(token), _p(info), _p(u), _p(step), B, V, logits.stride(0), float(temperature), int(top_k),
                                          float(top_p), seed, _stream()), f"sample_logits[B={B},V={V},T={temperature},top_k={top_k},top_p={top_p}]")
     return (token, info) if return_info else token
+
+
+# ------------------------------------------------------------------------------------------ training the causal stack
+CE_MAX_V = 65536          # include/vitamd.h vitamd_cross_entropy_fwd
+
+
+def cross_entropy_grid_rows(V):
+    """rows one sweep of the capped cross-entropy grid covers at this V (asked of the library); more rows make workgroups loop"""
+    n = int(_L().vitamd_cross_entropy_grid_rows(int(V)))
+    if n < 0:
+        raise ValueError(f"cross_entropy: the vocabulary must hold 2 .. {CE_MAX_V} entries, got {V}")
+    return n
+
+
+def _need_logits(logits, name="logits"):
+    """[M, V] fp32 or bf16 with unit inner stride (the row stride may exceed V) -> (M, V, ld, is_bf16); V out of range: ValueError"""
+    V = logits.shape[-1] if isinstance(logits, torch.Tensor) and logits.dim() == 2 else None
+    if V is not None and not 2 <= V <= CE_MAX_V:
+        raise ValueError(f"cross_entropy: the vocabulary must hold 2 .. {CE_MAX_V} entries, got {V}")
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise _lib.VitamdError(f"{name}: expected a ROCm device tensor (the HIP kernels are the only implementation)")
+    if logits.dtype not in (F32, BF16) or logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise _lib.VitamdError(f"{name}: expected fp32 or bf16 [M, V] with unit inner stride, got {logits.dtype} {tuple(logits.shape)} "
+                               f"strides {logits.stride()}")
+    if logits.shape[0] < 1:
+        raise _lib.VitamdError(f"{name}: expected at least one row")
+    return logits.shape[0], logits.shape[1], logits.stride(0), int(logits.dtype == BF16)
+
+
+def cross_entropy_fwd(logits, target, ignore_index=-100):
+    """Mean cross-entropy of logits fp32 / bf16 [M, V] (unit inner stride) against target int64 [M] over the rows whose target is not
+    ignore_index, fp32 arithmetic -> (loss_row fp32 [M], lse fp32 [M], stats fp32 [2] = (mean loss, 1 / count)); semantics:
+    include/vitamd.h vitamd_cross_entropy_fwd.  Nothing synchronises: a target outside [0, V) shows as a NaN mean."""
+    M, V, ld, is_bf16 = _need_logits(logits)
+    _need(target, torch.int64, "target", 1)
+    if target.numel() != M:
+        raise _lib.VitamdError(f"target: expected {M} elements, got {target.numel()}")
+    loss_row = torch.empty((M,), dtype=F32, device=logits.device)
+    lse = torch.empty((M,), dtype=F32, device=logits.device)
+    stats = torch.empty((2,), dtype=F32, device=logits.device)
+    _lib.check(_L().vitamd_cross_entropy_fwd(_p(logits), is_bf16, _p(target), _p(loss_row), _p(lse), _p(stats), M, V, ld, int(ignore_index),
+                                             _stream()), f"cross_entropy_fwd[M={M},V={V},ld={ld}]")
+    return loss_row, lse, stats
+
+
+def cross_entropy_bwd(logits, target, lse, stats, grad_out=None, ignore_index=-100, out=None, out_dtype=None):
+    """dlogits = (softmax(logits) - onehot(target)) * grad_out / count from the forward's lse and stats; ignored rows are zeros.
+    grad_out: device fp32 scalar (None = 1).  out: where to write (fp32 or bf16 [M, V], unit inner stride; `logits` itself = in place);
+    None allocates a dense tensor of out_dtype (default: the logits' dtype)."""
+    M, V, ld, is_bf16 = _need_logits(logits)
+    _need(target, torch.int64, "target", 1); _need(lse, F32, "lse", 1); _need(stats, F32, "stats", 1)
+    if target.numel() != M or lse.numel() != M or stats.numel() != 2:
+        raise _lib.VitamdError(f"cross_entropy_bwd: expected target [{M}], lse [{M}] and stats [2]")
+    if grad_out is not None:
+        _need(grad_out, F32, "grad_out")
+        if grad_out.numel() != 1:
+            raise _lib.VitamdError("grad_out: expected a one-element device fp32")
+    if out is None:
+        out = torch.empty((M, V), dtype=out_dtype or logits.dtype, device=logits.device)
+    Mo, Vo, ldo, out_bf16 = _need_logits(out, "out")
+    if (Mo, Vo) != (M, V):
+        raise _lib.VitamdError(f"out: expected [{M}, {V}], got {tuple(out.shape)}")
+    if out.data_ptr() == logits.data_ptr() and (out_bf16 != is_bf16 or ldo != ld):
+        raise _lib.VitamdError("cross_entropy_bwd: in place needs the logits' own dtype and stride")
+    _lib.check(_L().vitamd_cross_entropy_bwd(_p(logits), is_bf16, _p(target), _p(lse), _p(stats), _p(grad_out), _p(out), out_bf16, M, V, ld,
+                                             ldo, int(ignore_index), _stream()), f"cross_entropy_bwd[M={M},V={V},ld={ld},ldo={ldo}]")
+    return out
+
+
+def _need_embed(ids, tok_table, pos_table, what):
+    _need(tok_table, F32, "tok_table", 2); _need(pos_table, F32, "pos_table", 2); _need(ids, torch.int64, "ids", 2)
+    B, S = ids.shape
+    D = tok_table.shape[1]
+    if pos_table.shape[1] != D or D % 4 != 0 or D < 4:
+        raise _lib.VitamdError(f"{what}: tables must share D with D % 4 == 0, got {tuple(tok_table.shape)} / {tuple(pos_table.shape)}")
+    if B < 1 or not 1 <= S <= pos_table.shape[0]:
+        raise _lib.VitamdError(f"{what}: ids [B, S] need B >= 1 and 1 <= S <= {pos_table.shape[0]} positions, got {tuple(ids.shape)}")
+    return B, S, D
+
+
+def embed_tokens_fwd(ids, tok_table, pos_table, out=None):
+    """x fp32 [B*S, D] = tok_table[ids] + pos_table[:S] (one fp32 add, the bits of the torch gather-and-add): ids int64 [B, S], tables fp32
+    [rows, D], D % 4 == 0.  An id outside the table leaves that row of `out` as it was (the kernel never reads outside a table)."""
+    B, S, D = _need_embed(ids, tok_table, pos_table, "embed_tokens_fwd")
+    if out is None:
+        out = torch.empty((B * S, D), dtype=F32, device=ids.device)
+    _need(out, F32, "out", 2)
+    if tuple(out.shape) != (B * S, D):
+        raise _lib.VitamdError(f"embed_tokens_fwd: out must be [{B * S}, {D}], got {tuple(out.shape)}")
+    _lib.check(_L().vitamd_embed_tokens_fwd(_p(tok_table), _p(pos_table), _p(ids), _p(out), B, S, D, tok_table.shape[0], pos_table.shape[0],
+                                            _stream()), f"embed_tokens_fwd[B={B},S={S},D={D}]")
+    return out
+
+
+def embed_tokens_bwd(g, ids, dtok, dpos):
+    """g fp32 [B*S, D], ids int64 [B, S]: dtok fp32 [tok_rows, D] += the rows of g at their ids (fp32 atomics), dpos fp32 [pos_rows, D]:
+    rows < S += the sum over the batch in ascending order (reproducible).  Both are accumulated into."""
+    B, S, D = _need_embed(ids, dtok, dpos, "embed_tokens_bwd")
+    _need(g, F32, "g", 2)
+    if tuple(g.shape) != (B * S, D):
+        raise _lib.VitamdError(f"embed_tokens_bwd: g must be [{B * S}, {D}], got {tuple(g.shape)}")
+    _lib.check(_L().vitamd_embed_tokens_bwd(_p(g), _p(ids), _p(dtok), _p(dpos), B, S, D, dtok.shape[0], _stream()),
+               f"embed_tokens_bwd[B={B},S={S},D={D}]")
+    return dtok, dpos
