@@ -33,7 +33,7 @@ extern "C" {
 #define VITAMD_ERR_INIT 4    /* vitamd_init has not run for the current device (GELU epilogues need its table) */
 
 /* ABI version of this header (bumped on any signature change): 9 (the KV-cached decoding entry points; the cross-entropy and token-embedding
- * entry points were added to 9 without changing an existing signature). */
+ * entry points, and the multi-tensor optimiser entry points vitamd_mt_*, were added to 9 without changing an existing signature). */
 int vitamd_abi_version(void);
 
 /* Per-device set-up, once per device and process (idempotent; device < 0 = the current device; never inside a stream capture): builds the
@@ -333,6 +333,45 @@ int vitamd_adamw_step(float* p, const float* g, float* m, float* v, long n, floa
  * (with fp32 betas, 1 - beta inherits the rounding of beta: 1.3e-5 relative on exp_avg_sq at beta2 = 0.999).  vitamd.optim.AdamW calls this one. */
 int vitamd_adamw_step_d(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2,
                         float eps, float weight_decay, int step, void* stream);
+
+/* ---- multi-tensor optimiser step with on-device gradient-norm clipping ----
+ * The whole step after backward() in one to three launches over a ROW TABLE: one row per tensor that has a gradient this step.  Every
+ * per-step and per-group value lives in the row, so parameter groups, and parameters whose step count lags, share one launch.
+ * replaces train_titok.py / train_vit_vqgan.py / train_tatitok.py `clip_grad_norm_(model.parameters(), 1.0)` + `optim.step()`. */
+typedef struct vitamd_mt_row {
+  float* p;                /* parameter, updated in place (may be NULL for vitamd_mt_sumsq / vitamd_mt_scale) */
+  const float* g;          /* gradient; read by all three calls, written by vitamd_mt_scale alone */
+  float* m;                /* exp_avg (as p) */
+  float* v;                /* exp_avg_sq (as p) */
+  long long n;             /* elements, >= 1 */
+  int first_chunk;         /* running sum of ceil(n / vitamd_mt_chunk_elems()) over the rows before this one */
+  float lr, weight_decay;
+  float beta1, one_minus_beta1, beta2, one_minus_beta2; /* each rounded to fp32 once from the double, as vitamd_adamw_step_d does */
+  float eps;
+  float inv_bc1;           /* fp32(1 / (1 - beta1^step)) of THIS tensor's 1-based step */
+  float inv_sqrt_bc2;      /* fp32(1 / sqrt(1 - beta2^step)) */
+} vitamd_mt_row;           /* 80 bytes, 8-byte aligned */
+/* Queries: sizeof(vitamd_mt_row) as this library was compiled; the elements per chunk (a multiple of 4); the workgroups per launch, above
+ * which workgroups stride over further chunks.  For bindings that build the table, and for tests that have to cross the cap. */
+long vitamd_mt_row_bytes(void);
+int vitamd_mt_chunk_elems(void);
+int vitamd_mt_grid_cap(void);
+/* All three calls take the table twice: rows_host, the caller's HOST copy, is read before anything is launched - n_rows >= 1, every
+ * n >= 1, first_chunk the running sum above and total_chunks its final value (else VITAMD_ERR_SHAPE), every tensor pointer the call uses
+ * present and 16-byte aligned (else VITAMD_ERR_ARG, nothing launched, nothing touched) - and rows_dev, the same bytes in device memory
+ * (uploaded by the caller on `stream`), is what the kernels walk.  A missing buffer is VITAMD_ERR_ARG.
+ *
+ * Global gradient norm: partials fp32 [total_chunks] (scratch, every entry written) receives one sum of squares per chunk; a second,
+ * single-workgroup launch adds them in a fixed order in fp64 and writes norm_coef fp32 [2] = {norm, coef} with
+ * coef = min(1, max_norm / (norm + 1e-6)) evaluated in fp32 as torch.nn.utils.clip_grad_norm_ does; max_norm <= 0: coef = 1.
+ * No float atomics: the same gradients give the same bits on every call, whatever the grid.  Uses g alone. */
+int vitamd_mt_sumsq(const vitamd_mt_row* rows_host, const void* rows_dev, int n_rows, int total_chunks, float* partials, float* norm_coef,
+                    float max_norm, void* stream);
+/* AdamW over the table, arithmetic of vitamd_adamw_step_d element for element.  coef: DEVICE fp32 scalar (norm_coef + 1) by which the
+ * gradient is multiplied before the update, read by the kernel (no host synchronisation); NULL = not multiplied.  g is not written. */
+int vitamd_mt_adamw(const vitamd_mt_row* rows_host, const void* rows_dev, int n_rows, int total_chunks, const float* coef, void* stream);
+/* g *= *coef in place (coef required); stores nothing when *coef == 1.  Uses g alone.  For clipping in front of another optimiser. */
+int vitamd_mt_scale(const vitamd_mt_row* rows_host, const void* rows_dev, int n_rows, int total_chunks, const float* coef, void* stream);
 
 #ifdef __cplusplus
 }

@@ -203,7 +203,7 @@ def train_step(model, tokens, optim, lr_sched=None):
     return loss
 
 
-def main():
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description="VideoGPT training on synthetic tokens (MI355X-native path)")
     p.add_argument("--frame_size", type=int, default=64)
     p.add_argument("--codebook_size", type=int, default=1024)
@@ -215,11 +215,24 @@ def main():
     p.add_argument("--weight_decay", type=float, default=1e-4)
     p.add_argument("--warmup_steps", type=int, default=5000)
     p.add_argument("--train_steps", type=int, default=50)
-    args = p.parse_args()
+    p.add_argument("--max_grad_norm", type=float, default=None,
+                   help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
+    return p.parse_args(argv)
+
+
+def make_optim(model, args):
+    if args.max_grad_norm is None:
+        return torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    from vitamd.optim import AdamW
+    return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
+
+
+def main():
+    args = parse_args()
     dev = torch.device("cuda")
     cfg = VideoGPTConfig(args.frame_size, args.codebook_size, args.transformer, args.max_frames, args.dropout)
     model = VideoGPT(cfg).to(dev)
-    optim = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    optim = make_optim(model, args)
     sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
     g = torch.Generator(device="cpu").manual_seed(0)
     tokens = torch.randint(0, args.codebook_size, (args.bs, args.max_frames, args.frame_size), generator=g).to(dev)

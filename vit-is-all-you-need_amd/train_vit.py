@@ -75,7 +75,7 @@ def train_step(model, images, labels, optim, lr_sched=None, loss_fn=None):
     return loss
 
 
-def main():
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description="ViT classifier training on synthetic data (MI355X-native path)")
     p.add_argument("--image_size", type=int, default=224)
     p.add_argument("--patch_size", type=int, default=16)
@@ -87,11 +87,24 @@ def main():
     p.add_argument("--weight_decay", type=float, default=1e-2)
     p.add_argument("--warmup_steps", type=int, default=10)
     p.add_argument("--train_steps", type=int, default=50)
-    args = p.parse_args()
+    p.add_argument("--max_grad_norm", type=float, default=None,
+                   help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
+    return p.parse_args(argv)
+
+
+def make_optim(model, args):
+    if args.max_grad_norm is None:
+        return torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    from vitamd.optim import AdamW
+    return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
+
+
+def main():
+    args = parse_args()
     dev = torch.device("cuda")
     cfg = ViTConfig(args.image_size, 3, args.patch_size, args.transformer, args.extra_tokens, 0.0)
     model = ViTClassifier(cfg, args.num_classes).to(dev)
-    optim = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    optim = make_optim(model, args)
     sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
     g = torch.Generator(device="cpu").manual_seed(0)
     images = torch.randn(args.bs, 3, args.image_size, args.image_size, generator=g).to(dev)

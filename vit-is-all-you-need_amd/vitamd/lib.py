@@ -52,6 +52,12 @@ SIGNATURES = {
     "vitamd_conv3x3_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_adamw_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P],
     "vitamd_adamw_step_d": [_P, _P, _P, _P, _L, _F, _D, _D, _F, _F, _I, _P],
+    "vitamd_mt_row_bytes": [],
+    "vitamd_mt_chunk_elems": [],
+    "vitamd_mt_grid_cap": [],
+    "vitamd_mt_sumsq": [_P, _P, _I, _I, _P, _P, _F, _P],
+    "vitamd_mt_adamw": [_P, _P, _I, _I, _P, _P],
+    "vitamd_mt_scale": [_P, _P, _I, _I, _P, _P],
     "vitamd_kv_append": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_decode_attention_ws_bytes": [_I, _I, _I],
     "vitamd_decode_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
