@@ -60,7 +60,10 @@ int vitamd_init(int device, void* stream);
  * short reduction dim (K <= 1536) and >= 3 tiles per CU in the form that requests the next tile's operands before the epilogue);
  * 512 = auto without persistent launches; 1024 = auto with persistent launches but without the seam / loader forms; 2048 = the
  * loader-wave form (256-row tiles, twelve waves per workgroup, four of them only issue the operand requests; bias / GELU / dGELU-multiply
- * epilogues, K % 128 == 0; VITAMD_ERR_SHAPE where it does not apply).  All forms give bit-identical results.
+ * epilogues, K % 128 == 0; VITAMD_ERR_SHAPE where it does not apply); 4096 = the seam form on 256-row tiles (the same epilogues, K % 64 == 0,
+ * K >= 128; VITAMD_ERR_SHAPE where it does not apply).  All forms give bit-identical results.  With VITAMD_EPI_DMUL, colsum may be NULL:
+ * the seam and loader forms then run without the column sums in their epilogue (the bias gradient can come from
+ * vitamd_gemm_tn_bf16_ws_colsum instead); `out` is bit-identical either way.
  * Forward of nn.Linear (x W^T + b): A = x, B = W.  Input gradient (dy W): A = dy, B = W^T. */
 int vitamd_gemm_nt_bf16(const void* A, const void* B, void* out, void* out2, const float* bias, const void* aux,
                         float* colsum, int M, int N, int K, int ldo, int epi, int n_patches, int seq, int extra,
@@ -89,8 +92,8 @@ int vitamd_linear_dropout_resid_bf16(const void* A, const void* B, float* out, c
 int vitamd_gemm_tn_bf16(const void* L, const void* Rm, float* out, int R, int P, int Q, int ldl, int ldr, int ldo,
                         int splits, void* stream);
 
-/* Same GEMM with a caller-provided split-K workspace (>= splits * ceil(P/256) * ceil(Q/256) * 256 KiB,
- * vitamd_gemm_tn_ws_bytes tells): partial tiles are written with plain stores and summed by a second
+/* Same GEMM with a caller-provided split-K workspace (>= splits * ceil(P/256) * ceil(Q/256) * 256 KiB;
+ * vitamd_gemm_tn_ws_bytes tells, and adds the 1 KiB per split and row tile that vitamd_gemm_tn_bf16_ws_colsum needs): partial tiles are written with plain stores and summed by a second
  * pass (bitwise reproducible, ~4x the rate of the atomic form).  accumulate = 0 overwrites `out`.
  * `form` picks the kernel (same results): which one is faster depends on what runs beside the launch. */
 #define VITAMD_TN_FORM_SHARED 0    /* 8 waves per workgroup, 2/3 of the register file: waves of other kernels (LayerNorm) can share the CU */
@@ -98,6 +101,15 @@ int vitamd_gemm_tn_bf16(const void* L, const void* Rm, float* out, int R, int P,
 int vitamd_gemm_tn_bf16_ws(const void* L, const void* Rm, float* out, int R, int P, int Q, int ldl, int ldr, int ldo,
                            int splits, float* ws, long ws_bytes, int accumulate, int form, void* stream);
 long vitamd_gemm_tn_ws_bytes(int R, int P, int Q, int splits);
+
+/* The workspace form that also sums the columns of L: colsum[p] += sum_r float(L[r,p]) for p < P (fp32 [P], caller-zeroed or holding a
+ * running sum) - the bias gradient of the Linear whose weight gradient the call forms, taken from the operand tiles the GEMM stages anyway.
+ * The sums are formed by the workgroups of the first column tile beside their MFMAs; their partials (256 floats per split and row tile)
+ * lie behind the partial tiles in `ws` - vitamd_gemm_tn_ws_bytes counts them - and the reduce pass adds them in split order: no atomics,
+ * bitwise reproducible.  `out` is bit-identical to vitamd_gemm_tn_bf16_ws's.  colsum == NULL is that call; a workspace that is missing
+ * or too small is VITAMD_ERR_ARG (the atomic form has no reduce pass to sum in). */
+int vitamd_gemm_tn_bf16_ws_colsum(const void* L, const void* Rm, float* out, float* colsum, int R, int P, int Q, int ldl, int ldr,
+                                  int ldo, int splits, float* ws, long ws_bytes, int accumulate, int form, void* stream);
 
 /* ---- LayerNorm (no affine, eps as given) on the fp32 residual stream -------------------------
  * forward: x = x_in (+ addend_bf16 -> also written to x_out); y = bf16(LN(x)); mean/rstd saved.

@@ -16,7 +16,7 @@ extern "C" int vitamd_gemm_nt_bf16(const void* A, const void* B, void* out, void
   if (epi == 6) epi = EPI_GELU;
   if (epi == 7) epi = EPI_DGELU;
   GemmNtArgs p{A, B, out, out2, bias, aux, colsum, M, N, K, ldo, epi, n_patches, seq, extra, tile, 0u, 1.0f, 0u, 0u, 0, dg};
-  if (!is_auto(tile) && tile != NT_TILE_128 && tile != NT_TILE_256 && tile != NT_TILE_320 && tile != NT_TILE_LOADER) return VITAMD_ERR_ARG;
+  if (!is_auto(tile) && tile != NT_TILE_128 && tile != NT_TILE_256 && tile != NT_TILE_320 && tile != NT_TILE_LOADER && tile != NT_TILE_SEAM) return VITAMD_ERR_ARG;
   return vitamd_gemm_nt_impl(p, (hipStream_t)stream);
 }
 
@@ -27,7 +27,7 @@ extern "C" int vitamd_gemm_nt_plan(int M, int N, int K, int ldo, int epi, int ti
   if (epi == 7) epi = EPI_DGELU;
   static char dummy[16];                   // the launch rules only ask whether the optional pointers are present
   GemmNtArgs p{dummy, dummy, dummy, dummy, nullptr, dummy, (float*)dummy, M, N, K, ldo, epi, 1, 1, 0, tile, 0u, 1.0f, 0u, 0u, 0, dg};
-  if (!is_auto(tile) && tile != NT_TILE_128 && tile != NT_TILE_256 && tile != NT_TILE_320 && tile != NT_TILE_LOADER) return -VITAMD_ERR_ARG;
+  if (!is_auto(tile) && tile != NT_TILE_128 && tile != NT_TILE_256 && tile != NT_TILE_320 && tile != NT_TILE_LOADER && tile != NT_TILE_SEAM) return -VITAMD_ERR_ARG;
   return vitamd_gemm_nt_plan_impl(p);
 }
 
@@ -41,6 +41,14 @@ extern "C" int vitamd_gemm_tn_bf16_ws(const void* L, const void* Rm, float* out,
                                       int splits, float* ws, long ws_bytes, int accumulate, int form, void* stream) {
   if (form != 0 && form != 1) return VITAMD_ERR_ARG;
   GemmTnArgs a{L, Rm, out, R, P, Q, ldl, ldr, ldo, splits, ws, (size_t)(ws_bytes < 0 ? 0 : ws_bytes), accumulate, form};
+  return vitamd_gemm_tn_impl(a, (hipStream_t)stream);
+}
+
+extern "C" int vitamd_gemm_tn_bf16_ws_colsum(const void* L, const void* Rm, float* out, float* colsum, int R, int P, int Q, int ldl, int ldr,
+                                             int ldo, int splits, float* ws, long ws_bytes, int accumulate, int form, void* stream) {
+  if (form != 0 && form != 1) return VITAMD_ERR_ARG;
+  GemmTnArgs a{L, Rm, out, R, P, Q, ldl, ldr, ldo, splits, ws, (size_t)(ws_bytes < 0 ? 0 : ws_bytes), accumulate, form, colsum};
+  if (colsum && !ws) return VITAMD_ERR_ARG;
   return vitamd_gemm_tn_impl(a, (hipStream_t)stream);
 }
 

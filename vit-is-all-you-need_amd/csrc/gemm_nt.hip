@@ -330,6 +330,7 @@ static NtPlan plan_single(const GemmNtArgs& p) {
   const bool seam_epi = epi == EPI_BIAS_BF16 || epi == EPI_GELU || epi == EPI_DGELU;
   const bool tall_epi = seam_epi || epi == EPI_RESID_F32;
   if (tile == NT_TILE_LOADER) return (seam_epi && ld_ok(p)) ? NtPlan{NT_FORM_LOADER, 256, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
+  if (tile == NT_TILE_SEAM) return (seam_epi && seam_ok(p)) ? NtPlan{NT_FORM_SEAM, 256, VITAMD_OK} : NtPlan{0, 0, VITAMD_ERR_SHAPE};
   const bool no_seam = tile == NT_TILE_AUTO_NO_SEAM;      // the automatic choice with persistent launches but WITHOUT the seam / loader forms (A/B and start-up probe: ops.seam_probe)
   if (no_seam) tile = NT_TILE_AUTO;
   const long big_tiles = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
@@ -374,9 +375,11 @@ int dispatch_tile(const GemmNtArgs& p, hipStream_t stream) {
   if (pl.err) return pl.err;
   switch (pl.form) {
     case NT_FORM_LOADER:
+      if constexpr (EPI == EPI_DGELU) { if (!p.colsum) return launch_ld<EPI_DGELU_NOCS>(p, stream, device_cus()); }
       if constexpr (seam_epi) return launch_ld<EPI, EPI == EPI_GELU>(p, stream, device_cus());
       break;
     case NT_FORM_SEAM:
+      if constexpr (EPI == EPI_DGELU) { if (!p.colsum) return launch_seam<EPI_DGELU_NOCS, 8>(p, stream, device_cus()); }
       if constexpr (EPI == EPI_BIAS_BF16) { if (pl.rows == 320) return launch_seam<EPI, 10>(p, stream, device_cus()); }
       if constexpr (seam_epi) return launch_seam<EPI, 8, EPI == EPI_GELU>(p, stream, device_cus());
       break;

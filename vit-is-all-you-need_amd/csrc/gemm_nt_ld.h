@@ -35,9 +35,11 @@ namespace {
 // parameter stays part of the kernel's name, which the recorded profiles key on.
 template <int EPI, bool TAB = false, int SCHED = 1>
 __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
-  static_assert(EPI == EPI_BIAS_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU, "epilogues of the loader form");
+  static_assert(EPI == EPI_BIAS_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU || EPI == EPI_DGELU_NOCS, "epilogues of the loader form");
   static_assert(SCHED == 1, "request schedule");
   static_assert(!TAB || EPI == EPI_GELU, "table = GELU");
+  constexpr bool DG = EPI == EPI_DGELU || EPI == EPI_DGELU_NOCS;      // the dGELU-multiply epilogue ...
+  constexpr bool CS = EPI == EPI_DGELU;                               // ... with the column sums of the stored tile (p.colsum)
   constexpr int BM = 256, BN = 256, MT = 8, NT = 4;
   constexpr int AREG = 16384, ABUF = 32768, BBUF = 32768, BBASE = 2 * ABUF, OPS = BBASE + 2 * BBUF;
   constexpr int STG = 2048, TABOFF = OPS + 8 * STG;
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
         VITAMD_WAIT_VM(6);                              // A1(kt) (first read in phase 1) has landed
         __builtin_amdgcn_s_barrier();
         // ---- phase 1: B pieces 6, 7 and A0
-        if constexpr (EPI != EPI_DGELU) {
+        if constexpr (!DG) {
           // first K-tile of a tile: every compute wave is inside the main loop, its staging image idle - the bias of ITS 64 columns goes there
           // (256 B by LDS-DMA; both wave rows), long before the epilogue reads it
           if (kt == 0) {
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
   const int wm = wave >> 2, wn = wave & 3;
   const srd_t rsO = make_srd(p.out, (size_t)p.M * p.ldo * 2);
   const srd_t rsO2 = make_srd(EPI == EPI_GELU ? p.out2 : p.out, (size_t)p.M * p.ldo * 2);
-  const srd_t srdAux = make_srd(EPI == EPI_DGELU ? p.aux : p.out, (size_t)p.M * p.ldo * 2);
+  const srd_t srdAux = make_srd(DG ? p.aux : p.out, (size_t)p.M * p.ldo * 2);
   if constexpr (TAB) gelu_table_to_lds(p.gelu_tab, smem + TABOFF, tid);      // visible to every wave after the START barrier
   __builtin_amdgcn_s_barrier();                         // START: the loaders waited for the first K-tile's B and A0
   asm volatile("" ::: "memory");
@@ -236,10 +238,10 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
     const int mrow0 = m0 + wm * 128 + rsub;             // + 16 i + 8 h
     const unsigned obase = ncol_ok ? (unsigned)mrow0 * (unsigned)(p.ldo * 2) + (unsigned)ncol * 2u : OOB;
     const unsigned rstep = (unsigned)(p.ldo * 2) * 8u;
-    u32x4 aux[EPI == EPI_DGELU ? 2 * MT : 1];
-    u32x2 pk[EPI == EPI_DGELU ? MT : 1][NT];            // dGELU: the tile rounded to bf16 BEFORE the factors are loaded (64 + 64 registers)
+    u32x4 aux[DG ? 2 * MT : 1];
+    u32x2 pk[DG ? MT : 1][NT];            // dGELU: the tile rounded to bf16 BEFORE the factors are loaded (64 + 64 registers)
     f32x4 bias4[NT];
-    if constexpr (EPI == EPI_DGELU) {
+    if constexpr (DG) {
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -263,7 +265,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         u32x2 o;
-        if constexpr (EPI == EPI_DGELU) o = pk[i][j];
+        if constexpr (DG) o = pk[i][j];
         else {
           const f32x4 v = acc[i][j] + bias4[j];
           o = (u32x2){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
@@ -296,14 +298,14 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const GemmNtArgs p) {
           for (int c = 0; c < 4; ++c) {
             const float lo = round_bf16(bf16lo(v[c]) * bf16lo(pz[c]));          // aux holds gelu'(pre) (stored-derivative form only: ld_ok)
             const float hi = round_bf16(bf16hi(v[c]) * bf16hi(pz[c]));
-            if (voff != OOB) { cs[2 * c] += lo; cs[2 * c + 1] += hi; }
+            if constexpr (CS) { if (voff != OOB) { cs[2 * c] += lo; cs[2 * c + 1] += hi; } }
             o[c] = pack_bf16x2(lo, hi);
           }
           asm_bstore16_nt(o, rsO, voff, soff);
         }
       }
     }
-    if constexpr (EPI == EPI_DGELU) {
+    if constexpr (CS) {
       // column sums of the stored tile (bias gradient of the producing Linear): the butterfly of gemm_nt_seam_kernel, one atomic instruction per wave
 #pragma unroll
       for (int bf = 1; bf < 8; bf <<= 1)

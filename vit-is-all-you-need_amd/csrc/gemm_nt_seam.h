@@ -24,8 +24,10 @@ namespace {
 
 template <int EPI, int MT, bool TAB = false>
 __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
-  static_assert(EPI == EPI_BIAS_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU, "epilogues without (or with up-front) auxiliary loads");
+  static_assert(EPI == EPI_BIAS_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU || EPI == EPI_DGELU_NOCS, "epilogues without (or with up-front) auxiliary loads");
   static_assert(!TAB || (EPI == EPI_GELU && MT == 8), "the GELU table needs the 16 KiB that only the 256-row ring leaves");
+  constexpr bool DG = EPI == EPI_DGELU || EPI == EPI_DGELU_NOCS;      // the dGELU-multiply epilogue ...
+  constexpr bool CS = EPI == EPI_DGELU;                               // ... with the column sums of the stored tile (p.colsum)
   constexpr int LA = 4;
   using S = NtSchedule<MT, LA>;
   constexpr int NP = S::NP;
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
   constexpr int SL = STG / 2048;                     // 16-row slices staged per round
   static_assert(SL >= 1 && MT % SL == 0, "staging");
   // vector-memory instructions every wave issues per epilogue BEHIND the next tile's requests
-  constexpr int E = EPI == EPI_GELU ? 4 * MT : EPI == EPI_DGELU ? 2 * MT + 1 : 2 * MT;
+  constexpr int E = EPI == EPI_GELU ? 4 * MT : CS ? 2 * MT + 1 : 2 * MT;
   static_assert(S::wait(NP - 1) + E <= 63 && S::wait(0, E) <= 63, "vmcnt is a 6-bit counter");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
   const srd_t srdB = make_srd(p.B, (size_t)p.N * K * 2);
   const srd_t rsO = make_srd(p.out, (size_t)p.M * p.ldo * 2);
   const srd_t rsO2 = make_srd(EPI == EPI_GELU ? p.out2 : p.out, (size_t)p.M * p.ldo * 2);
-  const srd_t srdAux = make_srd(EPI == EPI_DGELU ? p.aux : p.out, (size_t)p.M * p.ldo * 2);
+  const srd_t srdAux = make_srd(DG ? p.aux : p.out, (size_t)p.M * p.ldo * 2);
   const srd_t srdBias = make_srd(p.bias ? (const void*)p.bias : p.out, p.bias ? (size_t)p.N * 4 : 0);     // no bias: zero records, every load returns 0
   constexpr unsigned OOB = 0x80000000u;
   const unsigned lds0 = lds_addr(smem) + wave * 1024;
@@ -130,9 +132,9 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
     const unsigned obase = ncol_ok ? (unsigned)mrow0 * (unsigned)(p.ldo * 2) + (unsigned)ncol * 2u : OOB;
     const unsigned rstep = (unsigned)(p.ldo * 2) * 8u;
     // pre-loads (inline asm, counted by hand): bias (fp32, 4 x 4 columns of the accumulator layout) or the dGELU factor (row-major view)
-    u32x4 aux[EPI == EPI_DGELU ? 2 * MT : 1];
-    u32x2 pk[EPI == EPI_DGELU ? MT : 1][NT];         // dGELU: the tile rounded to bf16 BEFORE the factor is loaded (64 + 64 registers instead of 128 + 64)
-    if constexpr (EPI == EPI_DGELU) {
+    u32x4 aux[DG ? 2 * MT : 1];
+    u32x2 pk[DG ? MT : 1][NT];         // dGELU: the tile rounded to bf16 BEFORE the factor is loaded (64 + 64 registers instead of 128 + 64)
+    if constexpr (DG) {
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
     // (two statements in the arms of a branch made hipcc copy the registers - before the data had landed - ahead of one of them)
     // (dGELU: one wait per ROUND - round 0 starting when 4 of the 16 factor loads are back - was measured equal, 275.6 against 276.6 us: what the
     // factor loads cost is their issue and their HBM bytes, not the latency of the last of them)
-    if constexpr (EPI == EPI_DGELU) {
+    if constexpr (DG) {
       static_assert(MT == 8, "16 pre-load registers named in one asm statement");
       asm volatile("s_waitcnt vmcnt(%16)" : "+v"(aux[0]), "+v"(aux[1]), "+v"(aux[2]), "+v"(aux[3]), "+v"(aux[4]), "+v"(aux[5]), "+v"(aux[6]), "+v"(aux[7]), "+v"(aux[8]), "+v"(aux[9]), "+v"(aux[10]), "+v"(aux[11]), "+v"(aux[12]), "+v"(aux[13]), "+v"(aux[14]), "+v"(aux[15]) : "n"(NREQ) : "memory");
     } else {
@@ -172,7 +174,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       bias4[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if constexpr (EPI != EPI_DGELU) {
+      if constexpr (!DG) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) bias4[j][r] = round_bf16(((const float*)stg)[16 * j + 4 * g + r]);     // autocast casts the bias to bf16
       }
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
           u32x2 o;
-          if constexpr (EPI == EPI_DGELU) o = pk[i][j];
+          if constexpr (DG) o = pk[i][j];
           else {
             const f32x4 v = acc[i][j] + bias4[j];
             o = (u32x2){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
@@ -225,7 +227,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
             for (int c = 0; c < 4; ++c) {
               const float lo = round_bf16(bf16lo(v[c]) * bf16lo(pz[c]));        // aux holds gelu'(pre) (stored-derivative form only: seam_ok)
               const float hi = round_bf16(bf16hi(v[c]) * bf16hi(pz[c]));
-              if (voff != OOB) { cs[2 * c] += lo; cs[2 * c + 1] += hi; }
+              if constexpr (CS) { if (voff != OOB) { cs[2 * c] += lo; cs[2 * c + 1] += hi; } }
               o[c] = pack_bf16x2(lo, hi);
             }
             asm_bstore16_nt(o, rsO, voff, soff);
@@ -233,7 +235,7 @@ __global__ __launch_bounds__(512) void gemm_nt_seam_kernel(const GemmNtArgs p) {
         }
       }
     }
-    if constexpr (EPI == EPI_DGELU) {
+    if constexpr (CS) {
       // column sums of the stored tile (bias gradient of the producing Linear).  Lanes (rsub, pc) with equal pc ^ rsub hold partial sums of the
       // same 8 columns (their rows differ): a butterfly over rsub (partner lane ^ 9 b keeps pc ^ rsub) totals them in registers, then lane
       // (rsub, pc) adds column rsub of its chunk - exactly one atomic instruction per wave (N % 256 == 0 is a launch condition), no barrier and
@@ -268,7 +270,7 @@ int launch_seam(const GemmNtArgs& p, hipStream_t stream, int cus) {
 static bool seam_ok(const GemmNtArgs& p) {
   if (p.K % 64 != 0 || p.K < 128 || p.N % 8 != 0 || p.ldo % 8 != 0) return false;
   if ((size_t)p.M * p.K * 2 >= 0xf0000000ull || (size_t)p.N * p.K * 2 >= 0xf0000000ull || (size_t)p.M * p.ldo * 2 >= 0x80000000ull) return false;
-  if (p.epi == EPI_DGELU) return p.gelu_dg && p.colsum != nullptr && p.N % 256 == 0 && p.aux != nullptr;
+  if (p.epi == EPI_DGELU) return p.gelu_dg && p.N % 256 == 0 && p.aux != nullptr;      // colsum == null: the EPI_DGELU_NOCS instantiations
   if (p.epi == EPI_GELU) return p.out2 != nullptr;
   return p.epi == EPI_BIAS_BF16;
 }

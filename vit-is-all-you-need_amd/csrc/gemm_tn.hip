@@ -33,6 +33,20 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* p) {
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// Column sums of L beside the GEMM (GemmTnArgs::colsum: the bias gradient of the Linear whose weight gradient this is).  An A fragment holds,
+// in lane l, the 8 reduction rows 8 (l >> 5) .. + 7 of column l & 31 of its 32-column p-tile: their sum is 4 v_dot2c_f32_bf16 against (1, 1)
+// into ONE fp32 register per lane, issued in the shadow of the phase's MFMAs; lanes l and l + 32 are combined once behind the main loop.
+// The four waves of a wave row hold the same four fragments, so wave column wq sums p-tile wq alone - and, so that this is the SAME register in
+// every wave (no selects), the CS kernels walk their p-tiles rotated by wq: fragment i of wave column wq is p-tile (i + wq) & 3 (frag_pairsum below).  Every
+// accumulator still sees its own k-steps in the same order, so `out` is bit-identical to the kernels without the flag.
+// Every workgroup of a CS launch sums (four VALU instructions per phase; a second copy of the main loop for the others would cost more in
+// code than it saves) but only those of the first column tile store: their 256 partial sums go to the workspace behind the partial tiles, [split][row tile][256], and the reduce pass adds them in split order: no atomics, bitwise reproducible.
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+__device__ __forceinline__ float frag_pairsum(bf16x8 f, int c, float s) {      // s + f[2 c] + f[2 c + 1]
+  const bf16x2 ones = {(__bf16)1.0f, (__bf16)1.0f};
+  return __builtin_amdgcn_fdot2_f32_bf16((bf16x2){f[2 * c], f[2 * c + 1]}, ones, s, false);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Ping-pong form of the same GEMM (the production kernel since round 2).  PMC on the kernel above: MFMA pipe 28 % busy, waves
 // parked on s_waitcnt / s_barrier 57 % of their cycles (profiles/r02/a_baseline_pmc_mfma.json) - its one vmcnt(0) + barrier
@@ -52,9 +66,10 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* p) {
 // Past-the-end quarters are still "loaded" (range-checked to zeros, no traffic) so the vmcnt arithmetic is uniform.
 constexpr int QSLOT = 16 * 512 * 2;   // bytes of one quarter slot
 
-template <bool WS, int NQ, int D>
+template <bool WS, int NQ, int D, bool CS = false>
 __global__ __launch_bounds__(NW * 64) void gemm_tn_pp_kernel(const GemmTnArgs a, int tiles_p, int tiles_q, int splits) {
   static_assert(D >= 2 && D <= NQ - 2, "prefetch distance: WAR rule");
+  static_assert(!CS || WS, "column sums go through the workspace");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -99,7 +114,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_tn_pp_kernel(const GemmTnArgs a,
   int offA[MT], offB[NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    const int chunk = (wp * (BP / WP) + i * 32) / 8 + 2 * colhalf + (pp >> 1);
+    const int ip = CS ? (i + wq) & (MT - 1) : i;     // CS: p-tiles rotated by wq (frag_pairsum)
+    const int chunk = (wp * (BP / WP) + ip * 32) / 8 + 2 * colhalf + (pp >> 1);
     offA[i] = rowpart + ((chunk ^ (qq << 2)) << 4);
   }
 #pragma unroll
@@ -126,6 +142,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_tn_pp_kernel(const GemmTnArgs a,
   asm volatile("" ::: "memory");
   if (wp == 1) __builtin_amdgcn_s_barrier();        // second wave row runs one barrier behind from here on
   int slot_r = 0;
+  float csum = 0.f;                                 // CS: this lane's column of p-tile wq over its half of every quarter's rows
   for (int g = g_lo; g < g_hi; ++g) {
     // ---- read section
     const char* q = smem + slot_r * QSLOT;
@@ -151,7 +168,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_tn_pp_kernel(const GemmTnArgs a,
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < NT; ++j) {
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+        if constexpr (CS) { if (i * NT + j < 4) csum = frag_pairsum(af[0], i * NT + j, csum); }     // one dot product behind each of the first four MFMAs
+      }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -161,6 +181,15 @@ __global__ __launch_bounds__(NW * 64) void gemm_tn_pp_kernel(const GemmTnArgs a,
   if (wp == 0) __builtin_amdgcn_s_barrier();        // balance the stagger
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the past-the-end pieces (zeros) must not outlive the workgroup's LDS
 #undef VITAMD_WAIT_VM
+  int rot = wq;                                     // the p-tile rotation again, opaque: store addresses that depend on it are formed here, behind the
+  if constexpr (CS) asm volatile("" : "+s"(rot));   // main loop, not hoisted above it into registers the loop has none to spare of
+  if constexpr (CS) {
+    if (tile % tiles_q == 0) {                      // one set of column sums per row tile: the first column tile's
+      csum += __shfl_xor(csum, 32, 64);
+      float* wc = a.ws + (size_t)splits * ntile * (BP * BQ) + ((size_t)split * tiles_p + tile / tiles_q) * BP;
+      if (lane < 32) wc[wp * (BP / WP) + rot * 32 + lane] = csum;
+    }
+  }
 
   if constexpr (WS) {
     float* wt = a.ws + ((size_t)split * ntile + tile) * (BP * BQ);
@@ -169,6 +198,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_tn_pp_kernel(const GemmTnArgs a,
       const int ql = wq * (BQ / WQ) + j * 32 + (lane & 31);
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
+        if constexpr (CS) {
+          float* const wti = wt + ((i + rot) & (MT - 1)) * (32 * BQ);             // p-tile of fragment i: a wave-uniform step
+          const int pl = wp * (BP / WP) + 4 * (lane >> 5);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) wti[(pl + (r & 3) + 8 * (r >> 2)) * BQ + ql] = acc[i][j][r];
+          continue;
+        }
         const int pl = wp * (BP / WP) + i * 32 + 4 * (lane >> 5);
 #pragma unroll
         for (int r = 0; r < 16; ++r) wt[(pl + (r & 3) + 8 * (r >> 2)) * BQ + ql] = acc[i][j][r];
@@ -204,7 +240,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_tn_pp_kernel(const GemmTnArgs a,
 // the two input-gradient GEMMs: -0.1 ... -0.36 ms per step) and loses where the 8-wave form shared CUs with LayerNorm (all launches: +0.46 ms).
 // Round 4 (from the NT loader kernel where it was worth 5-14 %): the loaders issue half of a quarter's four requests behind the phase's first
 // barrier instead of all four in front of it, and run at priority 3 - a loader that is late for a barrier holds up all twelve waves.
-template <int NQ, int D>
+template <int NQ, int D, bool CS = false>
 __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int tiles_p, int tiles_q, int splits) {
   static_assert(D >= 2 && D <= NQ - 2, "prefetch distance: WAR rule");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -279,7 +315,8 @@ __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int
   int offA[MT], offB[NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    const int chunk = (wp * (BP / WP) + i * 32) / 8 + 2 * colhalf + (pp >> 1);
+    const int ip = CS ? (i + wq) & (MT - 1) : i;     // CS: p-tiles rotated by wq (frag_pairsum)
+    const int chunk = (wp * (BP / WP) + ip * 32) / 8 + 2 * colhalf + (pp >> 1);
     offA[i] = rowpart + ((chunk ^ (qq << 2)) << 4);
   }
 #pragma unroll
@@ -291,6 +328,7 @@ __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int
   asm volatile("" ::: "memory");
   if (wp == 1) __builtin_amdgcn_s_barrier();
   int slot_r = 0;
+  float csum = 0.f;
   for (int g = g_lo; g < g_hi; ++g) {
     const char* q = smem + slot_r * QSLOT;
     bf16x8 af[MT], bfr[NT];
@@ -306,7 +344,10 @@ __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < NT; ++j) {
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+        if constexpr (CS) { if (i * NT + j < 4) csum = frag_pairsum(af[0], i * NT + j, csum); }     // one dot product behind each of the first four MFMAs
+      }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -315,12 +356,28 @@ __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int
   }
   if (wp == 0) __builtin_amdgcn_s_barrier();
 #undef VITAMD_WAIT_VM
+  int rot = wq;                                     // the p-tile rotation again, opaque: store addresses that depend on it are formed here, behind the
+  if constexpr (CS) asm volatile("" : "+s"(rot));   // main loop, not hoisted above it into registers the loop has none to spare of
+  if constexpr (CS) {
+    if (tile % tiles_q == 0) {                      // one set of column sums per row tile: the first column tile's
+      csum += __shfl_xor(csum, 32, 64);
+      float* wc = a.ws + (size_t)splits * ntile * (BP * BQ) + ((size_t)split * tiles_p + tile / tiles_q) * BP;
+      if (lane < 32) wc[wp * (BP / WP) + rot * 32 + lane] = csum;
+    }
+  }
   float* wt = a.ws + ((size_t)split * ntile + tile) * (BP * BQ);
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int ql = wq * (BQ / WQ) + j * 32 + (lane & 31);
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
+      if constexpr (CS) {
+        float* const wti = wt + ((i + rot) & (MT - 1)) * (32 * BQ);             // p-tile of fragment i: a wave-uniform step
+        const int pl = wp * (BP / WP) + 4 * (lane >> 5);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) wti[(pl + (r & 3) + 8 * (r >> 2)) * BQ + ql] = acc[i][j][r];
+        continue;
+      }
       const int pl = wp * (BP / WP) + i * 32 + 4 * (lane >> 5);
 #pragma unroll
       for (int r = 0; r < 16; ++r) wt[(pl + (r & 3) + 8 * (r >> 2)) * BQ + ql] = acc[i][j][r];
@@ -330,8 +387,19 @@ __global__ __launch_bounds__(768) void gemm_tn_ld_kernel(const GemmTnArgs a, int
 
 // out[p][q] (+)= sum_s ws[s][tile][p_local][q_local]; RPT float4 per thread
 constexpr int RPT = 1;      // 4 is faster back to back (9.2 vs ~12 us) but slower inside the step (13.9 vs 12.0 us)
+// colsum: blocks blockIdx.y >= ntile (one per row tile, launched only with a colsum) add the splits' column-sum partials of L, in split order
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out, int P, int Q, int ldo,
-                                                            int tiles_q, int ntile, int splits, int accumulate) {
+                                                            int tiles_q, int ntile, int splits, int accumulate, float* __restrict__ colsum) {
+  if ((int)blockIdx.y >= ntile) {
+    static_assert(BP == 256, "one thread per column of a row tile");
+    const int tiles_p = ntile / tiles_q, tp = (int)blockIdx.y - ntile, p = tp * BP + (int)threadIdx.x;
+    if (blockIdx.x != 0 || p >= P) return;
+    const float* part = ws + (size_t)splits * ntile * (BP * BQ) + tp * BP + threadIdx.x;
+    float s = part[0];
+    for (int s2 = 1; s2 < splits; ++s2) s += part[(size_t)s2 * tiles_p * BP];
+    colsum[p] += s;
+    return;
+  }
   const int tile = blockIdx.y;
   const int p0 = (tile / tiles_q) * BP, q0 = (tile % tiles_q) * BQ;
   f32x4 sum[RPT];
@@ -379,7 +447,9 @@ static int auto_splits(int R, int P, int Q, int requested) {
 extern "C" long vitamd_gemm_tn_ws_bytes(int R, int P, int Q, int splits) {
   if (R <= 0 || P <= 0 || Q <= 0) return 0;
   const long ntile = (long)((P + BP - 1) / BP) * ((Q + BQ - 1) / BQ);
-  return (long)auto_splits(R, P, Q, splits) * ntile * BP * BQ * (long)sizeof(float);
+  const long tiles_p = (P + BP - 1) / BP;
+  // partial tiles, then the column-sum partials of L (256 floats per split and row tile; used by launches with a colsum)
+  return (long)auto_splits(R, P, Q, splits) * (ntile * BP * BQ + tiles_p * BP) * (long)sizeof(float);
 }
 
 int vitamd_gemm_tn_impl(const GemmTnArgs& a, hipStream_t stream) {
@@ -390,19 +460,29 @@ int vitamd_gemm_tn_impl(const GemmTnArgs& a, hipStream_t stream) {
   const int ntile = tiles_p * tiles_q;
   const int splits = auto_splits(a.R, a.P, a.Q, a.splits);
   constexpr int lds = 8 * QSLOT;                                  // the ring of eight quarter slots (= two 64-row stages)
-  const bool use_ws = a.ws != nullptr && a.ws_bytes >= (size_t)splits * ntile * BP * BQ * sizeof(float);
+  const size_t cs_bytes = a.colsum ? (size_t)splits * tiles_p * BP * sizeof(float) : 0;
+  const bool use_ws = a.ws != nullptr && a.ws_bytes >= (size_t)splits * ntile * BP * BQ * sizeof(float) + cs_bytes;
   if (!use_ws && !a.accumulate) return VITAMD_ERR_ARG;      // overwrite mode needs the workspace: the atomic form can only add to `out`
+  if (!use_ws && a.colsum) return VITAMD_ERR_ARG;           // ... and so do the column sums (their partials are summed by the reduce pass)
   const dim3 grid(ntile * splits), block(NW * 64);
   if (use_ws) {
     if (a.form == 1) {
-      if (int e = set_lds(gemm_tn_ld_kernel<8, 4>, lds)) return e;
-      hipLaunchKernelGGL((gemm_tn_ld_kernel<8, 4>), grid, dim3(768), lds, stream, a, tiles_p, tiles_q, splits);
+      if (a.colsum) {
+        if (int e = set_lds(gemm_tn_ld_kernel<8, 4, true>, lds)) return e;
+        hipLaunchKernelGGL((gemm_tn_ld_kernel<8, 4, true>), grid, dim3(768), lds, stream, a, tiles_p, tiles_q, splits);
+      } else {
+        if (int e = set_lds(gemm_tn_ld_kernel<8, 4>, lds)) return e;
+        hipLaunchKernelGGL((gemm_tn_ld_kernel<8, 4>), grid, dim3(768), lds, stream, a, tiles_p, tiles_q, splits);
+      }
+    } else if (a.colsum) {
+      if (int e = set_lds(gemm_tn_pp_kernel<true, 8, 4, true>, lds)) return e;
+      hipLaunchKernelGGL((gemm_tn_pp_kernel<true, 8, 4, true>), grid, block, lds, stream, a, tiles_p, tiles_q, splits);
     } else {
       if (int e = set_lds(gemm_tn_pp_kernel<true, 8, 4>, lds)) return e;
       hipLaunchKernelGGL((gemm_tn_pp_kernel<true, 8, 4>), grid, block, lds, stream, a, tiles_p, tiles_q, splits);
     }
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(BP * BQ / 4 / 256 / RPT, ntile), dim3(256), 0, stream, a.ws, a.out, a.P, a.Q, a.ldo, tiles_q, ntile, splits,
-                       a.accumulate);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(BP * BQ / 4 / 256 / RPT, ntile + (a.colsum ? tiles_p : 0)), dim3(256), 0, stream, a.ws, a.out, a.P, a.Q, a.ldo,
+                       tiles_q, ntile, splits, a.accumulate, a.colsum);
   } else {
     if (int e = set_lds(gemm_tn_pp_kernel<false, 8, 4>, lds)) return e;
     hipLaunchKernelGGL((gemm_tn_pp_kernel<false, 8, 4>), grid, block, lds, stream, a, tiles_p, tiles_q, splits);

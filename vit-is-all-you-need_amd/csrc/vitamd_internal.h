@@ -9,6 +9,8 @@ enum GemmEpilogue {
   EPI_DGELU = 3,      // out bf16 = bf16(bf16(acc) * gelu'(aux_bf16)); colsum[n] += column sums of out
   EPI_PATCH_F32 = 4,  // out f32[b*seq + extra + p] = bf16(acc + bias) + aux_f32[p]  (patch embed + pos_emb)
   EPI_F32 = 5,        // out f32 = acc
+  EPI_DGELU_NOCS = 6, // template argument of the seam / loader kernels only (never GemmNtArgs::epi): EPI_DGELU launched with colsum == null - the
+                      // column sums, their butterfly and the atomic compiled out (the bias gradient then comes from the weight-gradient GEMM)
 };
 
 // `tile` codes of the NT GEMM entry points (include/vitamd.h documents the numbers; they are part of the C ABI)
@@ -20,6 +22,7 @@ enum NtTileCode {
   NT_TILE_AUTO_NO_PERSISTENT = 512,   // auto without persistent launches
   NT_TILE_AUTO_NO_SEAM = 1024,        // auto with persistent launches but without the seam / loader forms
   NT_TILE_LOADER = 2048,              // the loader-wave form
+  NT_TILE_SEAM = 4096,                // the seam form on 256-row tiles
 };
 inline bool is_auto(int tile) { return tile == NT_TILE_AUTO || tile == NT_TILE_AUTO_NO_PERSISTENT || tile == NT_TILE_AUTO_NO_SEAM; }
 
@@ -56,6 +59,7 @@ struct GemmTnArgs {
   size_t ws_bytes;
   int accumulate;  // with a workspace: 1 = out += sum, 0 = out = sum (no pre-zeroing needed)
   int form;        // with a workspace: 0 = 8-wave ping-pong kernel, 1 = 12-wave loader form (VITAMD_TN_FORM_*)
+  float* colsum;   // optional, workspace form only: colsum[p] += sum_r L[r,p] (fp32 [P], caller-zeroed); partials behind the tiles in `ws`
 };
 
 int vitamd_gemm_nt_impl(const GemmNtArgs& p, hipStream_t stream);

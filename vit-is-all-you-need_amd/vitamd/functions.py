@@ -384,6 +384,15 @@ def grad_arena(D, n_layers, device, params=None):
     return out, None
 
 
+BIAS_FROM_WGRAD = True    # the fc1 and fc2 bias gradients of a layer are column sums of the L operand of its own weight-gradient GEMMs (dpre, dy2), so those
+                          # GEMMs form them (ops.gemm_tn(colsum=): beside the MFMAs, on the side stream, summed in a fixed order) instead of the kernels
+                          # on the main stream's critical path: dgrad-fc2's epilogue (column sums, butterfly and one atomic per wave and tile), the
+                          # column-sum form of the LayerNorm backward of the layer above, ops.colsum for the top layer.  False: those producers (tests, A/B).
+                          # DESIGN.md section 4.9.
+
+BIAS_QKV_FROM_WGRAD = True    # the same for the QKV bias gradient (attention backward without its dbias atomics, colsum on the dWqkv GEMM): the part of the
+                              # change the whole-step A/B credits with most of the gain (profiles/bias_from_wgrad/gpu_visit.md).  False: tests, A/B.
+
 KEEP_WGRAD_SIDE = True    # the kept-row layer's two MLP weight gradients (R = B*keep rows: a few microseconds each) go to the side stream like every other
                           # weight gradient (True) or stay on the main stream (False).  Whole-step A/B in profiles/last_layer_keep/gpu_visit.md.
 
@@ -396,6 +405,8 @@ def layer_backward(g2, saved, wqkv, w1, w2, B, N, H, causal, grads, dy2=None, ha
     have_db2).  emit_bf16/emit_colsum: also produce bf16(g0) and add its column sums to emit_colsum
     (the fc2 bias gradient of the layer below); emit_dropout = that layer's fc2 dropout (p, seed), whose
     mask the emitted copy must carry.  drop = this layer's dropout record from layer_forward.
+    With BIAS_FROM_WGRAD, db2 and db1 come from this layer's own weight-gradient GEMMs (the masked dy2 is their operand, so the sum keeps
+    the dropout mask): have_db2 and emit_colsum are then ignored - no kernel of the layer above or below adds to a bias gradient.
     keep: the layer ran layer_forward(keep=): g2 is COMPACT fp32 [B*keep, D].  The MLP's gradients, LN2 backward and the attention's dO run
     on the B*keep kept rows; gradients become dense in the attention backward (every key's dK / dV receives from the kept queries), and
     the first LayerNorm's backward takes its residual gradient compact."""
@@ -429,28 +440,36 @@ def layer_backward(g2, saved, wqkv, w1, w2, B, N, H, causal, grads, dy2=None, ha
     if dy2 is None:
         dy2 = ops.cast_bf16_dropout(g2, drop[2:]) if drop[2] > 0 else ops.cast_bf16(g2)
     # ---- MLP
+    from_wgrad = BIAS_FROM_WGRAD
+    if from_wgrad:
+        emit_colsum = None
+
     def wgrad_fc2():
-        ops.gemm_tn(dy2, h, dW2, accumulate=False, splits=_tn_splits(dW2, R_mlp), form=_tn_form("fc2"))
-        if not have_db2:
+        ops.gemm_tn(dy2, h, dW2, accumulate=False, splits=_tn_splits(dW2, R_mlp), form=_tn_form("fc2"), colsum=db2 if from_wgrad else None)
+        if not from_wgrad and not have_db2:
             ops.colsum(dy2, db2)
     # the MLP weight gradients enter the side stream as soon as their inputs exist, beside the input-gradient GEMMs (holding them back until
     # after dgrad-fc1, beside LayerNorm / attention backward, measured equal or up to 0.4 ms slower: DESIGN.md section 4)
     on_side_mlp(wgrad_fc2, dy2, h, dW2, db2)
-    dpre = ops.gemm_nt(dy2, w2_t, ops.EPI_DMUL, aux=pre, colsum=db1)             # dgrad fc2 . gelu' (stored by the forward in `pre`)
-    on_side_mlp(lambda: ops.gemm_tn(dpre, bln, dW1, accumulate=False, splits=_tn_splits(dW1, R_mlp), form=_tn_form("fc1")), dpre, bln, dW1)
+    dpre = ops.gemm_nt(dy2, w2_t, ops.EPI_DMUL, aux=pre, colsum=None if from_wgrad else db1)      # dgrad fc2 . gelu' (stored by the forward in `pre`)
+    on_side_mlp(lambda: ops.gemm_tn(dpre, bln, dW1, accumulate=False, splits=_tn_splits(dW1, R_mlp), form=_tn_form("fc1"),
+                                    colsum=db1 if from_wgrad else None), dpre, bln, dW1, db1)
     dbln = ops.gemm_nt(dpre, w1_t, ops.EPI_BIAS_BF16)                            # dgrad fc1
     # LayerNorm backward reads xhat from the saved bf16 LN output instead of recomputing it from fp32 x
     g1, d_o = ops.layernorm_bwd(dbln, x1, mean2, rstd2, g_res=g2, want_bf16=True, xhat=bln)       # (kept-row layer: B*keep rows, all compact)
     # ---- attention
+    qkv_from_wgrad = BIAS_QKV_FROM_WGRAD
+    dbias = None if qkv_from_wgrad else dbqkv
     if keep is None:
-        dqkv = ops.attention_bwd(qkv, o, lse, d_o, B, N, H, causal, dbias=dbqkv, dropout=drop[:2])   # also adds the QKV bias gradient
+        dqkv = ops.attention_bwd(qkv, o, lse, d_o, B, N, H, causal, dbias=dbias, dropout=drop[:2])   # also adds the QKV bias gradient
     elif _keep_native(N, keep):
-        dqkv = ops.attention_bwd_keep(qkv, o, lse, d_o, B, N, H, keep, dbias=dbqkv)             # compact o / dO in, dense dqkv out
+        dqkv = ops.attention_bwd_keep(qkv, o, lse, d_o, B, N, H, keep, dbias=dbias)             # compact o / dO in, dense dqkv out
     else:
         d_o_full = torch.zeros((B, N, d_o.shape[1]), dtype=BF16, device=d_o.device)            # shapes without a kept-query kernel: zero-padded dO
         d_o_full[:, :keep] = d_o.view(B, keep, -1)
-        dqkv = ops.attention_bwd(qkv, o, lse, d_o_full.view(B * N, -1), B, N, H, causal, dbias=dbqkv)
-    on_side(lambda: ops.gemm_tn(dqkv, a, dWqkv, accumulate=False, splits=_tn_splits(dWqkv), form=_tn_form("qkv")), dqkv, a, dWqkv)
+        dqkv = ops.attention_bwd(qkv, o, lse, d_o_full.view(B * N, -1), B, N, H, causal, dbias=dbias)
+    on_side(lambda: ops.gemm_tn(dqkv, a, dWqkv, accumulate=False, splits=_tn_splits(dWqkv), form=_tn_form("qkv"),
+                                colsum=dbqkv if qkv_from_wgrad else None), dqkv, a, dWqkv, dbqkv)
     da = ops.gemm_nt(dqkv, wqkv_t, ops.EPI_BIAS_BF16)                            # dgrad qkv
     g0, g0b = ops.layernorm_bwd(da, x0, mean1, rstd1, g_res=g1, want_bf16=emit_bf16, colsum=emit_colsum, dropout=emit_dropout,
                                 xhat=a, keep=None if keep is None else (N, keep))
@@ -579,8 +598,10 @@ class TransformerStackFn(torch.autograd.Function):
                                           drop=ctx.drops[i], emit_dropout=ctx.drops[i - 1][2:] if i > 0 else (0.0, 0),
                                           keep=k_last if i + 1 == L else None)
                 if sink is not None:
-                    # bucket i is complete now: five gradients from this call, and its fc2 bias gradient was
-                    # added by layer i+1's LN1 backward (or by this call's own column sum for the top layer)
+                    # bucket i is complete now: with BIAS_FROM_WGRAD all six gradients are this call's own (the bias gradients of fc1 and
+                    # fc2 are enqueued on the side stream with their weight-gradient GEMMs, which layer_ready orders the reduction behind);
+                    # without it five are, and the fc2 bias gradient was added by layer i+1's LN1 backward (or by this call's own column
+                    # sum for the top layer)
                     sink.layer_ready(params, i)
                 side_checkpoint(cur.device)
         finally:

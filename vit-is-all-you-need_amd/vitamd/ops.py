@@ -170,25 +170,37 @@ def _workspace(device, nbytes):
 TN_FORM_SHARED, TN_FORM_EXCLUSIVE = 0, 1      # include/vitamd.h VITAMD_TN_FORM_*
 
 
-def gemm_tn(l, r, out, splits=0, accumulate=True, atomic=False, form=TN_FORM_SHARED):
+def gemm_tn(l, r, out, splits=0, accumulate=True, atomic=False, form=TN_FORM_SHARED, colsum=None):
     """out[P,Q] (fp32) (+)= l[R,P]^T @ r[R,Q].  Split-K partials go through a workspace + reduce
     pass (reproducible) unless atomic=True (fp32 atomics straight into `out`, accumulate only).
     form: TN_FORM_SHARED (8-wave workgroups that leave room on the CU for another stream's LayerNorm waves) or TN_FORM_EXCLUSIVE (12 waves,
-    four of them dedicated to the LDS-DMA requests: 15 % faster alone, fills the CU); bit-identical results."""
+    four of them dedicated to the LDS-DMA requests: 15 % faster alone, fills the CU); bit-identical results.
+    colsum: fp32 [P], ADDED to: the column sums of l (the bias gradient that goes with this weight gradient), formed beside the MFMAs
+    from the tiles the GEMM stages anyway and summed by the reduce pass in a fixed order; `out` does not change by a bit.  Not with atomic=True."""
     _need(l, BF16, "l", 2); _need(r, BF16, "r", 2); _need(out, F32, "out", 2)
     R, P = l.shape
     R2, Q = r.shape
     if R != R2 or tuple(out.shape) != (P, Q):
         raise _lib.VitamdError("gemm_tn: shape mismatch")
+    if colsum is not None:
+        _need(colsum, F32, "colsum", 1)
+        if colsum.numel() != P:
+            raise _lib.VitamdError("gemm_tn: colsum must be fp32 [P]")
     if atomic:
         if not accumulate:
             raise _lib.VitamdError("gemm_tn: the atomic form can only accumulate")
+        if colsum is not None:
+            raise _lib.VitamdError("gemm_tn: the atomic form has no reduce pass to sum colsum in")
         code = _L().vitamd_gemm_tn_bf16(_p(l), _p(r), _p(out), R, P, Q, P, Q, Q, splits, _stream())
     else:
         nbytes = _L().vitamd_gemm_tn_ws_bytes(R, P, Q, splits)
         ws = _workspace(l.device, nbytes)
-        code = _L().vitamd_gemm_tn_bf16_ws(_p(l), _p(r), _p(out), R, P, Q, P, Q, Q, splits, _p(ws), ws.numel() * 4, int(accumulate),
-                                           int(form), _stream())
+        if colsum is not None:
+            code = _L().vitamd_gemm_tn_bf16_ws_colsum(_p(l), _p(r), _p(out), _p(colsum), R, P, Q, P, Q, Q, splits, _p(ws), ws.numel() * 4,
+                                                      int(accumulate), int(form), _stream())
+        else:
+            code = _L().vitamd_gemm_tn_bf16_ws(_p(l), _p(r), _p(out), R, P, Q, P, Q, Q, splits, _p(ws), ws.numel() * 4, int(accumulate),
+                                               int(form), _stream())
     _lib.check(code, f"gemm_tn[R={R},P={P},Q={Q}]")
     return out
 
