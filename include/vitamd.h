@@ -385,6 +385,41 @@ int vitamd_mt_adamw(const vitamd_mt_row* rows_host, const void* rows_dev, int n_
 /* g *= *coef in place (coef required); stores nothing when *coef == 1.  Uses g alone.  For clipping in front of another optimiser. */
 int vitamd_mt_scale(const vitamd_mt_row* rows_host, const void* rows_dev, int n_rows, int total_chunks, const float* coef, void* stream);
 
+/* ---- training the image tokenizers -------------------------------------
+ * Every call only enqueues on `stream`; none allocates or synchronises; scalars are read from and written to device memory.
+ *
+ * The cosine-similarity quantiser of train_titok.py:50-59 / train_vit_vqgan.py:49-58, narrow codes (1 <= d <= 64, K >= 1; anything else
+ * VITAMD_ERR_SHAPE), fp32 throughout, eps = 1e-12 as F.normalize:
+ *   unit[m,:] = u = x / max(|x|, eps), rnorm[m] = 1 / max(|x|, eps) (exactly 1/eps marks a clamped row);
+ *   idx[m]    = first argmin_k |u - e^_k|^2 over e^_k = e_k / max(|e_k|, eps), by the arithmetic and tie-break of vitamd_vq_nearest;
+ *   q[m,:]    = u + (p - u) with p = codebook[idx[m],:], the RAW row;  *loss = 1.25 * mean over M*d of (p - u)^2.
+ * ws: vitamd_vq_quantize_ws_bytes(M, K, d) bytes of scratch (negative: the shape error).  Its first K*d floats hold e^ after the call.
+ * The loss is summed from per-workgroup partials in a fixed order: the same inputs give the same bits. */
+long vitamd_vq_quantize_ws_bytes(int M, int K, int d);
+int vitamd_vq_quantize_fwd(const float* x, const float* codebook, float* unit, float* rnorm, float* q, long long* idx, float* loss, float* ws,
+                           int M, int K, int d, void* stream);
+/* g_q fp32 [M,d] or NULL (the gradient of q), g_loss DEVICE fp32 or NULL (the gradient of the loss, s; NULL = 0):
+ *   du = g_q + 0.5 s (u - p) / (M d);  dx = (du - u (u . du)) * rnorm, or du / eps for a clamped row (overwritten);
+ *   dcodebook[idx[m],:] += 2 s (p - u) / (M d)   (ACCUMULATED into: zero it for a fresh gradient; nothing from g_q).
+ * Rows of one workgroup that share a code are summed on chip in row order, then added by one fp32 atomic per element: dcodebook depends
+ * on arrival order in its last bits where a code is picked in more than one 256-row block; dx never does.
+ * An idx outside [0, K): that row's dx is zero and it adds nothing. */
+int vitamd_vq_quantize_bwd(const float* g_q, const float* g_loss, const float* unit, const float* rnorm, const long long* idx,
+                           const float* codebook, float* dx, float* dcodebook, int M, int K, int d, void* stream);
+
+/* mse_loss(pixel_shuffle(y), img) without the image-shaped copy of y: y = tokens [B*G*G, F = p*p*c] with row stride ld (elements; columns
+ * F .. ld are never read or written), bf16 (y_bf16 != 0) or fp32; img fp32 [B, c, G*p, G*p] contiguous;
+ *   *loss = mean over b, ch, gh, p1, gw, p2 of (float(y[b*G*G + gh*G + gw, (p1*p + p2)*c + ch]) - img[b, ch, gh*p + p1, gw*p + p2])^2
+ * (the index map of 'b (h w) (p1 p2 c) -> b c (h p1) (w p2)', train_titok.py:73-75).  Only a 16-byte path exists: y 16-byte aligned, ld and
+ * F multiples of 8 (bf16) or 4 (fp32), one token within 48 KiB - anything else VITAMD_ERR_SHAPE, for the caller to take another route.
+ * ws: vitamd_recon_mse_ws_bytes(...) bytes (negative: the shape error); one partial per workgroup, summed in a fixed order (reproducible). */
+long vitamd_recon_mse_ws_bytes(int B, int G, int p, int c, int y_bf16);
+int vitamd_recon_mse_fwd(const void* y, int y_bf16, const float* img, float* loss, float* ws, int B, int G, int p, int c, int ld, void* stream);
+/* dy = 2 (float(y) - img) * (*grad_out) / (B c H W) in token layout and in y's type (bf16: one round-to-nearest-even), row stride ld_dy;
+ * grad_out: DEVICE fp32 or NULL (= 1).  dy == y (with ld_dy == ld) overwrites the tokens in place. */
+int vitamd_recon_mse_bwd(const void* y, int y_bf16, const float* img, const float* grad_out, void* dy, int B, int G, int p, int c, int ld,
+                         int ld_dy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,13 +5,16 @@ the same constructor signatures, attributes and state_dict keys (`enc.vit.*`, `e
 projections and the nearest-code search run on libvitamd kernels; the O(tokens x latent_dim)
 elementwise glue of the quantiser (L2 normalise, the two MSE terms, the straight-through add) and the
 pure data movement (token slicing, pixel shuffle) are torch device ops."""
+import argparse
+import time
 from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 
 from train_vit import ViT, ViTConfig
-from vitamd import ops
+from utils import get_lr_scheduler
+from vitamd import ops, tokenizer
 from vitamd.functions import linear
 
 
@@ -94,11 +97,14 @@ class TiTokDecoder(nn.Module):
         self.quant_proj = HipLinear(titok_config.latent_dim, titok_config.n_embd)
         self.embd_proj = HipConv1x1(titok_config.n_embd, 3 * titok_config.patch_size ** 2, kernel_size=1)
 
-    def forward(self, z):
+    def features(self, z):
+        """quantised latents -> the decoder ViT's output at the image patches [b, n_patches, n_embd], before the pixel head"""
         z = self.quant_proj(z)                                   # [b, latents, n_embd]
         z = z.transpose(1, 2).unsqueeze(-1)                      # 'b h c -> b c h 1'
-        out_embd = self.vit(z, keep=self.config.n_patches)       # mask tokens come first (extra tokens): [:, :n_patches]
-        return pixel_shuffle_tokens(self.embd_proj(out_embd), self.config.patch_dim, self.config.patch_size)
+        return self.vit(z, keep=self.config.n_patches)           # mask tokens come first (extra tokens): [:, :n_patches]
+
+    def forward(self, z):
+        return pixel_shuffle_tokens(self.embd_proj(self.features(z)), self.config.patch_dim, self.config.patch_size)
 
 
 class TiTok(nn.Module):
@@ -124,3 +130,94 @@ class TiTok(nn.Module):
         """-> (reconstruction [b, 3, H, W], code ids, quantiser loss)"""
         tokens, ids, qloss = self.quant(self.enc(x))
         return self.dec(tokens), ids, qloss
+
+    def loss(self, x):
+        """-> (reconstruction loss mse(recon, x), quantiser loss, code ids) on the fused route (vitamd.tokenizer):
+        encoder -> vq_quantize -> quant_proj -> decoder ViT -> linear_recon_mse on embd_proj's parameters.  No reconstruction image is
+        formed; forward() stays the route that yields one."""
+        return tokenizer_loss(self.enc, self.quant, self.dec, x)
+
+
+def tokenizer_loss(enc, quant, dec, x):
+    """the loss route shared by TiTok and ViTVQGAN (their decoders both have features(), embd_proj and config)"""
+    tokens, ids, qloss = tokenizer.vq_quantize(enc(x), quant.codebook.weight)
+    recon = tokenizer.linear_recon_mse(dec.features(tokens), dec.embd_proj.weight, dec.embd_proj.bias, x, dec.config.patch_dim, dec.config.patch_size)
+    return recon, qloss, ids
+
+
+def train_step(model, images, optim, lr_sched=None, perceptual=None, perceptual_weight=1.0):
+    """One iteration of the reference hot loop (train_titok.py:151-163) without the fp16 scaler, on model.loss: the pixel term is the mean
+    squared error.  perceptual: a callable (recon, images) -> per-image values (the reference's LPIPS network, which is not part of this
+    package): the step then runs model(images), which yields the image, and adds perceptual_weight * perceptual(recon, images).mean().
+    The reference clips the gradients AFTER the optimiser step, where the clip changes no update; this step does not clip.
+    -> the detached device loss"""
+    optim.zero_grad(set_to_none=True)
+    if perceptual is None:
+        recon_loss, qloss, _ = model.loss(images)
+    else:
+        recon, _, qloss = model(images)
+        recon_loss = torch.nn.functional.mse_loss(recon, images) + perceptual_weight * perceptual(recon, images).mean()
+    loss = recon_loss + qloss
+    loss.backward()
+    optim.step()
+    if lr_sched is not None:
+        lr_sched.step()
+    return loss.detach()
+
+
+def add_common_args(p):
+    p.add_argument("--image_size", type=int, default=128)
+    p.add_argument("--patch_size", type=int, default=16)
+    p.add_argument("--codebook_size", type=int, default=2048)
+    p.add_argument("--latent_dim", type=int, default=12)
+    p.add_argument("--transformer", type=str, default="B")
+    p.add_argument("--bs", type=int, default=32)
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--weight_decay", type=float, default=1e-4)
+    p.add_argument("--warmup_steps", type=int, default=5000)
+    p.add_argument("--train_steps", type=int, default=50)
+    p.add_argument("--max_grad_norm", type=float, default=None,
+                   help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
+    return p
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="TiTok training on synthetic images (MI355X-native path)")
+    p.add_argument("--latent_tokens", type=int, default=256)
+    return add_common_args(p).parse_args(argv)
+
+
+def make_optim(model, args):
+    if args.max_grad_norm is None:
+        return torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    from vitamd.optim import AdamW
+    return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
+
+
+def run(model, args, codebook_size):
+    """the training loop of both tokenizers on one seeded batch of random images in [0, 1], with the reference's codebook-usage counter"""
+    dev = torch.device("cuda")
+    model = model.to(dev)
+    optim = make_optim(model, args)
+    sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    images = torch.rand((args.bs, 3, args.image_size, args.image_size), generator=g).to(dev)
+    usage = torch.zeros([codebook_size], device=dev)
+    for step in range(args.train_steps):
+        t0 = time.time()
+        loss = train_step(model, images, optim, sched)
+        with torch.no_grad():
+            usage[model.encode(images)] = 1
+        torch.cuda.synchronize()
+        print(f"step {step} loss {loss.item():.4f} codebook_usage {usage.sum().item() / codebook_size:.3f} "
+              f"{args.bs / (time.time() - t0):.1f} images/s")
+
+
+def main():
+    args = parse_args()
+    cfg = TiTokConfig(args.image_size, args.patch_size, args.latent_tokens, args.codebook_size, args.latent_dim, args.transformer)
+    run(TiTok(cfg), args, cfg.codebook_size)
+
+
+if __name__ == "__main__":
+    main()

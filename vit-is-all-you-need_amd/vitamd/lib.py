@@ -77,6 +77,12 @@ SIGNATURES = {
     "vitamd_cross_entropy_bwd": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _P],
     "vitamd_embed_tokens_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_embed_tokens_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vitamd_vq_quantize_ws_bytes": [_I, _I, _I],
+    "vitamd_vq_quantize_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "vitamd_vq_quantize_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "vitamd_recon_mse_ws_bytes": [_I, _I, _I, _I, _I],
+    "vitamd_recon_mse_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vitamd_recon_mse_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
 }
 
 ERRORS = {1: "unsupported shape", 2: "bad argument", 3: "HIP launch failure", 4: "vitamd_init has not run for this device"}

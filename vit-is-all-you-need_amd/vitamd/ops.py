@@ -809,3 +809,118 @@ def embed_tokens_bwd(g, ids, dtok, dpos):
     _lib.check(_L().vitamd_embed_tokens_bwd(_p(g), _p(ids), _p(dtok), _p(dpos), B, S, D, dtok.shape[0], _stream()),
                f"embed_tokens_bwd[B={B},S={S},D={D}]")
     return dtok, dpos
+
+
+# ------------------------------------------------------------------------------------------ training the image tokenizers
+VQ_MAX_D = 64             # include/vitamd.h vitamd_vq_quantize_fwd: wider codes stay on vq_nearest and the torch expressions
+
+
+def _need_vq(x, codebook, what):
+    """x fp32 [M, d], codebook fp32 [K, d], 1 <= d <= VQ_MAX_D (shape errors before any device is looked at) -> (M, K, d)"""
+    if not isinstance(x, torch.Tensor) or not isinstance(codebook, torch.Tensor) or x.dim() != 2 or codebook.dim() != 2:
+        raise _lib.VitamdError(f"{what}: expected x [M, d] and codebook [K, d]")
+    (M, d), (K, d2) = x.shape, codebook.shape
+    if d != d2 or not 1 <= d <= VQ_MAX_D or M < 1 or K < 1:
+        raise ValueError(f"{what}: needs M >= 1 rows, K >= 1 codes and one code width 1 .. {VQ_MAX_D}, got x {tuple(x.shape)}, "
+                         f"codebook {tuple(codebook.shape)}")
+    _need(x, F32, "x", 2); _need(codebook, F32, "codebook", 2)
+    return M, K, d
+
+
+def vq_quantize_fwd(x, codebook, return_unit_codes=False):
+    """The cosine-similarity quantiser forward (include/vitamd.h vitamd_vq_quantize_fwd): x fp32 [M, d], codebook fp32 [K, d] ->
+    (unit [M, d], rnorm [M], q [M, d], idx int64 [M], loss fp32 0-dim); return_unit_codes: the unit codebook the search used as a sixth."""
+    M, K, d = _need_vq(x, codebook, "vq_quantize_fwd")
+    dev = x.device
+    unit, q = torch.empty((M, d), dtype=F32, device=dev), torch.empty((M, d), dtype=F32, device=dev)
+    rnorm = torch.empty((M,), dtype=F32, device=dev)
+    idx = torch.empty((M,), dtype=torch.int64, device=dev)
+    loss = torch.empty((), dtype=F32, device=dev)
+    ws = torch.empty((int(_L().vitamd_vq_quantize_ws_bytes(M, K, d)) // 4,), dtype=F32, device=dev)
+    _lib.check(_L().vitamd_vq_quantize_fwd(_p(x), _p(codebook), _p(unit), _p(rnorm), _p(q), _p(idx), _p(loss), _p(ws), M, K, d, _stream()),
+               f"vq_quantize_fwd[M={M},K={K},d={d}]")
+    return (unit, rnorm, q, idx, loss) + ((ws[:K * d].view(K, d),) if return_unit_codes else ())
+
+
+def vq_quantize_bwd(g_q, g_loss, unit, rnorm, idx, codebook, dcodebook=None):
+    """-> (dx fp32 [M, d], dcodebook fp32 [K, d]).  g_q fp32 [M, d] or None, g_loss device fp32 scalar or None; dcodebook is accumulated
+    into when given (else a zeroed one is made).  Semantics: include/vitamd.h vitamd_vq_quantize_bwd."""
+    M, K, d = _need_vq(unit, codebook, "vq_quantize_bwd")
+    _need(rnorm, F32, "rnorm", 1); _need(idx, torch.int64, "idx", 1)
+    if rnorm.numel() != M or idx.numel() != M:
+        raise _lib.VitamdError(f"vq_quantize_bwd: expected rnorm [{M}] and idx [{M}]")
+    if g_q is not None:
+        _need(g_q, F32, "g_q", 2)
+        if tuple(g_q.shape) != (M, d):
+            raise _lib.VitamdError(f"g_q: expected [{M}, {d}], got {tuple(g_q.shape)}")
+    if g_loss is not None:
+        _need(g_loss, F32, "g_loss")
+        if g_loss.numel() != 1:
+            raise _lib.VitamdError("g_loss: expected a one-element device fp32")
+    if dcodebook is None:
+        dcodebook = torch.zeros((K, d), dtype=F32, device=unit.device)
+    _need(dcodebook, F32, "dcodebook", 2)
+    if tuple(dcodebook.shape) != (K, d):
+        raise _lib.VitamdError(f"dcodebook: expected [{K}, {d}], got {tuple(dcodebook.shape)}")
+    dx = torch.empty((M, d), dtype=F32, device=unit.device)
+    _lib.check(_L().vitamd_vq_quantize_bwd(_p(g_q), _p(g_loss), _p(unit), _p(rnorm), _p(idx), _p(codebook), _p(dx), _p(dcodebook), M, K, d,
+                                           _stream()), f"vq_quantize_bwd[M={M},K={K},d={d}]")
+    return dx, dcodebook
+
+
+def recon_mse_applies(tokens, F=None):
+    """whether the reconstruction-loss kernels take these tokens (their 16-byte path: aligned base, F and the row stride multiples of 8
+    bf16 / 4 fp32 elements, one token within 48 KiB); callers take the torch expressions otherwise"""
+    if not isinstance(tokens, torch.Tensor) or tokens.dim() != 2 or tokens.dtype not in (F32, BF16) or tokens.stride(1) != 1:
+        return False
+    F = tokens.shape[1] if F is None else F
+    w = 8 if tokens.dtype == BF16 else 4
+    return (F % w == 0 and tokens.stride(0) % w == 0 and tokens.stride(0) >= F and tokens.data_ptr() % 16 == 0
+            and F * tokens.element_size() <= 48 * 1024)
+
+
+def _need_recon(tokens, images, grid, patch, what):
+    """tokens fp32 / bf16 [B*grid*grid, patch*patch*c] (unit inner stride), images fp32 [B, c, grid*patch, grid*patch] contiguous ->
+    (B, c, ld, is_bf16); shape errors before any device is looked at"""
+    if not isinstance(tokens, torch.Tensor) or not isinstance(images, torch.Tensor) or tokens.dim() != 2 or images.dim() != 4:
+        raise _lib.VitamdError(f"{what}: expected tokens [B*grid*grid, patch*patch*c] and images [B, c, H, W]")
+    B, c, H, Wd = images.shape
+    if grid < 1 or patch < 1 or B < 1 or c < 1 or H != grid * patch or Wd != grid * patch or tuple(tokens.shape) != (B * grid * grid, patch * patch * c):
+        raise ValueError(f"{what}: tokens {tuple(tokens.shape)} and images {tuple(images.shape)} do not fit grid {grid}, patch {patch}")
+    _need(images, F32, "images", 4)
+    if not tokens.is_cuda:
+        raise _lib.VitamdError(f"{what}: expected ROCm device tensors (the HIP kernels are the only implementation)")
+    if tokens.dtype not in (F32, BF16) or tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1]:
+        raise _lib.VitamdError(f"{what}: tokens must be fp32 or bf16 with unit inner stride, got {tokens.dtype} strides {tokens.stride()}")
+    return B, c, tokens.stride(0), int(tokens.dtype == BF16)
+
+
+def recon_mse_fwd(tokens, images, grid, patch):
+    """mean((pixel_shuffle(tokens) - images)^2) as a 0-dim device fp32, the image-shaped tensor never formed (include/vitamd.h
+    vitamd_recon_mse_fwd).  Shapes outside the kernel's 16-byte path raise (recon_mse_applies tells beforehand)."""
+    B, c, ld, is_bf16 = _need_recon(tokens, images, grid, patch, "recon_mse_fwd")
+    nbytes = int(_L().vitamd_recon_mse_ws_bytes(B, grid, patch, c, is_bf16))
+    _lib.check(-nbytes if nbytes < 0 else 0, f"recon_mse_fwd[B={B},G={grid},p={patch},c={c}]")
+    ws = torch.empty((nbytes // 4,), dtype=F32, device=tokens.device)
+    loss = torch.empty((), dtype=F32, device=tokens.device)
+    _lib.check(_L().vitamd_recon_mse_fwd(_p(tokens), is_bf16, _p(images), _p(loss), _p(ws), B, grid, patch, c, ld, _stream()),
+               f"recon_mse_fwd[B={B},G={grid},p={patch},c={c},ld={ld}]")
+    return loss
+
+
+def recon_mse_bwd(tokens, images, grid, patch, grad_out=None, out=None):
+    """d loss / d tokens = 2 (tokens - pixel_unshuffle(images)) * grad_out / images.numel(), in the tokens' layout and dtype.  grad_out:
+    device fp32 scalar (None = 1).  out: where to write (`tokens` itself = in place); None allocates a dense tensor."""
+    B, c, ld, is_bf16 = _need_recon(tokens, images, grid, patch, "recon_mse_bwd")
+    if grad_out is not None:
+        _need(grad_out, F32, "grad_out")
+        if grad_out.numel() != 1:
+            raise _lib.VitamdError("grad_out: expected a one-element device fp32")
+    if out is None:
+        out = torch.empty(tuple(tokens.shape), dtype=tokens.dtype, device=tokens.device)
+    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != tokens.dtype or tuple(out.shape) != tuple(tokens.shape)
+            or out.stride(1) != 1 or out.stride(0) < out.shape[1]):
+        raise _lib.VitamdError("recon_mse_bwd: out must be a device tensor of the tokens' shape and dtype with unit inner stride")
+    _lib.check(_L().vitamd_recon_mse_bwd(_p(tokens), is_bf16, _p(images), _p(grad_out), _p(out), B, grid, patch, c, ld, out.stride(0), _stream()),
+               f"recon_mse_bwd[B={B},G={grid},p={patch},c={c},ld={ld}]")
+    return out
