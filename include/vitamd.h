@@ -420,6 +420,41 @@ int vitamd_recon_mse_fwd(const void* y, int y_bf16, const float* img, float* los
 int vitamd_recon_mse_bwd(const void* y, int y_bf16, const float* img, const float* grad_out, void* dy, int B, int G, int p, int c, int ld,
                          int ld_dy, void* stream);
 
+/* ---- the ConvNeXt-S perceptual loss of the tokenizers ---------------------
+ * The frozen network of perceptual_loss.py:41 runs on channels-last activation rows [B*H*W, C]: its Linears, LayerNorms and strided
+ * convolutions are vitamd_gemm_nt_bf16 / vitamd_layernorm_affine_* calls; the entry points below are the rest.  Every call only enqueues
+ * on `stream`; none allocates or synchronises; no atomics: the same inputs give the same bits.  (Added to ABI 9: no signature changed.)
+ *
+ * Depthwise 7x7 convolution, stride 1, zero padding 3 (the first layer of a torchvision CNBlock, `nn.Conv2d(dim, dim, 7, padding=3,
+ * groups=dim)`, reached from perceptual_loss.py:63-64), on rows:
+ *   y[b,h,w,c] = bias[c] + sum_{kh,kw} w[c,kh,kw] * x[b,h+kh-3,w+kw-3,c]       x, y: [B,H,W,C], w fp32 [C,7,7], bias fp32 [C] or NULL.
+ * x is fp32, or bf16 when x_bf16 != 0; y is fp32; accumulation is fp32 in the order kh, then input column.  C % 4 == 0, B, H, W >= 1 (maps
+ * smaller than the window are fine), fewer than 2^40 elements, else VITAMD_ERR_SHAPE; a missing pointer VITAMD_ERR_ARG. */
+int vitamd_dwconv7_fwd(const void* x, int x_bf16, const float* w, const float* bias, float* y, int B, int H, int W, int C, void* stream);
+/* Its input gradient, the same kernel body on the reversed taps:
+ *   dx[b,h,w,c] = (add ? add[b,h,w,c] : 0) + sum_{kh,kw} w[c,kh,kw] * dy[b,h+3-kh,w+3-kw,c]
+ * add (fp32 rows, may be NULL, must not be dy): the gradient that reaches the block's input along the residual branch, added in the
+ * store.  dx may not alias dy.  The network is frozen: there is no weight gradient.  replaces the autograd backward of that Conv2d. */
+int vitamd_dwconv7_bwd(const void* dy, int dy_bf16, const float* w, const float* add, float* dx, int B, int H, int W, int C, void* stream);
+
+/* `F.interpolate(img, size=S, mode="bilinear", align_corners=False, antialias=True)` followed by `(x - mean) / std`
+ * (perceptual_loss.py:61-64) on img fp32 [B,3,Hin,Win] (C != 3: VITAMD_ERR_SHAPE), S % 4 == 0.  The resize is the separable product
+ * Wh . img . Ww^T; the caller passes each matrix as a BAND TABLE built once per (n_in, n_out): for output index o, start[o] (int32) is
+ * the first input index and taps[o*T .. o*T+T-1] (fp32) the weights of T consecutive inputs, zero-padded, with start[o] + T <= n_in
+ * (the kernels trust this; T > n_in is VITAMD_ERR_SHAPE).  Weights: scale = n_in/n_out, support = max(scale, 1), centre = (o + 0.5) scale,
+ * inputs j in [max(int(centre - support + 0.5), 0), min(int(centre + support + 0.5), n_in)), weight max(0, 1 - |(j - centre + 0.5) / support|)
+ * normalised to sum 1.  Sums are fp32: along W first, then along H.
+ * Outputs (either may be NULL, not both): rows_bf16 [B*(S/4)^2, 64], the operand of the 4x4 stride-4 stem convolution - row
+ * b*(S/4)^2 + (oh/4)*(S/4) + ow/4, column c*16 + (oh%4)*4 + ow%4, columns 48..63 written as zeros; nchw fp32 [B,3,S,S]. */
+int vitamd_resize_norm_fwd(const float* img, const int* start_h, const float* taps_h, int Th, const int* start_w, const float* taps_w, int Tw,
+                           const float* mean, const float* stdv, void* rows_bf16, float* nchw, int B, int C, int Hin, int Win, int S,
+                           void* stream);
+/* Its backward: dimg fp32 [B,3,Hin,Win] = Wh^T . g . Ww / std, overwritten, from g fp32 in the patch-row layout above with row stride
+ * ldg >= 48 (the gradient of the stem GEMM's operand).  The tables are those of the TRANSPOSED matrices: index = input pixel, start =
+ * first output index, start + T <= S.  replaces the autograd backward of perceptual_loss.py:61,63. */
+int vitamd_resize_norm_bwd(const float* g_rows, int ldg, const int* start_h, const float* taps_h, int Th, const int* start_w,
+                           const float* taps_w, int Tw, const float* stdv, float* dimg, int B, int C, int Hin, int Win, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

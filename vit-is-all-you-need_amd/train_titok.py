@@ -147,8 +147,9 @@ def tokenizer_loss(enc, quant, dec, x):
 
 def train_step(model, images, optim, lr_sched=None, perceptual=None, perceptual_weight=1.0):
     """One iteration of the reference hot loop (train_titok.py:151-163) without the fp16 scaler, on model.loss: the pixel term is the mean
-    squared error.  perceptual: a callable (recon, images) -> per-image values (the reference's LPIPS network, which is not part of this
-    package): the step then runs model(images), which yields the image, and adds perceptual_weight * perceptual(recon, images).mean().
+    squared error.  perceptual: a callable (recon, images) -> a loss or per-image values - vitamd.perceptual.PerceptualLoss, the reference's
+    frozen ConvNeXt-S on this library's kernels, fits as it is: the step then runs model(images), which yields the image, and adds
+    perceptual_weight * perceptual(recon, images).mean().
     The reference clips the gradients AFTER the optimiser step, where the clip changes no update; this step does not clip.
     -> the detached device loss"""
     optim.zero_grad(set_to_none=True)
@@ -178,6 +179,11 @@ def add_common_args(p):
     p.add_argument("--train_steps", type=int, default=50)
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
+    p.add_argument("--perceptual_weight", type=float, default=0.0,
+                   help="weight of the ConvNeXt-S perceptual term (reference train_titok.py:155-158); 0 = no perceptual term")
+    p.add_argument("--perceptual_weights", type=str, default=None,
+                   help="path of a torchvision convnext_small state dict for the perceptual network; without it the network is untrained "
+                        "(a throughput stand-in).  Nothing is ever downloaded")
     return p
 
 
@@ -194,18 +200,29 @@ def make_optim(model, args):
     return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
 
 
+def make_perceptual(args):
+    """the perceptual network the arguments ask for, or None (weight 0: the step stays on the fused model.loss route)"""
+    if args.perceptual_weight <= 0:
+        return None
+    from vitamd.perceptual import PerceptualLoss
+    return PerceptualLoss("convnext_s", weights=args.perceptual_weights)
+
+
 def run(model, args, codebook_size):
     """the training loop of both tokenizers on one seeded batch of random images in [0, 1], with the reference's codebook-usage counter"""
     dev = torch.device("cuda")
     model = model.to(dev)
     optim = make_optim(model, args)
     sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
+    perceptual = make_perceptual(args)
+    if perceptual is not None:
+        perceptual = perceptual.to(dev)
     g = torch.Generator(device="cpu").manual_seed(0)
     images = torch.rand((args.bs, 3, args.image_size, args.image_size), generator=g).to(dev)
     usage = torch.zeros([codebook_size], device=dev)
     for step in range(args.train_steps):
         t0 = time.time()
-        loss = train_step(model, images, optim, sched)
+        loss = train_step(model, images, optim, sched, perceptual=perceptual, perceptual_weight=args.perceptual_weight)
         with torch.no_grad():
             usage[model.encode(images)] = 1
         torch.cuda.synchronize()

@@ -83,6 +83,10 @@ SIGNATURES = {
     "vitamd_recon_mse_ws_bytes": [_I, _I, _I, _I, _I],
     "vitamd_recon_mse_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_recon_mse_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vitamd_dwconv7_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vitamd_dwconv7_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vitamd_resize_norm_fwd": [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vitamd_resize_norm_bwd": [_P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
 ERRORS = {1: "unsupported shape", 2: "bad argument", 3: "HIP launch failure", 4: "vitamd_init has not run for this device"}

@@ -924,3 +924,92 @@ def recon_mse_bwd(tokens, images, grid, patch, grad_out=None, out=None):
     _lib.check(_L().vitamd_recon_mse_bwd(_p(tokens), is_bf16, _p(images), _p(grad_out), _p(out), B, grid, patch, c, ld, out.stride(0), _stream()),
                f"recon_mse_bwd[B={B},G={grid},p={patch},c={c},ld={ld}]")
     return out
+
+
+# ------------------------------------------------------------------------------------------ the perceptual loss
+def _need_dwconv(x, w, what):
+    """x fp32 / bf16 rows [B, H, W, C] (channels last, contiguous), w fp32 [C, 7, 7] -> (B, H, W, C, is_bf16); shape errors before any
+    device is looked at"""
+    if not isinstance(x, torch.Tensor) or not isinstance(w, torch.Tensor) or x.dim() != 4 or w.dim() != 3:
+        raise _lib.VitamdError(f"{what}: expected rows [B, H, W, C] and a weight [C, 7, 7]")
+    B, H, W, C = x.shape
+    if tuple(w.shape) != (C, 7, 7) or C % 4 != 0 or min(B, H, W, C) < 1:
+        raise ValueError(f"{what}: needs rows [B, H, W, C] with C % 4 == 0 and a weight [C, 7, 7], got {tuple(x.shape)} and {tuple(w.shape)}")
+    if x.dtype not in (F32, BF16):
+        raise _lib.VitamdError(f"{what}: rows must be fp32 or bf16, got {x.dtype}")
+    _need(x, x.dtype, "rows", 4); _need(w, F32, "w", 3)
+    return B, H, W, C, int(x.dtype == BF16)
+
+
+def dwconv7_fwd(x, w, bias=None):
+    """Depthwise 7x7 convolution (stride 1, zero padding 3) on channels-last rows: x fp32 / bf16 [B, H, W, C], w fp32 [C, 7, 7], bias fp32
+    [C] or None -> y fp32 [B, H, W, C] (include/vitamd.h vitamd_dwconv7_fwd)."""
+    B, H, W, C, is_bf16 = _need_dwconv(x, w, "dwconv7_fwd")
+    if bias is not None:
+        _need(bias, F32, "bias", 1)
+        if bias.numel() != C:
+            raise _lib.VitamdError(f"dwconv7_fwd: bias must have {C} elements")
+    y = torch.empty((B, H, W, C), dtype=F32, device=x.device)
+    _lib.check(_L().vitamd_dwconv7_fwd(_p(x), is_bf16, _p(w), _p(bias), _p(y), B, H, W, C, _stream()), f"dwconv7_fwd[B={B},H={H},W={W},C={C}]")
+    return y
+
+
+def dwconv7_bwd(dy, w, add=None):
+    """Its input gradient: dy fp32 / bf16 [B, H, W, C] -> dx fp32 [B, H, W, C] = (add or 0) + conv^T(dy); add: fp32 rows of the same shape
+    (the gradient arriving along the residual branch).  No weight gradient: the network is frozen."""
+    B, H, W, C, is_bf16 = _need_dwconv(dy, w, "dwconv7_bwd")
+    if add is not None:
+        _need(add, F32, "add", 4)
+        if tuple(add.shape) != (B, H, W, C) or add.data_ptr() == dy.data_ptr():
+            raise _lib.VitamdError(f"dwconv7_bwd: add must be other fp32 rows of shape {(B, H, W, C)}")
+    dx = torch.empty((B, H, W, C), dtype=F32, device=dy.device)
+    _lib.check(_L().vitamd_dwconv7_bwd(_p(dy), is_bf16, _p(w), _p(add), _p(dx), B, H, W, C, _stream()), f"dwconv7_bwd[B={B},H={H},W={W},C={C}]")
+    return dx
+
+
+RESIZE_ROW_LD = 64        # include/vitamd.h vitamd_resize_norm_fwd: 3 * 4 * 4 = 48 patch values, zero-padded to the GEMM's K % 64 == 0
+
+
+def _need_band(table, n_index, n_other, name):
+    """a band table (start int32 [n_index], taps fp32 [n_index, T]) whose bands lie inside [0, n_other) -> T"""
+    start, taps = table
+    _need(start, torch.int32, f"{name}.start", 1); _need(taps, F32, f"{name}.taps", 2)
+    T = taps.shape[1]
+    if start.numel() != n_index or taps.shape[0] != n_index or not 1 <= T <= n_other:
+        raise _lib.VitamdError(f"{name}: expected start [{n_index}] and taps [{n_index}, T] with 1 <= T <= {n_other}")
+    return T
+
+
+def resize_norm_fwd(img, table_h, table_w, mean, std, size, want_rows=True, want_nchw=False):
+    """Antialiased bilinear resize to size x size, then (x - mean) / std: img fp32 [B, 3, H, W]; table_h / table_w: the band tables of the
+    two resize matrices (vitamd.perceptual.band_tables(n_in, size, device)[0], whose bands are inside the image by construction);
+    mean, std fp32 with 3 elements -> (rows bf16 [B*(size/4)^2, 64] or None, nchw fp32 [B, 3, size, size] or None)."""
+    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or min(img.shape) < 1 or size < 4 or size % 4 != 0:
+        raise ValueError(f"resize_norm_fwd: needs images [B, 3, H, W] and size % 4 == 0, got {tuple(getattr(img, 'shape', ()))} and size {size}")
+    if not (want_rows or want_nchw):
+        raise ValueError("resize_norm_fwd: nothing to write")
+    _need(img, F32, "img", 4); _need(mean, F32, "mean"); _need(std, F32, "std")
+    B, _, H, W = img.shape
+    if mean.numel() != 3 or std.numel() != 3:
+        raise _lib.VitamdError("resize_norm_fwd: mean and std must have 3 elements")
+    Th, Tw = _need_band(table_h, size, H, "table_h"), _need_band(table_w, size, W, "table_w")
+    rows = torch.empty((B * (size // 4) ** 2, RESIZE_ROW_LD), dtype=BF16, device=img.device) if want_rows else None
+    nchw = torch.empty((B, 3, size, size), dtype=F32, device=img.device) if want_nchw else None
+    _lib.check(_L().vitamd_resize_norm_fwd(_p(img), _p(table_h[0]), _p(table_h[1]), Th, _p(table_w[0]), _p(table_w[1]), Tw, _p(mean), _p(std),
+                                           _p(rows), _p(nchw), B, 3, H, W, size, _stream()), f"resize_norm_fwd[B={B},H={H},W={W},S={size}]")
+    return rows, nchw
+
+
+def resize_norm_bwd(g_rows, table_h_t, table_w_t, std, B, H, W, size):
+    """Backward of resize_norm_fwd: g_rows fp32 [B*(size/4)^2, ld >= 48] in the patch-row layout -> dimg fp32 [B, 3, H, W]; the tables
+    are those of the transposed matrices (band_tables(...)[1])."""
+    if size < 4 or size % 4 != 0 or min(B, H, W) < 1:
+        raise ValueError(f"resize_norm_bwd: needs B, H, W >= 1 and size % 4 == 0, got {(B, H, W)} and size {size}")
+    if not isinstance(g_rows, torch.Tensor) or g_rows.dim() != 2 or g_rows.shape[0] != B * (size // 4) ** 2 or g_rows.shape[1] < 48:
+        raise ValueError(f"resize_norm_bwd: g_rows must be [{B * (size // 4) ** 2}, >= 48], got {tuple(getattr(g_rows, 'shape', ()))}")
+    _need(g_rows, F32, "g_rows", 2); _need(std, F32, "std")
+    Th, Tw = _need_band(table_h_t, H, size, "table_h_t"), _need_band(table_w_t, W, size, "table_w_t")
+    dimg = torch.empty((B, 3, H, W), dtype=F32, device=g_rows.device)
+    _lib.check(_L().vitamd_resize_norm_bwd(_p(g_rows), g_rows.shape[1], _p(table_h_t[0]), _p(table_h_t[1]), Th, _p(table_w_t[0]), _p(table_w_t[1]),
+                                           Tw, _p(std), _p(dimg), B, 3, H, W, size, _stream()), f"resize_norm_bwd[B={B},H={H},W={W},S={size}]")
+    return dimg
