@@ -22,6 +22,7 @@
 // *_long_kernel forms and the lane-side set-up of dQ (as __forceinline__ functions they changed registers and waits of those kernels), and the
 // local zeroing loops / addressing lines of the kernels whose code the helpers changed (profiles/attention_shared_source/README.md).
 #include "common.h"
+#include "vitamd_internal.h"
 #include <type_traits>
 
 namespace {
@@ -1166,7 +1167,8 @@ int make_args(AttnArgs& out, bool bwd, const void* qkv, const void* o, const flo
               int N, int H, int head_dim, int causal, float p, unsigned long long seed, int nq = 0) {
   if (head_dim != DH || B <= 0 || N <= 0 || H <= 0 || N > MAX_N_LONG) return VITAMD_ERR_SHAPE;
   if (!qkv || !o || !lse2 || (bwd && (!d_o || !dqkv || !delta))) return VITAMD_ERR_ARG;
-  if (!(p >= 0.f) || p >= 1.f) return VITAMD_ERR_ARG;
+  const DropoutParams d = dropout_params(p, seed);
+  if (!d.ok) return VITAMD_ERR_ARG;
   AttnArgs a{};
   a.qkv = (const __bf16*)qkv;
   a.o = (__bf16*)o;
@@ -1181,23 +1183,15 @@ int make_args(AttnArgs& out, bool bwd, const void* qkv, const void* o, const flo
   a.causal = causal;
   a.scale = 0.125f;                                  // 1 / sqrt(64)
   a.scale_log2e = 0.125f * 1.4426950408889634f;
-  a.drop_thresh = p > 0.f ? (unsigned)((double)p * 4294967296.0) : 0u;
-  if (p > 0.f && a.drop_thresh == 0u) a.drop_thresh = 1u;
-  a.drop_scale = 1.0f / (1.0f - p);
-  a.seed_lo = (unsigned)seed;
-  a.seed_hi = (unsigned)(seed >> 32);
+  a.drop_thresh = d.thresh;
+  a.drop_scale = d.scale;
+  a.seed_lo = d.seed_lo;
+  a.seed_hi = d.seed_hi;
   a.nq = nq;
   out = a;
   return VITAMD_OK;
 }
 
-// dynamic-LDS opt-in + launch of one kernel instantiation
-template <auto Kernel>
-int launch(dim3 grid, dim3 block, int lds, hipStream_t stream, const AttnArgs& a) {
-  if (int e = set_lds(Kernel, lds)) return e;
-  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, a);
-  return VITAMD_OK;
-}
 int launched(int e) { return e ? e : hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH; }
 
 // A runtime value as a template argument: f is a generic lambda that gets a std::integral_constant and reads decltype(arg)::value.

@@ -52,20 +52,12 @@ extern "C" int vitamd_gemm_tn_bf16_ws_colsum(const void* L, const void* Rm, floa
   return vitamd_gemm_tn_impl(a, (hipStream_t)stream);
 }
 
-static bool dropout_params(float p, unsigned& thresh, float& scale) {
-  if (!(p >= 0.0f) || p >= 1.0f) return false;
-  thresh = p > 0.0f ? (unsigned)((double)p * 4294967296.0) : 0u;
-  if (p > 0.0f && thresh == 0u) thresh = 1u;
-  scale = 1.0f / (1.0f - p);
-  return true;
-}
-
 // fc2 with dropout: out f32 = resid + dropout_p(bf16(A.B^T + bias)) — reference transformer.py:39-40,44
 extern "C" int vitamd_linear_dropout_resid_bf16(const void* A, const void* B, float* out, const float* bias, const float* resid,
                                                 int M, int N, int K, float dropout_p, unsigned long long seed, int tile, void* stream) {
   if (!is_auto(tile) && tile != NT_TILE_128 && tile != NT_TILE_256 && tile != NT_TILE_320) return VITAMD_ERR_ARG;
-  GemmNtArgs p{A, B, out, nullptr, bias, resid, nullptr, M, N, K, N, EPI_RESID_F32, 0, 0, 0, tile, 0u, 1.0f,
-               (unsigned)seed, (unsigned)(seed >> 32), 0, 0};
-  if (!dropout_params(dropout_p, p.drop_thresh, p.drop_scale)) return VITAMD_ERR_ARG;
+  const DropoutParams d = dropout_params(dropout_p, seed);
+  if (!d.ok) return VITAMD_ERR_ARG;
+  GemmNtArgs p{A, B, out, nullptr, bias, resid, nullptr, M, N, K, N, EPI_RESID_F32, 0, 0, 0, tile, d.thresh, d.scale, d.seed_lo, d.seed_hi, 0, 0};
   return vitamd_gemm_nt_impl(p, (hipStream_t)stream);
 }

@@ -120,6 +120,13 @@ template <typename K>
 static inline int set_lds(K kern, int bytes) {
   return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
+// that opt-in + the launch of one kernel instantiation; the caller asks hipGetLastError() behind its last launch
+template <auto Kernel, typename... Args>
+static inline int launch(dim3 grid, dim3 block, int lds, hipStream_t stream, const Args&... args) {
+  if (int e = set_lds(Kernel, lds)) return e;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+  return VITAMD_OK;
+}
 
 // erf with |abs err| < 1.5e-7 (Abramowitz & Stegun 7.1.26): one v_exp, one v_rcp, 5 fma.
 // Outputs are rounded to bf16 (2^-9 relative) so this is exact for our purposes.

@@ -3,7 +3,7 @@
 // Why (profiles/r03/nt_request_ablations.log): with every LDS-DMA request taken out of gemm_nt_pp_kernel's main loop the K = 3072 input-gradient
 // GEMM runs in 142 us instead of 199; with the requests issued but out of range (no data) 171.  Half of what the operand feed costs is the ISSUE
 // of the requests from the compute waves: a 1-KiB vector-memory instruction holds the issuing wave for 60-185 cycles inside a read section that
-// its SIMD partner's 256 cycles of MFMAs are supposed to cover.  gemm_tn_ld_kernel (gemm_tn.hip) moved them into four dedicated waves and gained
+// its SIMD partner's 256 cycles of MFMAs are supposed to cover.  gemm_tn_kernel's loader form (gemm_tn.hip) moved them into four dedicated waves and gained
 // 15 %; this is the same step for the NT GEMM:
 //   * waves 0-7 compute (2 x 4, wave tile 128 x 64, mfma_f32_16x16x32_bf16 with A/B swapped, the ping-pong of gemm_nt_pp_kernel: the second wave
 //     row runs one barrier behind the first) and issue NO vector-memory instruction inside the K loop;

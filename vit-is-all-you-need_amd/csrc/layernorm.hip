@@ -7,6 +7,8 @@
 //             per-column sums of that bf16 copy (the bias gradient of the Linear whose output
 //             gradient it is).
 #include "common.h"
+#include "vitamd_internal.h"
+#include <type_traits>
 
 namespace {
 
@@ -220,110 +222,109 @@ int grid_for(int M, bool colsum = false) {
   return blocks < cap ? blocks : cap;
 }
 
-}  // namespace
+// The width as a template argument: f is a generic lambda that gets std::integral_constant<int, NV> for D = 256 NV, NV = 1 .. 4 (the
+// register-resident kernels), and <int, 0> for every other D (the generic kernels).
+bool register_width(int D) { return D == 256 || D == 512 || D == 768 || D == 1024; }
+template <typename F>
+void with_width(int D, F f) {
+  if (D == 256) f(std::integral_constant<int, 1>{});
+  else if (D == 512) f(std::integral_constant<int, 2>{});
+  else if (D == 768) f(std::integral_constant<int, 3>{});
+  else if (D == 1024) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 0>{});
+}
 
-extern "C" int vitamd_layernorm_fwd(const float* x_in, const void* addend_bf16, float* x_out, void* y_bf16, float* mean,
-                                    float* rstd, int M, int D, float eps, void* stream_) {
+// Every forward launch.  KEEP: the kept-row form (M = B * keep; the addend is required there, so only HAS_ADD = true exists).
+template <bool KEEP>
+int ln_fwd_launch(const float* x_in, const void* addend_bf16, float* x_out, void* y_bf16, float* mean, float* rstd, int M, int D, float eps, int seq,
+                  int keep, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (M <= 0 || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
-  if (!x_in || !y_bf16 || !mean || !rstd || (addend_bf16 && !x_out)) return VITAMD_ERR_ARG;
   const __bf16* add = (const __bf16*)addend_bf16;
   __bf16* y = (__bf16*)y_bf16;
-  const int grid = grid_for(M);
-#define LN_FWD(NV)                                                                                                   \
-  if (add) hipLaunchKernelGGL((ln_fwd_kernel<NV, true>), dim3(grid), dim3(256), 0, stream, x_in, add, x_out, y, mean, rstd, M, eps); \
-  else hipLaunchKernelGGL((ln_fwd_kernel<NV, false>), dim3(grid), dim3(256), 0, stream, x_in, add, x_out, y, mean, rstd, M, eps)
-  if (D == 256) { LN_FWD(1); }
-  else if (D == 512) { LN_FWD(2); }
-  else if (D == 768) { LN_FWD(3); }
-  else if (D == 1024) { LN_FWD(4); }
-  else if (add) hipLaunchKernelGGL((ln_fwd_generic<true>), dim3(grid), dim3(256), 0, stream, x_in, add, x_out, y, mean, rstd, M, D, eps);
-  else hipLaunchKernelGGL((ln_fwd_generic<false>), dim3(grid), dim3(256), 0, stream, x_in, add, x_out, y, mean, rstd, M, D, eps);
-#undef LN_FWD
+  const dim3 grid(grid_for(M)), block(256);
+  with_width(D, [&](auto W) {
+    constexpr int NV = decltype(W)::value;
+    auto go = [&](auto ADD) {
+      constexpr bool HAS_ADD = decltype(ADD)::value;
+      if constexpr (NV != 0) hipLaunchKernelGGL((ln_fwd_kernel<NV, HAS_ADD, KEEP>), grid, block, 0, stream, x_in, add, x_out, y, mean, rstd, M, eps, seq, keep);
+      else hipLaunchKernelGGL((ln_fwd_generic<HAS_ADD, KEEP>), grid, block, 0, stream, x_in, add, x_out, y, mean, rstd, M, D, eps, seq, keep);
+    };
+    if constexpr (KEEP) go(std::true_type{});
+    else if (add) go(std::true_type{});
+    else go(std::false_type{});
+  });
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
-static int ln_bwd_launch(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* g_res, float* g_out,
-                         void* g_bf16, float* colsum, int M, int D, float dropout_p, unsigned long long seed, void* stream_) {
+// Every backward launch.  GK: compact g_res (M = B * seq).  xhat: x_or_y is the forward's bf16 output (XH = true; the callers have refused
+// the widths without a register-resident kernel) and mean is not read.
+template <bool GK>
+int ln_bwd_launch(const void* dy_bf16, const void* x_or_y, const float* mean, const float* rstd, const float* g_res, float* g_out, void* g_bf16,
+                  float* colsum, int M, int D, bool xhat, const DropoutParams& dp, int seq, int keep, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  const __bf16* dy = (const __bf16*)dy_bf16;
+  const float* x = (const float*)x_or_y;          // XH: the kernel reinterprets it
+  __bf16* gb = (__bf16*)g_bf16;
+  const dim3 grid(grid_for(M, colsum != nullptr && g_bf16 != nullptr)), block(256);
+  with_width(D, [&](auto W) {
+    constexpr int NV = decltype(W)::value;
+    if constexpr (NV != 0) {
+      if (xhat) hipLaunchKernelGGL((ln_bwd_kernel<NV, true, GK>), grid, block, 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, dp.thresh, dp.scale, dp.seed_lo, dp.seed_hi, seq, keep);
+      else hipLaunchKernelGGL((ln_bwd_kernel<NV, false, GK>), grid, block, 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, dp.thresh, dp.scale, dp.seed_lo, dp.seed_hi, seq, keep);
+    } else {
+      hipLaunchKernelGGL(ln_bwd_generic<GK>, grid, block, 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, D, dp.thresh, dp.scale, dp.seed_lo, dp.seed_hi, seq, keep);
+    }
+  });
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+}  // namespace
+
+// The entry points keep their own checks, in this order: shape -> VITAMD_ERR_SHAPE, then null pointers, then the dropout probability -> VITAMD_ERR_ARG.
+extern "C" int vitamd_layernorm_fwd(const float* x_in, const void* addend_bf16, float* x_out, void* y_bf16, float* mean,
+                                    float* rstd, int M, int D, float eps, void* stream) {
+  if (M <= 0 || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
+  if (!x_in || !y_bf16 || !mean || !rstd || (addend_bf16 && !x_out)) return VITAMD_ERR_ARG;
+  return ln_fwd_launch<false>(x_in, addend_bf16, x_out, y_bf16, mean, rstd, M, D, eps, 0, 0, stream);
+}
+
+// the bf16 copy (and its column sums) additionally gets the dropout mask (p, seed) of the
+// Linear output whose gradient it is (index = row * D + column, as in vitamd_linear_dropout_resid_bf16)
+extern "C" int vitamd_layernorm_bwd_dropout(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
+                                            const float* g_res, float* g_out, void* g_bf16, float* colsum, int M, int D,
+                                            float dropout_p, unsigned long long seed, void* stream) {
   if (M <= 0 || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
   if (!dy_bf16 || !x || !mean || !rstd || !g_out) return VITAMD_ERR_ARG;
-  if (!(dropout_p >= 0.f) || dropout_p >= 1.f) return VITAMD_ERR_ARG;
-  unsigned dthresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
-  if (dropout_p > 0.f && dthresh == 0u) dthresh = 1u;
-  const float dscale = 1.0f / (1.0f - dropout_p);
-  const unsigned slo = (unsigned)seed, shi = (unsigned)(seed >> 32);
-  const __bf16* dy = (const __bf16*)dy_bf16;
-  __bf16* gb = (__bf16*)g_bf16;
-  const int grid = grid_for(M, colsum != nullptr && g_bf16 != nullptr);
-#define LN_BWD(NV) hipLaunchKernelGGL((ln_bwd_kernel<NV>), dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, dthresh, dscale, slo, shi)
-  if (D == 256) { LN_BWD(1); }
-  else if (D == 512) { LN_BWD(2); }
-  else if (D == 768) { LN_BWD(3); }
-  else if (D == 1024) { LN_BWD(4); }
-  else hipLaunchKernelGGL(ln_bwd_generic<>, dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, D, dthresh, dscale, slo, shi);
-#undef LN_BWD
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  const DropoutParams dp = dropout_params(dropout_p, seed);
+  if (!dp.ok) return VITAMD_ERR_ARG;
+  return ln_bwd_launch<false>(dy_bf16, x, mean, rstd, g_res, g_out, g_bf16, colsum, M, D, false, dp, 0, 0, stream);
 }
 
 extern "C" int vitamd_layernorm_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
                                     const float* g_res, float* g_out, void* g_bf16, float* colsum, int M, int D,
                                     void* stream) {
-  return ln_bwd_launch(dy_bf16, x, mean, rstd, g_res, g_out, g_bf16, colsum, M, D, 0.f, 0ull, stream);
-}
-
-// same; the bf16 copy (and its column sums) additionally gets the dropout mask (p, seed) of the
-// Linear output whose gradient it is (index = row * D + column, as in vitamd_linear_dropout_resid_bf16)
-extern "C" int vitamd_layernorm_bwd_dropout(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
-                                            const float* g_res, float* g_out, void* g_bf16, float* colsum, int M, int D,
-                                            float dropout_p, unsigned long long seed, void* stream) {
-  return ln_bwd_launch(dy_bf16, x, mean, rstd, g_res, g_out, g_bf16, colsum, M, D, dropout_p, seed, stream);
+  return vitamd_layernorm_bwd_dropout(dy_bf16, x, mean, rstd, g_res, g_out, g_bf16, colsum, M, D, 0.f, 0ull, stream);
 }
 
 // LayerNorm backward with xhat taken from the forward's bf16 output (see ln_bwd_kernel<NV, true>): D in {256, 512, 768, 1024}.
 extern "C" int vitamd_layernorm_bwd_xhat(const void* dy_bf16, const void* y_bf16, const float* rstd, const float* g_res, float* g_out,
                                          void* g_bf16, float* colsum, int M, int D, float dropout_p, unsigned long long seed,
-                                         void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (M <= 0 || (D != 256 && D != 512 && D != 768 && D != 1024)) return VITAMD_ERR_SHAPE;
+                                         void* stream) {
+  if (M <= 0 || !register_width(D)) return VITAMD_ERR_SHAPE;
   if (!dy_bf16 || !y_bf16 || !rstd || !g_out) return VITAMD_ERR_ARG;
-  if (!(dropout_p >= 0.f) || dropout_p >= 1.f) return VITAMD_ERR_ARG;
-  unsigned dthresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
-  if (dropout_p > 0.f && dthresh == 0u) dthresh = 1u;
-  const float dscale = 1.0f / (1.0f - dropout_p);
-  const unsigned slo = (unsigned)seed, shi = (unsigned)(seed >> 32);
-  const __bf16* dy = (const __bf16*)dy_bf16;
-  const float* yx = (const float*)y_bf16;        // the kernel reinterprets it (XH = true)
-  __bf16* gb = (__bf16*)g_bf16;
-  const int grid = grid_for(M, colsum != nullptr && g_bf16 != nullptr);
-#define LN_BWDX(NV) hipLaunchKernelGGL((ln_bwd_kernel<NV, true>), dim3(grid), dim3(256), 0, stream, dy, yx, (const float*)nullptr, rstd, g_res, g_out, gb, colsum, M, dthresh, dscale, slo, shi)
-  if (D == 256) { LN_BWDX(1); }
-  else if (D == 512) { LN_BWDX(2); }
-  else if (D == 768) { LN_BWDX(3); }
-  else { LN_BWDX(4); }
-#undef LN_BWDX
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  const DropoutParams dp = dropout_params(dropout_p, seed);
+  if (!dp.ok) return VITAMD_ERR_ARG;
+  return ln_bwd_launch<false>(dy_bf16, y_bf16, nullptr, rstd, g_res, g_out, g_bf16, colsum, M, D, true, dp, 0, 0, stream);
 }
 
 // Kept-row forward: M = B * keep output rows; row b*keep + t = LN(x_in[b*seq + t] + addend[b*keep + t]).  x_out, y, mean, rstd are compact
 // [B*keep, ...].  addend (bf16 [B*keep, D], the kept-query attention output) and x_out are required.
 extern "C" int vitamd_layernorm_fwd_keep(const float* x_in, const void* addend_bf16, float* x_out, void* y_bf16, float* mean, float* rstd,
-                                         int B, int seq, int keep, int D, float eps, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+                                         int B, int seq, int keep, int D, float eps, void* stream) {
   if (B <= 0 || seq <= 0 || keep <= 0 || keep > seq || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
   if ((long long)B * seq > 2147483647LL) return VITAMD_ERR_SHAPE;
   if (!x_in || !y_bf16 || !mean || !rstd || !addend_bf16 || !x_out) return VITAMD_ERR_ARG;
-  const __bf16* add = (const __bf16*)addend_bf16;
-  __bf16* y = (__bf16*)y_bf16;
-  const int M = B * keep, grid = grid_for(M);
-#define LN_FWDK(NV) hipLaunchKernelGGL((ln_fwd_kernel<NV, true, true>), dim3(grid), dim3(256), 0, stream, x_in, add, x_out, y, mean, rstd, M, eps, seq, keep)
-  if (D == 256) { LN_FWDK(1); }
-  else if (D == 512) { LN_FWDK(2); }
-  else if (D == 768) { LN_FWDK(3); }
-  else if (D == 1024) { LN_FWDK(4); }
-  else hipLaunchKernelGGL((ln_fwd_generic<true, true>), dim3(grid), dim3(256), 0, stream, x_in, add, x_out, y, mean, rstd, M, D, eps, seq, keep);
-#undef LN_FWDK
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return ln_fwd_launch<true>(x_in, addend_bf16, x_out, y_bf16, mean, rstd, B * keep, D, eps, seq, keep, stream);
 }
 
 // LayerNorm backward over M = B * seq rows with a COMPACT g_res [B*keep, D]: row b*seq + t adds g_res[b*keep + t] when t < keep, nothing
@@ -331,30 +332,12 @@ extern "C" int vitamd_layernorm_fwd_keep(const float* x_in, const void* addend_b
 // else the fp32 input with mean / rstd (vitamd_layernorm_bwd_dropout).  g_bf16, colsum and the dropout arguments as there.
 extern "C" int vitamd_layernorm_bwd_keep(const void* dy_bf16, const void* x_or_y, const float* mean, const float* rstd, const float* g_res,
                                          float* g_out, void* g_bf16, float* colsum, int B, int seq, int keep, int D, int use_xhat,
-                                         float dropout_p, unsigned long long seed, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+                                         float dropout_p, unsigned long long seed, void* stream) {
   if (B <= 0 || seq <= 0 || keep <= 0 || keep > seq || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
   if ((long long)B * seq > 2147483647LL) return VITAMD_ERR_SHAPE;
-  const bool wide = D == 256 || D == 512 || D == 768 || D == 1024;
-  if (use_xhat && !wide) return VITAMD_ERR_SHAPE;
+  if (use_xhat && !register_width(D)) return VITAMD_ERR_SHAPE;
   if (!dy_bf16 || !x_or_y || !rstd || !g_res || !g_out || (!use_xhat && !mean)) return VITAMD_ERR_ARG;
-  if (!(dropout_p >= 0.f) || dropout_p >= 1.f) return VITAMD_ERR_ARG;
-  unsigned dthresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
-  if (dropout_p > 0.f && dthresh == 0u) dthresh = 1u;
-  const float dscale = 1.0f / (1.0f - dropout_p);
-  const unsigned slo = (unsigned)seed, shi = (unsigned)(seed >> 32);
-  const __bf16* dy = (const __bf16*)dy_bf16;
-  const float* x = (const float*)x_or_y;
-  __bf16* gb = (__bf16*)g_bf16;
-  const int M = B * seq, grid = grid_for(M, colsum != nullptr && g_bf16 != nullptr);
-#define LN_BWDK(NV)                                                                                                                    \
-  if (use_xhat) hipLaunchKernelGGL((ln_bwd_kernel<NV, true, true>), dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, dthresh, dscale, slo, shi, seq, keep); \
-  else hipLaunchKernelGGL((ln_bwd_kernel<NV, false, true>), dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, dthresh, dscale, slo, shi, seq, keep)
-  if (D == 256) { LN_BWDK(1); }
-  else if (D == 512) { LN_BWDK(2); }
-  else if (D == 768) { LN_BWDK(3); }
-  else if (D == 1024) { LN_BWDK(4); }
-  else hipLaunchKernelGGL(ln_bwd_generic<true>, dim3(grid), dim3(256), 0, stream, dy, x, mean, rstd, g_res, g_out, gb, colsum, M, D, dthresh, dscale, slo, shi, seq, keep);
-#undef LN_BWDK
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  const DropoutParams dp = dropout_params(dropout_p, seed);
+  if (!dp.ok) return VITAMD_ERR_ARG;
+  return ln_bwd_launch<true>(dy_bf16, x_or_y, mean, rstd, g_res, g_out, g_bf16, colsum, B * seq, D, use_xhat != 0, dp, seq, keep, stream);
 }

@@ -17,6 +17,8 @@ __device__ __forceinline__ void put(float* p, float v) { *p = v; }
 __device__ __forceinline__ float get(const __bf16* p) { return bf2f(*p); }
 __device__ __forceinline__ float get(const float* p) { return *p; }
 
+dim3 grid_for(int M, int cap) { const int blocks = (M + WAVES - 1) / WAVES; return dim3(blocks > cap ? cap : blocks); }   // one row per wave, grid-stride beyond `cap` workgroups
+
 // YT = __bf16 (feeds a GEMM) or float (ln_pre / ln_post of the tokenizers, whose output stays in the fp32 stream)
 template <typename YT>
 __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -87,8 +89,7 @@ extern "C" int vitamd_layernorm_affine_fwd(const float* x, const float* gamma, c
                                            float* rstd, int M, int D, float eps, void* stream) {
   if (M <= 0 || D <= 0) return VITAMD_ERR_SHAPE;
   if (!x || !gamma || !beta || !y_bf16 || !mean || !rstd) return VITAMD_ERR_ARG;
-  int grid = (M + WAVES - 1) / WAVES; grid = grid > 2048 ? 2048 : grid;
-  hipLaunchKernelGGL(ln_affine_fwd_kernel<__bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (__bf16*)y_bf16, mean, rstd, M, D, eps);
+  hipLaunchKernelGGL(ln_affine_fwd_kernel<__bf16>, grid_for(M, 2048), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (__bf16*)y_bf16, mean, rstd, M, D, eps);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
@@ -96,8 +97,7 @@ extern "C" int vitamd_layernorm_affine_fwd_f32(const float* x, const float* gamm
                                                float* rstd, int M, int D, float eps, void* stream) {
   if (M <= 0 || D <= 0) return VITAMD_ERR_SHAPE;
   if (!x || !gamma || !beta || !y || !mean || !rstd) return VITAMD_ERR_ARG;
-  int grid = (M + WAVES - 1) / WAVES; grid = grid > 2048 ? 2048 : grid;
-  hipLaunchKernelGGL(ln_affine_fwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, M, D, eps);
+  hipLaunchKernelGGL(ln_affine_fwd_kernel<float>, grid_for(M, 2048), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, M, D, eps);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
@@ -106,8 +106,7 @@ extern "C" int vitamd_layernorm_affine_bwd(const void* dy_bf16, const float* x, 
                                            float* dgamma, float* dbeta, int M, int D, void* stream) {
   if (M <= 0 || D <= 0 || D > 4096) return VITAMD_ERR_SHAPE;
   if (!dy_bf16 || !x || !mean || !rstd || !gamma || !g_out || !dgamma || !dbeta) return VITAMD_ERR_ARG;
-  int grid = (M + WAVES - 1) / WAVES; grid = grid > 1024 ? 1024 : grid;
-  hipLaunchKernelGGL(ln_affine_bwd_kernel<__bf16>, dim3(grid), dim3(256), 3 * D * sizeof(float), (hipStream_t)stream, (const __bf16*)dy_bf16, x,
+  hipLaunchKernelGGL(ln_affine_bwd_kernel<__bf16>, grid_for(M, 1024), dim3(256), 3 * D * sizeof(float), (hipStream_t)stream, (const __bf16*)dy_bf16, x,
                      mean, rstd, gamma, g_res, g_out, (__bf16*)g_bf16, colsum, dgamma, dbeta, M, D);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
@@ -116,8 +115,7 @@ extern "C" int vitamd_layernorm_affine_bwd_f32(const float* dy, const float* x, 
                                                const float* gamma, float* g_out, float* dgamma, float* dbeta, int M, int D, void* stream) {
   if (M <= 0 || D <= 0 || D > 4096) return VITAMD_ERR_SHAPE;
   if (!dy || !x || !mean || !rstd || !gamma || !g_out || !dgamma || !dbeta) return VITAMD_ERR_ARG;
-  int grid = (M + WAVES - 1) / WAVES; grid = grid > 1024 ? 1024 : grid;
-  hipLaunchKernelGGL(ln_affine_bwd_kernel<float>, dim3(grid), dim3(256), 3 * D * sizeof(float), (hipStream_t)stream, dy, x, mean, rstd, gamma,
+  hipLaunchKernelGGL(ln_affine_bwd_kernel<float>, grid_for(M, 1024), dim3(256), 3 * D * sizeof(float), (hipStream_t)stream, dy, x, mean, rstd, gamma,
                      (const float*)nullptr, g_out, (__bf16*)nullptr, (float*)nullptr, dgamma, dbeta, M, D);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }

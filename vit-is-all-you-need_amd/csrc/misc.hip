@@ -1,6 +1,7 @@
 // Small HBM-bound helpers around the GEMMs: dtype casts, weight transpose, patch gather (im2col),
 // column sums (bias gradients) and the patch-embed backward reduction.
 #include "common.h"
+#include "vitamd_internal.h"
 
 namespace {
 
@@ -417,24 +418,21 @@ extern "C" int vitamd_cast_f32_bf16(const float* in, void* out_bf16, long n, voi
 
 extern "C" int vitamd_cast_f32_bf16_dropout(const float* in, void* out_bf16, long n, float dropout_p, unsigned long long seed, void* stream) {
   if (n <= 0) return n == 0 ? VITAMD_OK : VITAMD_ERR_SHAPE;
-  if (!in || !out_bf16 || !(dropout_p >= 0.f) || dropout_p >= 1.f) return VITAMD_ERR_ARG;
-  unsigned thresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
-  if (dropout_p > 0.f && thresh == 0u) thresh = 1u;
+  const DropoutParams d = dropout_params(dropout_p, seed);
+  if (!in || !out_bf16 || !d.ok) return VITAMD_ERR_ARG;
   int grid = (int)(((size_t)n + 255) / 256); grid = grid > 8192 ? 8192 : grid;
-  hipLaunchKernelGGL(cast_dropout_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (__bf16*)out_bf16, (size_t)n, thresh,
-                     1.0f / (1.0f - dropout_p), (unsigned)seed, (unsigned)(seed >> 32));
+  hipLaunchKernelGGL(cast_dropout_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (__bf16*)out_bf16, (size_t)n, d.thresh, d.scale, d.seed_lo, d.seed_hi);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
 template <typename T>
 static int launch_dropout(const void* in, void* out, long n, long group, float dropout_p, unsigned long long seed, void* stream) {
   if (n <= 0 || group <= 0) return n == 0 ? VITAMD_OK : VITAMD_ERR_SHAPE;
-  if (!in || !out || !(dropout_p >= 0.f) || dropout_p >= 1.f) return VITAMD_ERR_ARG;
-  unsigned thresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
-  if (dropout_p > 0.f && thresh == 0u) thresh = 1u;
+  const DropoutParams d = dropout_params(dropout_p, seed);
+  if (!in || !out || !d.ok) return VITAMD_ERR_ARG;
   int grid = (int)(((size_t)n + 255) / 256); grid = grid > 8192 ? 8192 : grid;
-  hipLaunchKernelGGL(dropout_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)in, (T*)out, (size_t)n, (size_t)group, thresh,
-                     1.0f / (1.0f - dropout_p), (unsigned)seed, (unsigned)(seed >> 32));
+  hipLaunchKernelGGL(dropout_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)in, (T*)out, (size_t)n, (size_t)group, d.thresh, d.scale, d.seed_lo,
+                     d.seed_hi);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 extern "C" int vitamd_dropout_bf16(const void* in, void* out, long n, long group, float dropout_p, unsigned long long seed, void* stream) {

@@ -62,6 +62,23 @@ struct GemmTnArgs {
   float* colsum;   // optional, workspace form only: colsum[p] += sum_r L[r,p] (fp32 [P], caller-zeroed); partials behind the tiles in `ws`
 };
 
+// Host side of the counter-based dropout (common.h, dropout_keep): (p, seed) -> the four scalars every dropout kernel takes.
+// ok is false for a p outside [0, 1), NaN included (the entry points answer VITAMD_ERR_ARG); thresh = p * 2^32, 0 only for p == 0 (off).
+struct DropoutParams {
+  unsigned thresh;
+  float scale;               // 1 / (1 - p)
+  unsigned seed_lo, seed_hi;
+  bool ok;
+};
+inline DropoutParams dropout_params(float p, unsigned long long seed) {
+  DropoutParams d{0u, 1.0f, (unsigned)seed, (unsigned)(seed >> 32), p >= 0.f && p < 1.f};
+  if (!d.ok) return d;
+  d.thresh = p > 0.f ? (unsigned)((double)p * 4294967296.0) : 0u;
+  if (p > 0.f && d.thresh == 0u) d.thresh = 1u;
+  d.scale = 1.0f / (1.0f - p);
+  return d;
+}
+
 int vitamd_gemm_nt_impl(const GemmNtArgs& p, hipStream_t stream);
 int vitamd_gemm_nt_plan_impl(const GemmNtArgs& p);
 int vitamd_init_impl(int device, hipStream_t stream);
