@@ -53,7 +53,13 @@ int vitamd_init(int device, void* stream);
                                   shared with the erf and the VALU work hides under the output stores */
 #define VITAMD_EPI_DMUL 7      /* as DGELU, but aux_bf16 already holds gelu'(pre) (written by GELU_DG): out = bf16(bf16(acc) * aux) */
 
-/* Requirements: K % 64 == 0, N % 4 == 0, ldo % 4 == 0.  bias may be NULL.  `tile`: 0 = auto; 128 = the 128x128 small-problem
+/* Requirements: K % 64 == 0 (whatever the first argument check lets through: K = 96 is VITAMD_ERR_SHAPE from every tile code, nothing
+ * written), N % 4 == 0, ldo % 4 == 0, ldo >= N.  `ldo` (elements) is the row stride of `out` AND of `out2`, of the RESID / DGELU / DMUL `aux`
+ * and of the PATCH position table aux_f32[n_patches][ldo]; A and B are dense (row stride K), bias and colsum hold N elements.  Columns
+ * N .. ldo-1 of every row, and the rows a PATCH launch skips, are neither read nor written.  N % 8 != 0 or ldo % 8 != 0 takes the
+ * direct-store epilogue inside the 256- / 320-row kernels (4-column pieces per lane instead of 8-column row segments): same results, bit for
+ * bit.  The loader-wave and seam forms (2048 / 4096) exist for N % 8 == 0 and ldo % 8 == 0 only, their dGELU-multiply epilogue for
+ * N % 256 == 0 only: VITAMD_ERR_SHAPE otherwise.  bias may be NULL.  `tile`: 0 = auto; 128 = the 128x128 small-problem
  * kernel; 256 / 320 = the ping-pong kernel on 256- / 320-row tiles (320: bias, GELU, residual and dGELU epilogues only),
  * one workgroup per tile.  Auto launches problems with more tiles than CUs PERSISTENT (one workgroup per CU walking a strided tile
  * list: faster next to a second stream's kernels, but sensitive to CUs held by other long-running kernels, e.g. collectives; with a

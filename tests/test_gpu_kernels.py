@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import vit_oracle as O
+from _gemm_ref import bf16_rne_exact as _bf16_rne_exact      # float64 array -> bf16 bit patterns, nearest-even on exact distances
 
 pytestmark = pytest.mark.gpu
 
@@ -203,21 +204,6 @@ def test_gemm_nt_tall_tile_gelu_epilogues_match_256(hip):
         y2 = ops.gemm_nt(a, b, epi, aux=aux, colsum=c2, tile=256)
         assert torch.equal(y1, y2)
         assert O.rel_l2(c1.cpu(), c2.cpu()) < 1.0e-6          # column sums: atomics, order differs
-
-
-def _bf16_rne_exact(v):
-    """float64 array -> bf16 bit patterns, nearest-even decided on exact distances (no float32 intermediate rounding)."""
-    import numpy as np
-    u = v.astype(np.float32).view(np.uint32).astype(np.int64)
-    first = (u + 0x7fff + ((u >> 16) & 1)) >> 16
-    val = lambda b: (b.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-    best, bd = first.copy(), np.abs(val(first) - v)
-    for dl in (-1, 1):
-        n = first + dl
-        dd = np.abs(val(n) - v)
-        take = (dd < bd) | ((dd == bd) & (n % 2 == 0) & (best % 2 == 1))
-        best, bd = np.where(take, n, best), np.where(take, dd, bd)
-    return best.astype(np.int64)
 
 
 def test_gelu_table_exact_on_every_bf16_input(hip):

@@ -102,7 +102,7 @@ def _tn(L, colsum, *, R=64, P_=256, Q=256, ldl=256, ldr=256, ldo=256, splits=1, 
     return L.vitamd_gemm_tn_bf16_ws_colsum(*ptrs, colsum, R, P_, Q, ldl, ldr, ldo, splits, ws, ws_bytes, accumulate, form, None)
 
 
-@pytest.mark.parametrize("colsum", [False, None, P])
+@pytest.mark.parametrize("colsum", [False, None, P], ids=["False", "None", "buffer"])      # (P is an address: as an id it changes from run to run)
 def test_tn_refusals(L, colsum):
     for form in (-1, 2, 7):          # before anything else: with a bad shape and null operands the answer is still the form's
         assert _tn(L, colsum, form=form) == ARG
