@@ -426,6 +426,41 @@ int vitamd_recon_mse_fwd(const void* y, int y_bf16, const float* img, float* los
 int vitamd_recon_mse_bwd(const void* y, int y_bf16, const float* img, const float* grad_out, void* dy, int B, int G, int p, int c, int ld,
                          int ld_dy, void* stream);
 
+/* The quantiser of blocks.VectorQuantizer(use_l2_norm=True, commitment_cost=0.25): the two calls above with UNIT codes.
+ * Same arguments, shapes, search, workspace and error rules; the differences:
+ *   forward   p = e^_idx = e_idx / max(|e_idx|, eps), the NORMALISED row: q = u + (p - u), *loss = 1.25 * mean over M*d of (p - u)^2;
+ *   backward  du and dx as above with that p; the per-code sum T_k = sum over the rows m with idx[m] = k of 2 s (p - u) / (M d) goes through
+ *             the normalisation before it is added: dcodebook[k,:] += (T_k - e^_k (e^_k . T_k)) / |e_k|, or T_k / eps where |e_k| < eps.
+ * The projection is linear, so it is applied to each workgroup's on-chip sum; the atomics and their order dependence are those of
+ * vitamd_vq_quantize_bwd.  `codebook` is the RAW codebook in both calls. */
+int vitamd_vq_quantize_unit_fwd(const float* x, const float* codebook, float* unit, float* rnorm, float* q, long long* idx, float* loss, float* ws,
+                                int M, int K, int d, void* stream);
+int vitamd_vq_quantize_unit_bwd(const float* g_q, const float* g_loss, const float* unit, const float* rnorm, const long long* idx,
+                                const float* codebook, float* dx, float* dcodebook, int M, int K, int d, void* stream);
+
+/* The pixel tail of blocks.TiTokDecoder on the tokens of its head GEMM, c = 3:
+ *   yimg = pixel_shuffle(y) (the index map of vitamd_recon_mse_fwd), r = conv3x3(yimg, w[3,3,3,3], stride 1, zero padding 1) + bias[3],
+ *   *loss = mean over B*3*H*W of (r - img)^2, H = W = G*p.
+ * y = tokens [B*G*G, 3*p*p], bf16 (y_bf16 != 0) or fp32, read as stored, row stride ld >= 3*p*p; all arithmetic fp32; yimg is never formed.
+ * recon: fp32 [B,3,H,W] that receives r, or NULL.  One workgroup per 32 x 32 pixel tile of one image, the tile index in blockIdx.x alone
+ * (no grid cap); a halo never reads another image of the batch: outside the image yimg is zero.
+ * Only a 16-byte path exists: p % 8 == 0 (bf16) / p % 4 == 0 (fp32), ld a multiple of 8 / 4, y 16-byte aligned - anything else
+ * VITAMD_ERR_SHAPE, for the caller to take another route.  ws: vitamd_conv_recon_mse_ws_bytes(B, G, p, y_bf16, backward) bytes
+ * (negative: the shape error): one loss partial per tile (forward), 84 gradient partials per tile (backward), summed in a fixed order. */
+long vitamd_conv_recon_mse_ws_bytes(int B, int G, int p, int y_bf16, int backward);
+int vitamd_conv_recon_mse_fwd(const void* y, int y_bf16, const float* w, const float* bias, const float* img, float* loss, float* recon, float* ws,
+                              int B, int G, int p, int ld, void* stream);
+/* e = (*g_loss) * 2 (r - img) / (B*3*H*W) + g_recon, r recomputed; g_loss: DEVICE fp32 or NULL (= 1); g_recon: fp32 [B,3,H,W] or NULL (= 0);
+ * e is zero outside the image.
+ *   dy = the input gradient of the convolution at e, in token layout and in y's type (bf16: one round-to-nearest-even), row stride ld_dy,
+ *        columns 3*p*p .. ld_dy untouched.  dy == y is VITAMD_ERR_ARG: a tile reads its neighbours' tokens, so this call is never in place.
+ *   dw[co,ci,kh,kw] = sum over b, y, x of e[b,co,y,x] * yimg[b,ci,y+kh-1,x+kw-1],  db[co] = sum of e[b,co,y,x]   (both OVERWRITTEN)
+ * Each pixel's e is counted once (by the tile that owns it); per-thread sums, then lanes, waves and tiles in a fixed order, no float
+ * atomics: the same inputs give the same bits in dy, dw and db. */
+int vitamd_conv_recon_mse_bwd(const void* y, int y_bf16, const float* w, const float* bias, const float* img, const float* g_loss,
+                              const float* g_recon, void* dy, float* dw, float* db, float* ws, int B, int G, int p, int ld, int ld_dy,
+                              void* stream);
+
 /* ---- the ConvNeXt-S perceptual loss of the tokenizers ---------------------
  * The frozen network of perceptual_loss.py:41 runs on channels-last activation rows [B*H*W, C]: its Linears, LayerNorms and strided
  * convolutions are vitamd_gemm_nt_bf16 / vitamd_layernorm_affine_* calls; the entry points below are the rest.  Every call only enqueues

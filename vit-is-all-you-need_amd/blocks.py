@@ -295,12 +295,22 @@ class TiTokDecoder(nn.Module):
         canvas = (canvas + self.positional_embedding).to(latents.dtype).expand(batch, -1, -1)
         return torch.cat([canvas, latents], dim=1)
 
-    def _pixels(self, x):
-        batchsize, g, p = x.shape[0], self.grid_size, self.patch_size
+    def _grid_rows(self, x):
+        """the stack on a decoder input sequence -> the ln_post rows of the grid tokens [B, grid**2, width]"""
+        g = self.grid_size
         x = _ln(self.ln_pre, x)
         for blk in self.transformer:
             x = blk.forward_nld(x)
-        x = _ln(self.ln_post, x[:, 1:1 + g * g])                                   # remove cls embed
+        return _ln(self.ln_post, x[:, 1:1 + g * g])                                # remove cls embed
+
+    def features(self, z_quantized):
+        """quantised latents [B, C, 1, N] -> what the pixel head (`ffn`, `conv_out`) is applied to: the ln_post rows of the grid tokens.
+        forward() = the head on these rows; vitamd.tokenizer.linear_conv_recon_mse takes them to the reconstruction loss directly."""
+        return self._grid_rows(self._tokens(z_quantized))
+
+    def _pixels(self, x):
+        batchsize, g, p = x.shape[0], self.grid_size, self.patch_size
+        x = self._grid_rows(x)
         y = _conv1x1_tokens(self.ffn[0], x)                                         # [B, grid**2, p*p*3], token t = (h, w)
         img = y.view(batchsize, g, g, p, p, 3).permute(0, 5, 1, 3, 2, 4).reshape(batchsize, 3, g * p, g * p)
         return Conv3x3Fn.apply(img, self.conv_out.weight, self.conv_out.bias)

@@ -10,8 +10,10 @@ fp32, no padding, nothing left to the framework's ops.  `train_step` is one iter
 runs it on seeded random tokens.  The greedy argmax of generation is a torch device op; sampled generation (temperature / top-k /
 top-p) draws each token in one HIP kernel (csrc/sample.hip).  `generate` adds a KV cache (vitamd/decode.py): the prompt is prefilled
 once and every further token costs one single-row pass through the stack - with graph=True one graph launch (vitamd/graph.py
-GraphedDecoder).  The reference's data loading and its external TiTok video tokenizer (train_videogpt.py:92-128) are not part of this
-module."""
+GraphedDecoder).  `frames_to_tokens` and `tokens_to_frames` are the reference loop's two uses of its frame tokenizer
+(train_videogpt.py:122-127 and :148-156) for any object with `encode(x) -> (z_q, {"min_encoding_indices": ...})` and
+`decode_tokens(ids) -> frames` - train_tatitok.TiTok is one - and `main(--tokenizer tatitok)` trains on the code ids of seeded random
+frames and decodes a generated continuation.  The reference's data loading is not part of this module."""
 import argparse
 import time
 from dataclasses import dataclass
@@ -192,6 +194,44 @@ class VideoGPT(nn.Module):
                              top_k=top_k, top_p=top_p, seed=seed, graph=graph)
 
 
+@torch.no_grad()
+def frames_to_tokens(tokenizer, videos):
+    """videos [B, T, 3, H, W] -> code ids int64 [B, T, N] (train_videogpt.py:122-127): every frame through tokenizer.encode, in eval mode
+    and without a graph; the tokenizer's training flag is put back"""
+    if videos.dim() != 5:
+        raise ValueError(f"frames_to_tokens: expected videos [B, T, C, H, W], got {tuple(videos.shape)}")
+    B, T = videos.shape[:2]
+    was_training = getattr(tokenizer, "training", False)
+    if was_training:
+        tokenizer.eval()
+    try:
+        _, info = tokenizer.encode(videos.reshape(B * T, *videos.shape[2:]))
+    finally:
+        if was_training:
+            tokenizer.train()
+    ids = info["min_encoding_indices"]
+    if ids.dim() == 3:
+        ids = ids.squeeze(1)                                     # [B*T, 1, N] -> [B*T, N]
+    return ids.reshape(B, T, -1).long()
+
+
+@torch.no_grad()
+def tokens_to_frames(tokenizer, tokens, T):
+    """flattened code ids [B, T*N] (what generate_frames returns) -> frames [B, T, 3, H, W] clamped to [0, 1] (train_videogpt.py:148-156)"""
+    if tokens.dim() != 2 or T < 1 or tokens.shape[1] % T:
+        raise ValueError(f"tokens_to_frames: expected tokens [B, T*N] with T = {T}, got {tuple(tokens.shape)}")
+    B = tokens.shape[0]
+    was_training = getattr(tokenizer, "training", False)
+    if was_training:
+        tokenizer.eval()
+    try:
+        frames = tokenizer.decode_tokens(tokens.reshape(B * T, -1))
+    finally:
+        if was_training:
+            tokenizer.train()
+    return torch.clamp(frames, 0.0, 1.0).reshape(B, T, *frames.shape[1:])
+
+
 def train_step(model, tokens, optim, lr_sched=None):
     """One iteration of the reference hot loop (train_videogpt.py:130-136) without the fp16 scaler, on VideoGPT.loss."""
     optim.zero_grad(set_to_none=True)
@@ -217,7 +257,21 @@ def parse_args(argv=None):
     p.add_argument("--train_steps", type=int, default=50)
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
+    p.add_argument("--tokenizer", type=str, default="none", choices=("none", "tatitok"),
+                   help="none: seeded random token ids; tatitok: a random-weight train_tatitok.TiTok (latent_tokens = frame_size) tokenises "
+                        "seeded random frames and decodes one generated continuation at the end")
+    p.add_argument("--image_size", type=int, default=64, help="frame side for --tokenizer tatitok")
+    p.add_argument("--patch_size", type=int, default=16, help="patch side for --tokenizer tatitok")
+    p.add_argument("--condition_frames", type=int, default=1, help="frames the final generation is conditioned on (--tokenizer tatitok)")
     return p.parse_args(argv)
+
+
+def make_tatitok(args, device):
+    """a random-weight 1D TiTok whose frames have args.frame_size code ids out of args.codebook_size"""
+    import train_tatitok as TA
+    torch.manual_seed(0)
+    cfg = TA.TiTokConfig(args.image_size, args.patch_size, args.frame_size, args.codebook_size, 12, "small")
+    return TA.TiTok(cfg).to(device).eval()
 
 
 def make_optim(model, args):
@@ -227,20 +281,32 @@ def make_optim(model, args):
     return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
 
 
-def main():
-    args = parse_args()
+def main(argv=None):
+    args = parse_args(argv)
     dev = torch.device("cuda")
     cfg = VideoGPTConfig(args.frame_size, args.codebook_size, args.transformer, args.max_frames, args.dropout)
     model = VideoGPT(cfg).to(dev)
     optim = make_optim(model, args)
     sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
     g = torch.Generator(device="cpu").manual_seed(0)
-    tokens = torch.randint(0, args.codebook_size, (args.bs, args.max_frames, args.frame_size), generator=g).to(dev)
+    titok = None
+    if args.tokenizer == "tatitok":
+        titok = make_tatitok(args, dev)
+        videos = torch.rand((args.bs, args.max_frames, 3, args.image_size, args.image_size), generator=g).to(dev)
+        tokens = frames_to_tokens(titok, videos)
+    else:
+        tokens = torch.randint(0, args.codebook_size, (args.bs, args.max_frames, args.frame_size), generator=g).to(dev)
     for step in range(args.train_steps):
         t0 = time.time()
         loss = train_step(model, tokens, optim, sched)
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} {tokens.numel() / (time.time() - t0):.0f} tokens/s")
+    if titok is not None:
+        model.eval()
+        cond = min(max(args.condition_frames, 1), args.max_frames - 1)
+        gen = model.generate_frames(tokens[:1, :cond], n=args.max_frames - cond)
+        frames = tokens_to_frames(titok, gen, args.max_frames)
+        print(f"generated {tuple(frames.shape)} frames from {cond} conditioning frame(s): min {float(frames.min()):.3f} max {float(frames.max()):.3f}")
 
 
 if __name__ == "__main__":

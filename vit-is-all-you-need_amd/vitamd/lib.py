@@ -83,6 +83,11 @@ SIGNATURES = {
     "vitamd_recon_mse_ws_bytes": [_I, _I, _I, _I, _I],
     "vitamd_recon_mse_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_recon_mse_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vitamd_vq_quantize_unit_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "vitamd_vq_quantize_unit_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "vitamd_conv_recon_mse_ws_bytes": [_I, _I, _I, _I, _I],
+    "vitamd_conv_recon_mse_fwd": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vitamd_conv_recon_mse_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_dwconv7_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "vitamd_dwconv7_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "vitamd_resize_norm_fwd": [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

@@ -926,6 +926,115 @@ def recon_mse_bwd(tokens, images, grid, patch, grad_out=None, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ the 1D TiTok tokenizer's kernels
+def vq_quantize_unit_fwd(x, codebook, return_unit_codes=False):
+    """vq_quantize_fwd with UNIT codes (include/vitamd.h vitamd_vq_quantize_unit_fwd: blocks.VectorQuantizer(use_l2_norm=True)): q and
+    the loss are taken on the normalised code rows.  Same arguments and results."""
+    M, K, d = _need_vq(x, codebook, "vq_quantize_unit_fwd")
+    dev = x.device
+    unit, q = torch.empty((M, d), dtype=F32, device=dev), torch.empty((M, d), dtype=F32, device=dev)
+    rnorm = torch.empty((M,), dtype=F32, device=dev)
+    idx = torch.empty((M,), dtype=torch.int64, device=dev)
+    loss = torch.empty((), dtype=F32, device=dev)
+    ws = torch.empty((int(_L().vitamd_vq_quantize_ws_bytes(M, K, d)) // 4,), dtype=F32, device=dev)
+    _lib.check(_L().vitamd_vq_quantize_unit_fwd(_p(x), _p(codebook), _p(unit), _p(rnorm), _p(q), _p(idx), _p(loss), _p(ws), M, K, d, _stream()),
+               f"vq_quantize_unit_fwd[M={M},K={K},d={d}]")
+    return (unit, rnorm, q, idx, loss) + ((ws[:K * d].view(K, d),) if return_unit_codes else ())
+
+
+def vq_quantize_unit_bwd(g_q, g_loss, unit, rnorm, idx, codebook, dcodebook=None):
+    """vq_quantize_bwd with UNIT codes: the codebook gradient goes through the normalisation (include/vitamd.h vitamd_vq_quantize_unit_bwd).
+    `codebook` is the raw codebook.  -> (dx fp32 [M, d], dcodebook fp32 [K, d])"""
+    M, K, d = _need_vq(unit, codebook, "vq_quantize_unit_bwd")
+    _need(rnorm, F32, "rnorm", 1); _need(idx, torch.int64, "idx", 1)
+    if rnorm.numel() != M or idx.numel() != M:
+        raise _lib.VitamdError(f"vq_quantize_unit_bwd: expected rnorm [{M}] and idx [{M}]")
+    if g_q is not None:
+        _need(g_q, F32, "g_q", 2)
+        if tuple(g_q.shape) != (M, d):
+            raise _lib.VitamdError(f"g_q: expected [{M}, {d}], got {tuple(g_q.shape)}")
+    if g_loss is not None:
+        _need(g_loss, F32, "g_loss")
+        if g_loss.numel() != 1:
+            raise _lib.VitamdError("g_loss: expected a one-element device fp32")
+    if dcodebook is None:
+        dcodebook = torch.zeros((K, d), dtype=F32, device=unit.device)
+    _need(dcodebook, F32, "dcodebook", 2)
+    if tuple(dcodebook.shape) != (K, d):
+        raise _lib.VitamdError(f"dcodebook: expected [{K}, {d}], got {tuple(dcodebook.shape)}")
+    dx = torch.empty((M, d), dtype=F32, device=unit.device)
+    _lib.check(_L().vitamd_vq_quantize_unit_bwd(_p(g_q), _p(g_loss), _p(unit), _p(rnorm), _p(idx), _p(codebook), _p(dx), _p(dcodebook), M, K, d,
+                                                _stream()), f"vq_quantize_unit_bwd[M={M},K={K},d={d}]")
+    return dx, dcodebook
+
+
+def conv_recon_mse_applies(tokens, patch):
+    """whether the pixel-tail kernels take these tokens (their 16-byte path: recon_mse_applies' alignment rules, and a patch side that is
+    a multiple of 8 for bf16 / 4 for fp32); callers take the present operators otherwise"""
+    if not isinstance(patch, int) or patch < 1 or not recon_mse_applies(tokens):
+        return False
+    return patch % (8 if tokens.dtype == BF16 else 4) == 0 and tokens.shape[1] == 3 * patch * patch
+
+
+def _need_conv_recon(tokens, w, bias, images, grid, patch, what):
+    """_need_recon with c = 3, w fp32 [3, 3, 3, 3], bias fp32 [3] -> (B, ld, is_bf16); shape errors before any device is looked at"""
+    if not isinstance(w, torch.Tensor) or not isinstance(bias, torch.Tensor) or tuple(w.shape) != (3, 3, 3, 3) or tuple(bias.shape) != (3,):
+        raise ValueError(f"{what}: expected a convolution weight [3, 3, 3, 3] and bias [3]")
+    if isinstance(images, torch.Tensor) and images.dim() == 4 and images.shape[1] != 3:
+        raise ValueError(f"{what}: expected three image channels, got images {tuple(images.shape)}")
+    B, _, ld, is_bf16 = _need_recon(tokens, images, grid, patch, what)
+    _need(w, F32, "conv weight", 4); _need(bias, F32, "conv bias", 1)
+    return B, ld, is_bf16
+
+
+def _conv_recon_ws(B, grid, patch, is_bf16, backward, device, what):
+    nbytes = int(_L().vitamd_conv_recon_mse_ws_bytes(B, grid, patch, is_bf16, backward))
+    _lib.check(-nbytes if nbytes < 0 else 0, f"{what}[B={B},G={grid},p={patch}]")
+    return torch.empty((nbytes // 4,), dtype=F32, device=device)
+
+
+def conv_recon_mse_fwd(tokens, w, bias, images, grid, patch, want_recon=False):
+    """mean((conv3x3(pixel_shuffle(tokens), w, padding 1) + bias - images)^2) as a 0-dim device fp32 and, with want_recon, the convolved
+    image fp32 [B, 3, H, W] (else None); the shuffled image is never formed (include/vitamd.h vitamd_conv_recon_mse_fwd).  Shapes outside
+    the kernel's 16-byte path raise (conv_recon_mse_applies tells beforehand)."""
+    B, ld, is_bf16 = _need_conv_recon(tokens, w, bias, images, grid, patch, "conv_recon_mse_fwd")
+    ws = _conv_recon_ws(B, grid, patch, is_bf16, 0, tokens.device, "conv_recon_mse_fwd")
+    loss = torch.empty((), dtype=F32, device=tokens.device)
+    recon = torch.empty(tuple(images.shape), dtype=F32, device=tokens.device) if want_recon else None
+    _lib.check(_L().vitamd_conv_recon_mse_fwd(_p(tokens), is_bf16, _p(w), _p(bias), _p(images), _p(loss), _p(recon), _p(ws), B, grid, patch, ld,
+                                              _stream()), f"conv_recon_mse_fwd[B={B},G={grid},p={patch},ld={ld}]")
+    return loss, recon
+
+
+def conv_recon_mse_bwd(tokens, w, bias, images, grid, patch, g_loss=None, g_recon=None, out=None):
+    """-> (dtokens in the tokens' layout and dtype, dw fp32 [3, 3, 3, 3], db fp32 [3]) at e = g_loss * 2 (r - images) / images.numel()
+    + g_recon.  g_loss: device fp32 scalar (None = 1); g_recon: fp32 [B, 3, H, W] (None = 0).  out: where dtokens go (never the tokens
+    themselves); None allocates a dense tensor.  The same bits on every call."""
+    B, ld, is_bf16 = _need_conv_recon(tokens, w, bias, images, grid, patch, "conv_recon_mse_bwd")
+    if g_loss is not None:
+        _need(g_loss, F32, "g_loss")
+        if g_loss.numel() != 1:
+            raise _lib.VitamdError("g_loss: expected a one-element device fp32")
+    if g_recon is not None:
+        _need(g_recon, F32, "g_recon", 4)
+        if tuple(g_recon.shape) != tuple(images.shape):
+            raise _lib.VitamdError(f"g_recon: expected {tuple(images.shape)}, got {tuple(g_recon.shape)}")
+    if out is None:
+        out = torch.empty(tuple(tokens.shape), dtype=tokens.dtype, device=tokens.device)
+    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != tokens.dtype or tuple(out.shape) != tuple(tokens.shape)
+            or out.stride(1) != 1 or out.stride(0) < out.shape[1]):
+        raise _lib.VitamdError("conv_recon_mse_bwd: out must be a device tensor of the tokens' shape and dtype with unit inner stride")
+    if out.data_ptr() == tokens.data_ptr():
+        raise _lib.VitamdError("conv_recon_mse_bwd: the gradient cannot overwrite the tokens (neighbouring tiles re-read them)")
+    ws = _conv_recon_ws(B, grid, patch, is_bf16, 1, tokens.device, "conv_recon_mse_bwd")
+    dw = torch.empty((3, 3, 3, 3), dtype=F32, device=tokens.device)
+    db = torch.empty((3,), dtype=F32, device=tokens.device)
+    _lib.check(_L().vitamd_conv_recon_mse_bwd(_p(tokens), is_bf16, _p(w), _p(bias), _p(images), _p(g_loss), _p(g_recon), _p(out), _p(dw), _p(db),
+                                              _p(ws), B, grid, patch, ld, out.stride(0), _stream()),
+               f"conv_recon_mse_bwd[B={B},G={grid},p={patch},ld={ld}]")
+    return out, dw, db
+
+
 # ------------------------------------------------------------------------------------------ the perceptual loss (DESIGN.md section 14)
 def _need_dwconv(x, w, what):
     """x fp32 / bf16 rows [B, H, W, C] (channels last, contiguous), w fp32 [C, 7, 7] -> (B, H, W, C, is_bf16); shape errors before any

@@ -5,6 +5,12 @@ head (csrc/tokenizer.hip).
     loss = tokenizer.recon_mse(tokens, images, grid, patch)                      # mse_loss(pixel_shuffle_tokens(tokens), images)
     loss = tokenizer.linear_recon_mse(h, embd_proj.weight, embd_proj.bias, images, grid, patch)   # head GEMM -> bf16 tokens -> loss
 
+and the 1D TiTok of train_tatitok (blocks.TiTokDecoder's tail, blocks.VectorQuantizer(use_l2_norm=True)):
+
+    q, ids, qloss = tokenizer.vq_quantize(latents, quantize.embedding.weight, unit_codes=True)    # normalised codes out, gradient through the norm
+    loss = tokenizer.conv_recon_mse(tokens, conv_out.weight, conv_out.bias, images, grid, patch)  # mse(conv3x3(pixel_shuffle(tokens)), images)
+    loss, recon = tokenizer.linear_conv_recon_mse(h, ffn0.weight, ffn0.bias, conv_out.weight, conv_out.bias, images, grid, patch, return_recon=True)
+
 Every value the backward needs stays on the device (upstream gradients are read by the kernels).
 """
 from __future__ import annotations
@@ -53,9 +59,49 @@ class VQQuantizeFn(torch.autograd.Function):
         return dx.view(*ctx.lead, unit.shape[1]), dcb
 
 
-def vq_quantize(x, codebook_weight):
+def vq_quantize_unit_torch(x, codebook_weight):
+    """blocks.VectorQuantizer(use_l2_norm=True, commitment_cost=0.25).forward on [..., d] rows, as torch device ops around the nearest-code
+    kernel: the route of wide codes"""
+    normalize = torch.nn.functional.normalize
+    unit = normalize(x, dim=-1)
+    with torch.no_grad():
+        ids = ops.vq_nearest(unit.reshape(-1, unit.shape[-1]).float().contiguous(),
+                             normalize(codebook_weight, dim=-1).float().contiguous()).view(unit.shape[:-1])
+    picked = normalize(torch.nn.functional.embedding(ids, codebook_weight), dim=-1)
+    sq = lambda t: t.pow(2).mean()
+    loss = 0.25 * sq(picked.detach() - unit) + sq(picked - unit.detach())
+    return unit + (picked - unit).detach(), ids, loss
+
+
+class VQQuantizeUnitFn(torch.autograd.Function):
+    """VQQuantizeFn on the unit-code kernels: q and the loss on the normalised rows, the codebook gradient through the normalisation"""
+
+    @staticmethod
+    def forward(ctx, x, codebook):
+        lead, d = x.shape[:-1], x.shape[-1]
+        x2 = x.detach().reshape(-1, d).contiguous()
+        cb = codebook.detach().contiguous()
+        unit, rnorm, q, idx, loss = ops.vq_quantize_unit_fwd(x2, cb)
+        ctx.save_for_backward(unit, rnorm, idx, cb)
+        ctx.lead = tuple(lead)
+        ids = idx.view(lead)
+        ctx.mark_non_differentiable(ids)
+        return q.view(*lead, d), ids, loss
+
+    @staticmethod
+    def backward(ctx, g_q, _g_ids, g_loss):
+        unit, rnorm, idx, cb = ctx.saved_tensors
+        gq = None if g_q is None else g_q.detach().to(F32).reshape(unit.shape).contiguous()
+        gl = None if g_loss is None else _scalar(g_loss)
+        dx, dcb = ops.vq_quantize_unit_bwd(gq, gl, unit, rnorm, idx, cb)
+        return dx.view(*ctx.lead, unit.shape[1]), dcb
+
+
+def vq_quantize(x, codebook_weight, unit_codes=False):
     """train_titok.Quantizer.forward on x fp32 [..., d] and the codebook fp32 [K, d] -> (q [..., d], ids int64 [...], loss 0-dim):
     q = unit + (picked - unit) with the straight-through gradient, loss = |picked - sg(unit)|^2 + 0.25 |sg(picked) - unit|^2 (means).
+    unit_codes: picked = normalize(codebook[ids]) instead of the raw rows, the codebook gradient taken through the normalisation -
+    blocks.VectorQuantizer(use_l2_norm=True, commitment_cost=0.25).forward on channels-last rows.
     d <= 64: the two quantiser kernels; wider codes: the present torch expressions around ops.vq_nearest."""
     if not isinstance(x, torch.Tensor) or not isinstance(codebook_weight, torch.Tensor) or x.dim() < 1 or codebook_weight.dim() != 2 \
             or x.shape[-1] != codebook_weight.shape[1]:
@@ -65,8 +111,8 @@ def vq_quantize(x, codebook_weight):
     if not x.is_cuda or not codebook_weight.is_cuda:
         raise ops._lib.VitamdError("vq_quantize: expected ROCm device tensors (the HIP kernels are the only implementation)")
     if x.shape[-1] > ops.VQ_MAX_D:
-        return vq_quantize_torch(x, codebook_weight)
-    return VQQuantizeFn.apply(x, codebook_weight)
+        return vq_quantize_unit_torch(x, codebook_weight) if unit_codes else vq_quantize_torch(x, codebook_weight)
+    return VQQuantizeUnitFn.apply(x, codebook_weight) if unit_codes else VQQuantizeFn.apply(x, codebook_weight)
 
 
 # ------------------------------------------------------------------------------------------------ reconstruction loss
@@ -179,3 +225,127 @@ def linear_recon_mse(h, weight, bias, images, grid, patch):
     if not fused_head_applies(F, D):
         return recon_mse(linear(h, weight, bias).reshape(B, grid * grid, F), images, grid, patch)
     return LinearReconMSEFn.apply(h.reshape(-1, D), weight, bias, images, grid, patch)
+
+
+# ------------------------------------------------------------------------------------------------ pixel tail of blocks.TiTokDecoder
+def _zero_scalar(like):
+    return torch.zeros((), dtype=F32, device=like.device)
+
+
+def _check_conv_tail(what, rows, F, conv_w, conv_b, images, grid, patch):
+    """shape and argument errors of the two pixel-tail entry points, before any device is looked at -> B"""
+    if not isinstance(conv_w, torch.Tensor) or not isinstance(conv_b, torch.Tensor) or not isinstance(images, torch.Tensor) or images.dim() != 4:
+        raise ops._lib.VitamdError(f"{what}: expected conv weight [3, 3, 3, 3], conv bias [3] and images [B, 3, H, W]")
+    B, c, H, Wd = images.shape
+    if tuple(conv_w.shape) != (3, 3, 3, 3) or tuple(conv_b.shape) != (3,) or c != 3:
+        raise ValueError(f"{what}: conv weight {tuple(conv_w.shape)}, bias {tuple(conv_b.shape)} and images {tuple(images.shape)} are not "
+                         "those of Conv2d(3, 3, 3, padding=1)")
+    if grid < 1 or patch < 1 or H != grid * patch or Wd != grid * patch or F != patch * patch * 3 or rows != B * grid * grid:
+        raise ValueError(f"{what}: {rows} token rows of width {F} and images {tuple(images.shape)} do not fit grid {grid}, patch {patch}")
+    return B
+
+
+class ConvReconMSEFn(torch.autograd.Function):
+    """(loss, recon or None) of the pixel tail on tokens that exist already; the backward takes the gradients of both outputs at once"""
+
+    @staticmethod
+    def forward(ctx, tokens, conv_w, conv_b, images, grid, patch, want_recon):
+        t = _rows(tokens)
+        img, w, b = _f32c(images), _f32c(conv_w), _f32c(conv_b)
+        loss, recon = ops.conv_recon_mse_fwd(t, w, b, img, grid, patch, want_recon)
+        ctx.save_for_backward(t, w, b, img)
+        ctx.meta = (tuple(tokens.shape), grid, patch)
+        ctx.set_materialize_grads(False)
+        return loss, recon
+
+    @staticmethod
+    def backward(ctx, g_loss, g_recon):
+        t, w, b, img = ctx.saved_tensors
+        shape, grid, patch = ctx.meta
+        gl = _zero_scalar(t) if g_loss is None else _scalar(g_loss)
+        dt, dw, db = ops.conv_recon_mse_bwd(t, w, b, img, grid, patch, gl, None if g_recon is None else _f32c(g_recon))
+        return dt.view(shape), dw, db, None, None, None, None
+
+
+def _conv_tail_torch(tokens3, conv_w, conv_b, images, grid, patch, return_recon):
+    """the present operators: pixel-shuffle copy -> Conv3x3Fn -> mse_loss"""
+    from .block_functions import Conv3x3Fn
+    recon = Conv3x3Fn.apply(pixel_shuffle_tokens(tokens3.float(), grid, patch), conv_w, conv_b)
+    loss = torch.nn.functional.mse_loss(recon, images)
+    return (loss, recon) if return_recon else loss
+
+
+def conv_recon_mse(tokens, conv_w, conv_b, images, grid, patch, return_recon=False):
+    """mse_loss(conv3x3(pixel_shuffle_tokens(tokens), conv_w, padding 1) + conv_b, images) for tokens fp32 or bf16 [B, grid*grid, 3*patch*patch]
+    (or [B*grid*grid, ...]), conv_w fp32 [3, 3, 3, 3], conv_b fp32 [3], images fp32 [B, 3, grid*patch, grid*patch]: the 0-dim fp32 loss in
+    one kernel, fp32 arithmetic on the tokens as stored, the shuffled image never formed.  return_recon: -> (loss, recon fp32 [B, 3, H, W]),
+    the convolved image as a second differentiable output; a gradient arriving on it joins the loss's own inside the backward kernel.
+    The token gradient comes back in the tokens' dtype.  Shapes outside the kernels' 16-byte path (patch % 8 for bf16, % 4 for fp32,
+    alignment) take the present operators."""
+    if not isinstance(tokens, torch.Tensor) or tokens.dim() not in (2, 3):
+        raise ops._lib.VitamdError("conv_recon_mse: expected tokens [B, grid*grid, F]")
+    B = _check_conv_tail("conv_recon_mse", tokens.numel() // max(tokens.shape[-1], 1), tokens.shape[-1], conv_w, conv_b, images, grid, patch)
+    if not tokens.is_cuda or not images.is_cuda or not conv_w.is_cuda or not conv_b.is_cuda:
+        raise ops._lib.VitamdError("conv_recon_mse: expected ROCm device tensors (the HIP kernels are the only implementation)")
+    if not ops.conv_recon_mse_applies(_rows(tokens), patch):
+        return _conv_tail_torch(tokens.reshape(B, grid * grid, -1), conv_w, conv_b, images, grid, patch, return_recon)
+    loss, recon = ConvReconMSEFn.apply(tokens, conv_w, conv_b, images, grid, patch, bool(return_recon))
+    return (loss, recon) if return_recon else loss
+
+
+class LinearConvReconMSEFn(torch.autograd.Function):
+    """(loss, recon or None) = conv_recon_mse(h W^T + b, ...) with bf16 tokens written once by the head GEMM and read by the tail kernel;
+    the backward writes their gradient to a second buffer (a tile re-reads its neighbours' tokens) and feeds it to the two gradient GEMMs
+    and the bias column sum.  One backward per forward, as LinearReconMSEFn."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, h, weight, bias, conv_w, conv_b, images, grid, patch, want_recon):
+        hb = ops.cast_bf16(_f32c(h))
+        wb, _ = WEIGHTS.get(weight, True)
+        tokens = ops.gemm_nt(hb, wb, ops.EPI_BIAS_BF16, bias=None if bias is None else _f32c(bias))
+        img, cw, cb = _f32c(images), _f32c(conv_w), _f32c(conv_b)
+        loss, recon = ops.conv_recon_mse_fwd(tokens, cw, cb, img, grid, patch, want_recon)
+        ctx.save_for_backward(hb, tokens, img, cw, cb)
+        ctx.weight = weight
+        ctx.meta = (h.dtype, bias is not None, grid, patch)
+        ctx.consumed = False
+        ctx.set_materialize_grads(False)
+        return loss, recon
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g_loss, g_recon):
+        if ctx.consumed:
+            raise RuntimeError("linear_conv_recon_mse: one backward per forward (the contract of linear_recon_mse); "
+                               "a second backward through the same loss needs a new forward")
+        ctx.consumed = True
+        hb, tokens, img, cw, cb = ctx.saved_tensors
+        hdtype, has_bias, grid, patch = ctx.meta
+        weight = ctx.weight
+        _, wbt = WEIGHTS.get(weight, True)
+        gl = _zero_scalar(tokens) if g_loss is None else _scalar(g_loss)
+        dy, dcw, dcb = ops.conv_recon_mse_bwd(tokens, cw, cb, img, grid, patch, gl, None if g_recon is None else _f32c(g_recon))
+        dx = ops.gemm_nt(dy, wbt, ops.EPI_BIAS_BF16).to(hdtype) if ctx.needs_input_grad[0] else None
+        dW = torch.empty((weight.shape[0], weight.numel() // weight.shape[0]), dtype=F32, device=dy.device)
+        ops.gemm_tn(dy, hb, dW, accumulate=False)
+        db = ops.colsum(dy) if has_bias else None
+        return dx, dW.view(weight.shape), db, dcw, dcb, None, None, None, None
+
+
+def linear_conv_recon_mse(h, ffn_w, ffn_b, conv_w, conv_b, images, grid, patch, return_recon=False):
+    """conv_recon_mse(nn.Linear(h), ...) for h [..., D] (B*grid*grid rows), ffn_w fp32 [F, D] (or a 1x1 conv's [F, D, 1, 1]), ffn_b fp32 [F]
+    or None - blocks.TiTokDecoder's `ffn` and `conv_out` on the ln_post rows.  F % 64 == 0 and D % 64 == 0 and a patch the tail kernels
+    take: the fused head (LinearConvReconMSEFn: bf16 tokens written once; one backward per forward).  Other shapes: functions.linear
+    followed by conv_recon_mse.  return_recon as conv_recon_mse."""
+    if not isinstance(h, torch.Tensor) or not isinstance(ffn_w, torch.Tensor) or h.dim() < 1 or ffn_w.dim() < 2 \
+            or ffn_w.numel() != ffn_w.shape[0] * h.shape[-1]:
+        raise ops._lib.VitamdError("linear_conv_recon_mse: expected h [..., D] and ffn weight [F, D]")
+    F, D = ffn_w.shape[0], h.shape[-1]
+    B = _check_conv_tail("linear_conv_recon_mse", h.numel() // max(D, 1), F, conv_w, conv_b, images, grid, patch)
+    if not h.is_cuda or not ffn_w.is_cuda or not images.is_cuda or not conv_w.is_cuda or not conv_b.is_cuda:
+        raise ops._lib.VitamdError("linear_conv_recon_mse: expected ROCm device tensors (the HIP kernels are the only implementation)")
+    if not fused_head_applies(F, D) or patch % 8 != 0:
+        return conv_recon_mse(linear(h, ffn_w, ffn_b).reshape(B, grid * grid, F), conv_w, conv_b, images, grid, patch, return_recon)
+    loss, recon = LinearConvReconMSEFn.apply(h.reshape(-1, D), ffn_w, ffn_b, conv_w, conv_b, images, grid, patch, bool(return_recon))
+    return (loss, recon) if return_recon else loss
