@@ -296,6 +296,28 @@ int vitamd_embed_tokens_fwd(const float* tok_table, const float* pos_table, cons
  * last bits, as vitamd_embed_bwd's outputs are), each wave-instruction adding 64 contiguous floats of one row.  Both are ACCUMULATED
  * into: zero them for a fresh gradient.  Ids out of range add nothing to dtok.  D % 4 == 0. */
 int vitamd_embed_tokens_bwd(const float* g, const long long* ids, float* dtok, float* dpos, int B, int S, int D, int tok_rows, void* stream);
+/* Sequence assembly of the code-id TiTok: x fp32 [B, E+S, D], x[b, e, :] = prefix[e, :] for e < E and
+ * x[b, E+t, :] = src(b, t) + pos[t, :], one fp32 add per element (bit-equal to the framework's embedding / add / expand / cat).
+ * Gather mode (tok_table and ids given, body NULL): src(b, t) = tok_table[ids[b*S+t], :], ids int64 [B, S]; an id outside [0, tok_rows)
+ * leaves that row of x untouched and no table is read out of bounds (as vitamd_embed_tokens_fwd).  Dense mode (body given, tok_table and
+ * ids NULL): src(b, t) = body[b*S+t, :], body fp32 [B*S, D].  prefix fp32 [E, D] (NULL allowed when E == 0), pos fp32 [pos_rows, D].
+ * B >= 1, E >= 0, S >= 1, D % 4 == 0, pos_rows >= S, tok_rows >= 1 in gather mode, else VITAMD_ERR_SHAPE; a missing pointer, both
+ * sources or neither: VITAMD_ERR_ARG (after the shape check, before any launch).  16-byte accesses; the grid is capped at
+ * vitamd_assemble_tokens_grid_cap() workgroups with a stride loop beyond.  Only enqueues on `stream`.
+ * replaces train_llamagen_titok.py:43-46 (tok_emb(x) + pos_emb, extra_emb in front) and :80-82 (quant_proj(z) + pos_emb, mask_tokens in front). */
+int vitamd_assemble_tokens_fwd(const float* prefix, const float* pos, const float* tok_table, const long long* ids, const float* body,
+                               float* x, int B, int E, int S, int D, int tok_rows, int pos_rows, void* stream);
+/* Its backward.  g fp32 [B, E+S, D] is read ONCE.  dprefix fp32 [E, D] += sum over b of g[b, e]; dpos fp32 [pos_rows, D]: rows t < S +=
+ * sum over b of g[b, E+t]; both sums are taken in ascending b by the one wave that owns (position, 256 columns): no atomics, reproducible
+ * bits.  Gather mode (ids and dtok given): dtok fp32 [tok_rows, D] += g[b, E+t] at row ids[b*S+t] by fp32 atomics (order-dependent in
+ * the last bits), each wave-instruction adding 64 contiguous floats; ids out of range add nothing.  Dense mode (ids and dtok NULL): the
+ * body's gradient is the view g[:, E:], nothing is written for it.  All three outputs are ACCUMULATED into.  Shapes, errors, grid cap
+ * and stream rule as the forward's (dprefix may be NULL when E == 0; one of ids / dtok without the other: VITAMD_ERR_ARG). */
+int vitamd_assemble_tokens_bwd(const float* g, const long long* ids, float* dprefix, float* dpos, float* dtok, int B, int E, int S, int D,
+                               int tok_rows, int pos_rows, void* stream);
+/* Workgroups per launch of the two assembly kernels (the cap of their grids), for tests that have to cross it: the forward needs
+ * B * (E+S) * D / 4 / 256 workgroups, the backward (E+S) * ceil(D / 256) / 4. */
+int vitamd_assemble_tokens_grid_cap(void);
 
 /* ---- helpers around the GEMMs ---------------------------------------------------------------- */
 /* fp32 -> bf16 (autocast's per-step weight / activation cast, train_vit.py:100). */

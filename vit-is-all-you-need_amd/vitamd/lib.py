@@ -77,6 +77,9 @@ SIGNATURES = {
     "vitamd_cross_entropy_bwd": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _P],
     "vitamd_embed_tokens_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_embed_tokens_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vitamd_assemble_tokens_grid_cap": [],
+    "vitamd_assemble_tokens_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vitamd_assemble_tokens_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vitamd_vq_quantize_ws_bytes": [_I, _I, _I],
     "vitamd_vq_quantize_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vitamd_vq_quantize_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],

@@ -4,6 +4,8 @@ token + position embedding (csrc/loss.hip).
     loss = lm.cross_entropy(logits, target)                       # F.cross_entropy(logits.float(), target), mean, on the device
     loss = lm.linear_cross_entropy(h, proj.weight, proj.bias, y)  # head GEMM -> bf16 logits -> loss, nothing in fp32 in between
     x = lm.token_embed(ids, tok_embed.weight, pos_embed.weight)   # tok[ids] + pos[:S], fp32
+    x = lm.prefixed_token_embed(ids, tok, pos, prefix)            # cat([prefix rows, tok[ids] + pos[:S]], 1), one kernel (csrc/assemble.hip)
+    x = lm.prefixed_rows(body, pos, prefix)                       # cat([prefix rows, body + pos[:S]], 1), DESIGN.md section 16
 
 Every value the backward needs stays on the device (the upstream gradient is read by the kernel), so a step built from these records
 into a graph (vitamd.graph.GraphedStep) like the rest of the path.
@@ -152,3 +154,67 @@ def token_embed(ids, tok_weight, pos_weight):
     """tok_weight[ids] + pos_weight[:S] for ids int64 [B, S] -> fp32 [B, S, D] (the bits of the torch gather-and-add), with the gradients
     of both tables from one pass over the incoming gradient."""
     return TokenEmbedFn.apply(ids, tok_weight, pos_weight)
+
+
+# ------------------------------------------------------------------------------------------------ sequence assembly (DESIGN.md section 16)
+def _table(t, name):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ops._lib.VitamdError(f"{name}: expected a 2-d fp32 table [rows, D]")
+    return t.detach()
+
+
+class PrefixedTokenEmbedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ids, tok_weight, pos_weight, prefix_weight):
+        if not isinstance(ids, torch.Tensor) or ids.dim() != 2:
+            raise ops._lib.VitamdError("prefixed_token_embed: ids must be int64 [B, S]")
+        tok, pos, prefix = _table(tok_weight, "tok_weight"), _table(pos_weight, "pos_weight"), _table(prefix_weight, "prefix_weight")
+        ids = ids.contiguous()
+        x = ops.assemble_tokens_fwd(prefix if prefix.shape[0] else None, pos, ids=ids, tok_table=tok)
+        ctx.save_for_backward(ids)
+        ctx.meta = (tuple(tok.shape), tuple(pos.shape), tuple(prefix.shape))
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        (ids,) = ctx.saved_tensors
+        tok_shape, pos_shape, prefix_shape = ctx.meta
+        dtok = torch.zeros(tok_shape, dtype=F32, device=g.device)
+        dpos = torch.zeros(pos_shape, dtype=F32, device=g.device)          # the full table: rows >= S stay zero
+        dprefix = torch.zeros(prefix_shape, dtype=F32, device=g.device)
+        ops.assemble_tokens_bwd(_f32c(g), dprefix if prefix_shape[0] else None, dpos, ids=ids, dtok=dtok)
+        return None, dtok, dpos, dprefix
+
+
+def prefixed_token_embed(ids, tok_weight, pos_weight, prefix_weight):
+    """cat([prefix_weight expanded over the batch, tok_weight[ids] + pos_weight[:S]], dim=1) for ids int64 [B, S] and prefix_weight fp32
+    [E, D] -> fp32 [B, E+S, D] (the bits of the torch embedding / add / expand / cat) in one kernel, with the gradients of the three
+    tables from one pass over the incoming gradient: those of the prefix and the positions summed over the batch in a fixed order."""
+    return PrefixedTokenEmbedFn.apply(ids, tok_weight, pos_weight, prefix_weight)
+
+
+class PrefixedRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, body, pos_weight, prefix_weight):
+        if not isinstance(body, torch.Tensor) or body.dim() != 3 or body.dtype not in (F32, BF16):
+            raise ops._lib.VitamdError("prefixed_rows: body must be fp32 or bf16 [B, S, D]")
+        pos, prefix = _table(pos_weight, "pos_weight"), _table(prefix_weight, "prefix_weight")
+        x = ops.assemble_tokens_fwd(prefix if prefix.shape[0] else None, pos, body=_f32c(body))
+        ctx.meta = (body.dtype, tuple(pos.shape), tuple(prefix.shape))
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        dtype, pos_shape, prefix_shape = ctx.meta
+        g = _f32c(g)
+        dpos = torch.zeros(pos_shape, dtype=F32, device=g.device)
+        dprefix = torch.zeros(prefix_shape, dtype=F32, device=g.device)
+        ops.assemble_tokens_bwd(g, dprefix if prefix_shape[0] else None, dpos)
+        dbody = g[:, prefix_shape[0]:]                                     # a view: the body's gradient needs no kernel work
+        return (dbody if dtype == F32 else dbody.to(dtype)), dpos, dprefix
+
+
+def prefixed_rows(body, pos_weight, prefix_weight):
+    """cat([prefix_weight expanded over the batch, body + pos_weight[:S]], dim=1) for body fp32 or bf16 [B, S, D] -> fp32 [B, E+S, D] in
+    one kernel; the body's gradient (in its dtype) is the tail of the incoming one, those of the two tables come from one pass over it."""
+    return PrefixedRowsFn.apply(body, pos_weight, prefix_weight)

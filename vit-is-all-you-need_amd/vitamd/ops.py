@@ -811,6 +811,85 @@ def embed_tokens_bwd(g, ids, dtok, dpos):
     return dtok, dpos
 
 
+def assemble_tokens_grid_cap():
+    """workgroups per launch of the two assembly kernels (asked of the library); more work makes workgroups loop"""
+    return int(_L().vitamd_assemble_tokens_grid_cap())
+
+
+def _need_assemble(what, x_shape, prefix, pos, ids, tok, named):
+    """The checks of _need_embed for the assembly ops, dtypes and shapes first (before any device is looked at), then device and
+    contiguity of every tensor in `named`.  x_shape: (B, E+S, D) when the [B, E+S, D] tensor is given (the backward's g), else None;
+    prefix [E, D] or None (E = 0), pos [pos_rows, D], ids int64 [B, S] with tok [tok_rows, D] in gather mode -> (B, E, S, D)"""
+    for name, (t, dtype, ndim) in named.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != ndim:
+            raise _lib.VitamdError(f"{what}: {name}: expected a {ndim}-d {dtype} tensor, got "
+                                   f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    D = pos.shape[1]
+    E = 0 if prefix is None else prefix.shape[0]
+    widths = {name: t.shape[-1] for name, (t, dtype, _) in named.items() if dtype == F32}
+    if any(w != D for w in widths.values()) or D % 4 != 0 or D < 4:
+        raise _lib.VitamdError(f"{what}: prefix, positions, source and output must share D with D % 4 == 0, got {widths}")
+    if ids is not None:
+        B, S = ids.shape
+        if x_shape is not None and tuple(x_shape[:2]) != (B, E + S):
+            raise _lib.VitamdError(f"{what}: ids {tuple(ids.shape)} behind a prefix of {E} do not fit {tuple(x_shape)}")
+    else:
+        B, S = x_shape[0], x_shape[1] - E
+    if B < 1 or not 1 <= S <= pos.shape[0] or (tok is not None and tok.shape[0] < 1):
+        raise _lib.VitamdError(f"{what}: needs B >= 1, 1 <= S <= {pos.shape[0]} positions (pos_rows >= S) and a table with rows, "
+                               f"got B={B}, S={S}, E={E}")
+    for name, (t, dtype, ndim) in named.items():
+        _need(t, dtype, name, ndim)
+    return B, E, S, D
+
+
+def assemble_tokens_fwd(prefix, pos_table, *, ids=None, tok_table=None, body=None, out=None):
+    """x fp32 [B, E+S, D]: x[:, :E] = prefix, x[:, E:] = tok_table[ids] + pos_table[:S] (gather mode) or body + pos_table[:S] (dense mode;
+    body fp32 [B, S, D]) - one fp32 add, the bits of the torch embedding / add / expand / cat.  prefix fp32 [E, D] or None.  An id outside
+    the table leaves that row of `out` as it was (the kernel never reads outside a table)."""
+    if (ids is None) != (tok_table is None) or (ids is None) == (body is None):
+        raise _lib.VitamdError("assemble_tokens_fwd: give either ids with a token table or a dense body")
+    named = {"pos_table": (pos_table, F32, 2)}
+    if prefix is not None:
+        named["prefix"] = (prefix, F32, 2)
+    if ids is not None:
+        named.update(ids=(ids, torch.int64, 2), tok_table=(tok_table, F32, 2))
+    else:
+        named["body"] = (body, F32, 3)
+    if out is not None:
+        named["out"] = (out, F32, 3)
+    E = prefix.shape[0] if isinstance(prefix, torch.Tensor) and prefix.dim() == 2 else 0
+    src_shape = (body.shape[0], body.shape[1] + E) if isinstance(body, torch.Tensor) and body.dim() == 3 else None
+    B, E, S, D = _need_assemble("assemble_tokens_fwd", src_shape, prefix, pos_table, ids, tok_table, named)
+    if out is None:
+        out = torch.empty((B, E + S, D), dtype=F32, device=pos_table.device)
+    if tuple(out.shape) != (B, E + S, D):
+        raise _lib.VitamdError(f"assemble_tokens_fwd: out must be [{B}, {E + S}, {D}], got {tuple(out.shape)}")
+    _lib.check(_L().vitamd_assemble_tokens_fwd(_p(prefix) if E else None, _p(pos_table), _p(tok_table), _p(ids), _p(body), _p(out), B, E, S, D,
+                                               0 if tok_table is None else tok_table.shape[0], pos_table.shape[0], _stream()),
+               f"assemble_tokens_fwd[B={B},E={E},S={S},D={D}]")
+    return out
+
+
+def assemble_tokens_bwd(g, dprefix, dpos, *, ids=None, dtok=None):
+    """g fp32 [B, E+S, D]: dprefix fp32 [E, D] (or None, E = 0) += the sum over the batch of g[:, :E], dpos fp32 [pos_rows, D]: rows < S +=
+    that of g[:, E:], both in ascending order (reproducible); with ids int64 [B, S] and dtok fp32 [tok_rows, D] (gather mode) dtok += the
+    rows of g[:, E:] at their ids (fp32 atomics).  All are accumulated into.  Dense mode: the body's gradient is the view g[:, E:]."""
+    if (ids is None) != (dtok is None):
+        raise _lib.VitamdError("assemble_tokens_bwd: ids and dtok go together (gather mode) or are both absent (dense mode)")
+    named = {"g": (g, F32, 3), "dpos": (dpos, F32, 2)}
+    if dprefix is not None:
+        named["dprefix"] = (dprefix, F32, 2)
+    if ids is not None:
+        named.update(ids=(ids, torch.int64, 2), dtok=(dtok, F32, 2))
+    g_shape = tuple(g.shape) if isinstance(g, torch.Tensor) and g.dim() == 3 else None
+    B, E, S, D = _need_assemble("assemble_tokens_bwd", g_shape, dprefix, dpos, ids, dtok, named)
+    _lib.check(_L().vitamd_assemble_tokens_bwd(_p(g), _p(ids), _p(dprefix) if E else None, _p(dpos), _p(dtok), B, E, S, D,
+                                               0 if dtok is None else dtok.shape[0], dpos.shape[0], _stream()),
+               f"assemble_tokens_bwd[B={B},E={E},S={S},D={D}]")
+    return dprefix, dpos, dtok
+
+
 # ------------------------------------------------------------------------------------------ training the image tokenizers
 VQ_MAX_D = 64             # include/vitamd.h vitamd_vq_quantize_fwd: wider codes stay on vq_nearest and the torch expressions
 
