@@ -319,6 +319,40 @@ int vitamd_assemble_tokens_bwd(const float* g, const long long* ids, float* dpre
  * B * (E+S) * D / 4 / 256 workgroups, the backward (E+S) * ceil(D / 256) / 4. */
 int vitamd_assemble_tokens_grid_cap(void);
 
+/* ---- device input pipeline: uint8 frames -> patch rows and images ------
+ * src uint8 [Nsrc, Hs, Ws, C], channels last and contiguous (byte alignment is enough).  For output sample b < B:
+ *   image[b, c, y, x] = table[c][ src[index[b], y0 + y, x0 + (flip ? W-1-x : x), c] ]          fp32 [B, C, H, W]
+ *   patches_bf16[(b*gh + ph)*gw + pw, (c*p + kh)*p + kw] = bf16 (round to nearest even) of image[b, c, ph*p + kh, pw*p + kw]
+ * the latter bit for bit the rows vitamd_im2col_bf16 makes of `image`.  index int64 [B] on the device names each sample's source
+ * frame (NULL: sample b reads frame b, which needs Nsrc >= B): the frame gather of ImagesFromVideoDataset (datasets.py) and the window
+ * videos[:, offset:offset+T] in one.  geom int32 [B, 3] on the device holds (y0, x0, flip) per sample (NULL: (0, 0, 0)): RandomCrop /
+ * CenterCrop and RandomHorizontalFlip.  table fp32 [C, 256] on the device: ToTensor + Normalize per byte value.  Either output may be
+ * NULL, not both; image must be 16-byte and patches_bf16 8-byte aligned for the fast form (C == 3, W % 4 == 0, p % 4 == 0), anything
+ * else takes the generic one.
+ * CLAMPS: the kernel clamps index[b] into [0, Nsrc), y0 into [0, Hs-H] and x0 into [0, Ws-W] before they form an address, and any
+ * non-zero flip counts as 1: no device-side value can make it read outside src.
+ * VITAMD_ERR_SHAPE (answered first): B, Nsrc, Hs, Ws, H, W < 1; C outside 1..4; H > Hs or W > Ws; NULL index with Nsrc < B; with
+ * patches_bf16 given p < 1, H % p != 0 or W % p != 0; Nsrc*Hs*Ws*C or B*C*H*W beyond 2^40 elements.  VITAMD_ERR_ARG: NULL src, NULL
+ * table, both outputs NULL.  Nothing is launched in either case.  The grid is capped at vitamd_frames_prep_grid_cap() workgroups of
+ * 256 lanes with a stride loop beyond (a lane owns 4 pixels x 3 channels in the fast form, one element in the generic one).
+ * Only enqueues on `stream`; no backward (a uint8 input takes no gradient).
+ * replaces the CPU-side transforms of the reference's loaders (datasets.py: ToTensor, Normalize, crop, flip; Resize stays on the
+ * CPU workers) and vitamd_im2col_bf16's read of the fp32 image. */
+int vitamd_frames_prep(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16,
+                       float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, void* stream);
+int vitamd_frames_prep_grid_cap(void);
+/* Fills geom int32 [B, 3] on the device for vitamd_frames_prep.  Sample b takes the words w0, w1, w2 of Philox4x32-10 with key
+ * (seed low, seed high) and counter (b, 1, step low, step high) - c1 = 1 keeps it off vitamd_sample_logits' stream, which uses c1 = 0:
+ *   y0 = (w0 * (Hs-H+1)) >> 32     x0 = (w1 * (Ws-W+1)) >> 32     flip = flip_enabled ? w2 >> 31 : 0       (64-bit products)
+ * seed and step are passed by value: no host synchronisation, and the same (seed, step) gives the same crops on any device.
+ * B, Hs, Ws, H, W < 1, H > Hs or W > Ws: VITAMD_ERR_SHAPE; NULL geom: VITAMD_ERR_ARG. */
+int vitamd_crop_flip_draw(int* geom, int B, int Hs, int Ws, int H, int W, int flip_enabled, unsigned long long seed,
+                          unsigned long long step, void* stream);
+/* The way back, for frames that leave the tokenizers: img fp32 [B, C, H, W] -> out uint8 [B, H, W, C] = rint(clamp(v, 0, 1) * 255)
+ * (ties to even), NaN -> 0: bit-equal to (x.clamp(0, 1) * 255).round().to(uint8) for finite input.  C in 1..4, all sizes >= 1,
+ * at most 2^40 elements, else VITAMD_ERR_SHAPE; a NULL pointer: VITAMD_ERR_ARG.  Grid cap as vitamd_frames_prep. */
+int vitamd_frames_to_u8(const float* img, unsigned char* out, int B, int C, int H, int W, void* stream);
+
 /* ---- helpers around the GEMMs ---------------------------------------------------------------- */
 /* fp32 -> bf16 (autocast's per-step weight / activation cast, train_vit.py:100). */
 int vitamd_cast_f32_bf16(const float* in, void* out_bf16, long n, void* stream);

@@ -170,6 +170,19 @@ __device__ __forceinline__ float dropout_keep(unsigned long long idx, unsigned s
   return h >= thresh ? scale : 0.f;
 }
 
+// Philox4x32-10: the four output words of counter (c0..c3) under key (k0, k1).  The sampler (sample.hip, c1 = 0) and the crop / flip draw
+// (input.hip, c1 = 1) share it; a caller that uses fewer words lets the compiler drop the rest.
+__device__ __forceinline__ u32x4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return u32x4{c0, c1, c2, c3};
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -1,0 +1,246 @@
+// The device input pipeline: raw uint8 frames [Nsrc, Hs, Ws, C] (channels last, as decoders and video sets hand
+// them over) -> the patch-embed GEMM's bf16 operand AND the fp32 NCHW image the tokenizers' losses take as their target, in one pass that
+// reads every source byte once.  Frame gather (index), crop and horizontal flip (geom) are an index map; ToTensor + Normalize are a
+// 256-entry table per channel, so the arithmetic of the reference's CPU transform is reproduced bit for bit by a lookup.
+//
+// A pure HBM stream: per pixel and channel 1 byte in, 4 (fp32) + 2 (bf16) bytes out.
+// Fast form (C == 3, W % 4 == 0, p % 4 == 0 when patches are wanted): a lane owns 4 consecutive output pixels of one image row and all
+// three channels - 12 contiguous source bytes (in reverse pixel order under a flip), one 16-byte fp32 store and one 8-byte bf16 store
+// per channel.  Consecutive lanes walk an image row, as in im2col_kernel, when only the image is wanted, and (kw, 4 image rows, pw)
+// when patch rows are: see the loop.  Source addresses are byte-aligned only (x0, Ws * 3 and the
+// flip make every offset possible): the 12 bytes are taken from the four ALIGNED dwords that enclose them where src itself is 4-byte
+// aligned and that window lies inside src, and by twelve byte loads otherwise (the last lanes of the last frame, an odd base pointer).
+// Generic form: one lane per output element.
+// Every device-side value is clamped before it forms an address: index into [0, Nsrc), y0 into [0, Hs-H], x0 into [0, Ws-W].
+#include "common.h"
+#include "../../include/vitamd.h"
+
+namespace {
+
+constexpr int PREP_GRID_CAP = 2048;                  // workgroups per launch (8 per CU); further work is reached by the stride loop
+constexpr long long MAX_ELEMS = 1ll << 40;           // per tensor: keeps every product of the index arithmetic inside 64 bits
+
+// the element count of a tensor, or -1 beyond MAX_ELEMS (checked factor by factor: four ints can overflow 64 bits)
+inline long long count(int a, int b, int c, int d) {
+  long long n = a;
+  for (const int f : {b, c, d}) {
+    n *= f;
+    if (n > MAX_ELEMS) return -1;
+  }
+  return n;
+}
+
+struct Placement { const unsigned char* frame; int y0, x0, flip; };
+
+// where output sample b reads: its (clamped) source frame and crop origin
+__device__ __forceinline__ Placement place(const unsigned char* src, const long long* index, const int* geom, int b, int Nsrc, int Hs, int Ws,
+                                           int C, int H, int W) {
+  long long f = index ? index[b] : b;
+  f = f < 0 ? 0 : (f > Nsrc - 1 ? Nsrc - 1 : f);
+  Placement pl = {src + (size_t)f * Hs * Ws * C, 0, 0, 0};
+  if (geom) {
+    const int* g = geom + (size_t)b * 3;
+    pl.y0 = min(max(g[0], 0), Hs - H);
+    pl.x0 = min(max(g[1], 0), Ws - W);
+    pl.flip = g[2] != 0;
+  }
+  return pl;
+}
+
+template <bool DWORDS>
+__global__ __launch_bounds__(256) void frames_prep_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ index,
+                                                          const int* __restrict__ geom, const float* __restrict__ table,
+                                                          __bf16* __restrict__ patches, float* __restrict__ image, int B, int Nsrc, int Hs,
+                                                          int Ws, int H, int W, int p, size_t src_bytes) {
+  __shared__ float tab[3 * 256];
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) tab[i] = table[i];
+  __syncthreads();
+  const int w4 = W / 4;
+  const unsigned per_sample = (unsigned)H * w4;
+  const size_t total = (size_t)B * per_sample;
+  const int gh = patches ? H / p : 0, gw = patches ? W / p : 0, pd = 3 * p * p;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    // one 64-bit division per item (the sample), 32-bit arithmetic inside the sample: the host keeps H * W / 4 below 2^31
+    const int b = (int)(i / per_sample);
+    unsigned t = (unsigned)(i - (size_t)b * per_sample);
+    int x, y;
+    if (patches) {
+      // consecutive lanes walk (kw, 4 image rows, pw): the 4 rows of one patch are neighbours in its patch vector, so a bf16 store
+      // instruction writes pieces of 4 * p * 2 bytes (whole 128-byte lines at p = 16) where a row-major walk writes p * 2, and
+      // the fp32 stores still cover runs of whole patches of each row
+      const unsigned p4 = p / 4;
+      const int kw4 = (int)(t % p4); t /= p4;
+      const int r = (int)(t & 3); t >>= 2;
+      const int pw = (int)(t % (unsigned)gw); t /= (unsigned)gw;
+      x = pw * p + kw4 * 4;
+      y = (int)t * 4 + r;                                           // H % p == 0 and p % 4 == 0: rows come in fours
+    } else {
+      x = (int)(t % (unsigned)w4) * 4;
+      y = (int)(t / (unsigned)w4);
+    }
+    const Placement pl = place(src, index, geom, b, Nsrc, Hs, Ws, 3, H, W);
+    // the 4 source pixels are neighbours either way; under a flip output pixel j takes source pixel 3 - j
+    const int sx = pl.x0 + (pl.flip ? W - 4 - x : x);
+    const unsigned char* s = pl.frame + ((size_t)(pl.y0 + y) * Ws + sx) * 3;
+    const size_t off = (size_t)(s - src);
+    unsigned w[3];
+    if (DWORDS && (off & ~(size_t)3) + 16 <= src_bytes) {
+      const unsigned* q = (const unsigned*)(src + (off & ~(size_t)3));
+      const unsigned d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
+      const unsigned sh = (unsigned)(off & 3) * 8;
+      w[0] = (unsigned)((((uint64_t)d1 << 32) | d0) >> sh);
+      w[1] = (unsigned)((((uint64_t)d2 << 32) | d1) >> sh);
+      w[2] = (unsigned)((((uint64_t)d3 << 32) | d2) >> sh);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) w[k] = s[4 * k] | (s[4 * k + 1] << 8) | (s[4 * k + 2] << 16) | ((unsigned)s[4 * k + 3] << 24);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      f32x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = 3 * j + c;                                   // byte of source pixel j, channel c
+        const float val = tab[c * 256 + ((w[k >> 2] >> (8 * (k & 3))) & 0xffu)];
+        if (pl.flip) v[3 - j] = val; else v[j] = val;
+      }
+      if (image) *(f32x4*)(image + (((size_t)b * 3 + c) * H + y) * W + x) = v;
+      if (patches) {
+        const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
+        *(u32x2*)(patches + (((size_t)b * gh + ph) * gw + pw) * pd + (c * p + kh) * p + kw) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void frames_prep_generic_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ index,
+                                                                  const int* __restrict__ geom, const float* __restrict__ table,
+                                                                  __bf16* __restrict__ patches, float* __restrict__ image, int B, int Nsrc,
+                                                                  int Hs, int Ws, int C, int H, int W, int p) {
+  __shared__ float tab[4 * 256];
+  for (int i = threadIdx.x; i < C * 256; i += 256) tab[i] = table[i];
+  __syncthreads();
+  const size_t total = (size_t)B * C * H * W;
+  const int gh = patches ? H / p : 0, gw = patches ? W / p : 0, pd = C * p * p;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {      // i = the element of image
+    size_t t = i;
+    const int x = (int)(t % W); t /= W;
+    const int y = (int)(t % H); t /= H;
+    const int c = (int)(t % C);
+    const int b = (int)(t / C);
+    const Placement pl = place(src, index, geom, b, Nsrc, Hs, Ws, C, H, W);
+    const int sx = pl.x0 + (pl.flip ? W - 1 - x : x);
+    const float v = tab[c * 256 + pl.frame[((size_t)(pl.y0 + y) * Ws + sx) * C + c]];
+    if (image) image[i] = v;
+    if (patches) {
+      const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
+      patches[(((size_t)b * gh + ph) * gw + pw) * pd + (c * p + kh) * p + kw] = f2bf(v);
+    }
+  }
+}
+
+// one lane per sample: (y0, x0, flip) from three words of Philox4x32-10, key = seed, counter = (b, 1, step)
+__global__ __launch_bounds__(256) void crop_flip_draw_kernel(int* __restrict__ geom, int B, unsigned ny, unsigned nx, int flip, unsigned k0,
+                                                             unsigned k1, unsigned s0, unsigned s1) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const u32x4 r = philox4x32_10((unsigned)b, 1u, s0, s1, k0, k1);
+  geom[b * 3 + 0] = (int)(((uint64_t)r[0] * ny) >> 32);
+  geom[b * 3 + 1] = (int)(((uint64_t)r[1] * nx) >> 32);
+  geom[b * 3 + 2] = flip ? (int)(r[2] >> 31) : 0;
+}
+
+// rint(clamp(v, 0, 1) * 255), NaN -> 0 (fmaxf returns its other operand)
+__device__ __forceinline__ unsigned to_u8(float v) { return (unsigned)__builtin_rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f); }
+
+// fp32 [B, C, H, W] -> uint8 [B, H, W, C].  A lane owns 4 neighbouring pixels: one 16-byte load per channel plane, and its 4 * C output
+// bytes are C whole dwords at a 4-byte-aligned offset.
+template <int C>
+__global__ __launch_bounds__(256) void frames_to_u8_kernel(const float* __restrict__ img, unsigned* __restrict__ out, size_t groups, size_t hw4) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (size_t)gridDim.x * 256) {
+    const size_t b = i / hw4, g = i - b * hw4;
+    unsigned bytes[4 * C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const f32x4 v = *(const f32x4*)(img + ((b * C + c) * hw4 + g) * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bytes[j * C + c] = to_u8(v[j]);
+    }
+#pragma unroll
+    for (int d = 0; d < C; ++d)
+      out[i * C + d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | (bytes[4 * d + 3] << 24);
+  }
+}
+
+__global__ __launch_bounds__(256) void frames_to_u8_generic_kernel(const float* __restrict__ img, unsigned char* __restrict__ out, size_t total,
+                                                                   int C, size_t hw) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {       // i = the element of out
+    const int c = (int)(i % C);
+    const size_t px = i / C, b = px / hw, yx = px - b * hw;
+    out[i] = (unsigned char)to_u8(img[(b * C + c) * hw + yx]);
+  }
+}
+
+inline dim3 capped_grid(size_t items) {
+  const size_t wgs = (items + 255) / 256;
+  return dim3((unsigned)(wgs < (size_t)PREP_GRID_CAP ? wgs : (size_t)PREP_GRID_CAP));
+}
+
+}  // namespace
+
+extern "C" int vitamd_frames_prep_grid_cap(void) { return PREP_GRID_CAP; }
+
+extern "C" int vitamd_frames_prep(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16,
+                                  float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, void* stream) {
+  if (B < 1 || Nsrc < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || C < 1 || C > 4 || H > Hs || W > Ws) return VITAMD_ERR_SHAPE;
+  if (patches_bf16 && (p < 1 || H % p != 0 || W % p != 0)) return VITAMD_ERR_SHAPE;
+  if (!index && Nsrc < B) return VITAMD_ERR_SHAPE;
+  const long long n_src = count(Nsrc, Hs, Ws, C), n_out = count(B, C, H, W);
+  if (n_src < 0 || n_out < 0) return VITAMD_ERR_SHAPE;
+  if (!src || !table || (!patches_bf16 && !image)) return VITAMD_ERR_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool aligned = ((uintptr_t)image & 15) == 0 && ((uintptr_t)patches_bf16 & 7) == 0;      // of the 16- and 8-byte stores
+  if (C == 3 && W % 4 == 0 && (!patches_bf16 || p % 4 == 0) && aligned && (long long)H * W / 4 < 0x7fffffffll) {
+    const dim3 grid = capped_grid((size_t)n_out / 12);
+    if (((uintptr_t)src & 3) == 0)
+      hipLaunchKernelGGL(frames_prep_kernel<true>, grid, dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16, image, B, Nsrc, Hs, Ws,
+                         H, W, p, (size_t)n_src);
+    else
+      hipLaunchKernelGGL(frames_prep_kernel<false>, grid, dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16, image, B, Nsrc, Hs, Ws,
+                         H, W, p, (size_t)n_src);
+  } else {
+    hipLaunchKernelGGL(frames_prep_generic_kernel, capped_grid((size_t)n_out), dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16,
+                       image, B, Nsrc, Hs, Ws, C, H, W, p);
+  }
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+extern "C" int vitamd_crop_flip_draw(int* geom, int B, int Hs, int Ws, int H, int W, int flip, unsigned long long seed, unsigned long long step,
+                                     void* stream) {
+  if (B < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || H > Hs || W > Ws || B > 0x7fffffff / 3) return VITAMD_ERR_SHAPE;
+  if (!geom) return VITAMD_ERR_ARG;
+  hipLaunchKernelGGL(crop_flip_draw_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, geom, B, (unsigned)(Hs - H + 1),
+                     (unsigned)(Ws - W + 1), flip, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32));
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+extern "C" int vitamd_frames_to_u8(const float* img, unsigned char* out, int B, int C, int H, int W, void* stream) {
+  if (B < 1 || C < 1 || C > 4 || H < 1 || W < 1) return VITAMD_ERR_SHAPE;
+  const long long n = count(B, C, H, W);
+  if (n < 0) return VITAMD_ERR_SHAPE;
+  if (!img || !out) return VITAMD_ERR_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t hw = (size_t)H * W;
+  if (hw % 4 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 3) == 0) {
+    const size_t groups = (size_t)B * (hw / 4);
+    const dim3 grid = capped_grid(groups);
+    unsigned* o = (unsigned*)out;
+    if (C == 1) hipLaunchKernelGGL(frames_to_u8_kernel<1>, grid, dim3(256), 0, st, img, o, groups, hw / 4);
+    else if (C == 2) hipLaunchKernelGGL(frames_to_u8_kernel<2>, grid, dim3(256), 0, st, img, o, groups, hw / 4);
+    else if (C == 3) hipLaunchKernelGGL(frames_to_u8_kernel<3>, grid, dim3(256), 0, st, img, o, groups, hw / 4);
+    else hipLaunchKernelGGL(frames_to_u8_kernel<4>, grid, dim3(256), 0, st, img, o, groups, hw / 4);
+  } else {
+    hipLaunchKernelGGL(frames_to_u8_generic_kernel, capped_grid((size_t)n), dim3(256), 0, st, img, out, (size_t)n, C, hw);
+  }
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}

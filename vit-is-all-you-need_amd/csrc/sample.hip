@@ -66,16 +66,9 @@ __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
   return v;
 }
 
-// Philox4x32-10, first output word
+// Philox4x32-10 (common.h), first output word
 __device__ __forceinline__ unsigned philox_first(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const u64 p0 = (u64)0xD2511F53u * c0, p1 = (u64)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c0;
+  return philox4x32_10(c0, c1, c2, c3, k0, k1)[0];
 }
 
 struct SampleArgs {

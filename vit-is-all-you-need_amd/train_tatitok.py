@@ -20,6 +20,7 @@ import torch.nn as nn
 from blocks import TiTokDecoder, TiTokEncoder, VectorQuantizer
 from utils import get_lr_scheduler
 from vitamd import ops, tokenizer
+from vitamd.data import Frames
 
 
 @dataclass
@@ -90,6 +91,9 @@ class TiTok(nn.Module):
         tokenizer.vq_quantize(unit_codes=True) -> decoder.features -> tokenizer.linear_conv_recon_mse on the parameters of `ffn` and
         `conv_out`.  return_recon: the decoded image as a differentiable fourth result (a perceptual term's gradient joins the pixel
         loss's inside the backward kernel).  A quantiser the kernels do not cover (use_l2_norm=False) runs as in forward()."""
+        target = x
+        if isinstance(x, Frames):      # uint8 frames: the encoder's patch rows and the fp32 target come out of one launch
+            target = x.materialise(self.encoder.patch_size, image=True).images()
         z = self.encoder(pixel_values=x, latent_tokens=self.latent_tokens)                 # [B, C, 1, N]
         if self._fused_quantiser():
             q, ids, qloss = tokenizer.vq_quantize(z.float().permute(0, 2, 3, 1), self.quantize.embedding.weight, unit_codes=True)
@@ -99,7 +103,7 @@ class TiTok(nn.Module):
             ids, qloss = info["min_encoding_indices"], info["quantizer_loss"]
         dec = self.decoder
         out = tokenizer.linear_conv_recon_mse(dec.features(z_quantized), dec.ffn[0].weight, dec.ffn[0].bias, dec.conv_out.weight,
-                                              dec.conv_out.bias, x, dec.grid_size, dec.patch_size, return_recon=return_recon)
+                                              dec.conv_out.bias, target, dec.grid_size, dec.patch_size, return_recon=return_recon)
         if return_recon:
             return out[0], qloss, ids, out[1]
         return out, qloss, ids
@@ -137,16 +141,17 @@ def train_step(model, images, optim, lr_sched=None, perceptual=None, perceptual_
     per-image values (vitamd.perceptual.PerceptualLoss fits); with one the step calls model.loss(images, return_recon=True) and stays
     on the fused tail.  Gradient clipping is the optimiser's (make_optim).  -> the detached device loss"""
     optim.zero_grad(set_to_none=True)
+    target = images.images() if isinstance(images, Frames) and (perceptual is not None or not FUSED_ROUTE) else images
     if not FUSED_ROUTE:
         recon, info = model(images)
-        recon_loss, qloss = torch.nn.functional.mse_loss(recon, images), info["quantizer_loss"]
+        recon_loss, qloss = torch.nn.functional.mse_loss(recon, target), info["quantizer_loss"]
     elif perceptual is None:
         recon_loss, qloss, _ = model.loss(images)
         recon = None
     else:
         recon_loss, qloss, _, recon = model.loss(images, return_recon=True)
     if perceptual is not None:
-        recon_loss = recon_loss + perceptual_weight * perceptual(recon, images).mean()
+        recon_loss = recon_loss + perceptual_weight * perceptual(recon, target).mean()
     loss = recon_loss + qloss
     loss.backward()
     optim.step()

@@ -15,6 +15,7 @@ import torch.nn as nn
 from train_vit import ViT, ViTConfig
 from utils import get_lr_scheduler
 from vitamd import ops, tokenizer
+from vitamd.data import Frames
 from vitamd.functions import linear
 
 
@@ -139,9 +140,11 @@ class TiTok(nn.Module):
 
 
 def tokenizer_loss(enc, quant, dec, x):
-    """the loss route shared by TiTok and ViTVQGAN (their decoders both have features(), embd_proj and config)"""
+    """the loss route shared by TiTok and ViTVQGAN (their decoders both have features(), embd_proj and config).  x: fp32 images, or
+    uint8 vitamd.data.Frames - one launch then makes the encoder's patch rows and the fp32 target together"""
+    target = x.materialise(enc.vit.config.patch_size, image=True).images() if isinstance(x, Frames) else x
     tokens, ids, qloss = tokenizer.vq_quantize(enc(x), quant.codebook.weight)
-    recon = tokenizer.linear_recon_mse(dec.features(tokens), dec.embd_proj.weight, dec.embd_proj.bias, x, dec.config.patch_dim, dec.config.patch_size)
+    recon = tokenizer.linear_recon_mse(dec.features(tokens), dec.embd_proj.weight, dec.embd_proj.bias, target, dec.config.patch_dim, dec.config.patch_size)
     return recon, qloss, ids
 
 
@@ -156,8 +159,9 @@ def train_step(model, images, optim, lr_sched=None, perceptual=None, perceptual_
     if perceptual is None:
         recon_loss, qloss, _ = model.loss(images)
     else:
+        target = images.materialise(model.config.patch_size, image=True).images() if isinstance(images, Frames) else images
         recon, _, qloss = model(images)
-        recon_loss = torch.nn.functional.mse_loss(recon, images) + perceptual_weight * perceptual(recon, images).mean()
+        recon_loss = torch.nn.functional.mse_loss(recon, target) + perceptual_weight * perceptual(recon, target).mean()
     loss = recon_loss + qloss
     loss.backward()
     optim.step()
@@ -179,6 +183,8 @@ def add_common_args(p):
     p.add_argument("--train_steps", type=int, default=50)
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
+    p.add_argument("--u8", action="store_true",
+                   help="feed seeded random uint8 frames through vitamd.data.DeviceLoader (the device input pipeline) instead of one fp32 batch")
     p.add_argument("--perceptual_weight", type=float, default=0.0,
                    help="weight of the ConvNeXt-S perceptual term (reference train_titok.py:155-158); 0 = no perceptual term")
     p.add_argument("--perceptual_weights", type=str, default=None,
@@ -220,8 +226,15 @@ def run(model, args, codebook_size):
     g = torch.Generator(device="cpu").manual_seed(0)
     images = torch.rand((args.bs, 3, args.image_size, args.image_size), generator=g).to(dev)
     usage = torch.zeros([codebook_size], device=dev)
+    feed = None
+    if getattr(args, "u8", False):
+        from vitamd.data import DeviceLoader
+        u8 = torch.randint(0, 256, (args.bs, args.image_size, args.image_size, 3), generator=g, dtype=torch.uint8)
+        feed = DeviceLoader(((u8, None) for _ in range(args.train_steps)), dev, args.image_size, patch=args.patch_size, train=False)
     for step in range(args.train_steps):
         t0 = time.time()
+        if feed is not None:
+            images, _ = next(feed)
         loss = train_step(model, images, optim, sched, perceptual=perceptual, perceptual_weight=args.perceptual_weight)
         with torch.no_grad():
             usage[model.encode(images)] = 1

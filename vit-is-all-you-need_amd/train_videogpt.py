@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from transformer import Transformer, transformer_configs
 from utils import get_lr_scheduler
-from vitamd import lm, ops
+from vitamd import data, lm, ops
 from vitamd.functions import WEIGHTS, linear
 
 
@@ -195,17 +195,30 @@ class VideoGPT(nn.Module):
 
 
 @torch.no_grad()
-def frames_to_tokens(tokenizer, videos):
+def frames_to_tokens(tokenizer, videos, index=None):
     """videos [B, T, 3, H, W] -> code ids int64 [B, T, N] (train_videogpt.py:122-127): every frame through tokenizer.encode, in eval mode
-    and without a graph; the tokenizer's training flag is put back"""
+    and without a graph; the tokenizer's training flag is put back.  videos may also be raw uint8 [B, T, H, W, C] on the device (what the
+    reference's video sets hold): they go through vitamd.data.Frames, scaled to [0, 1].  index (uint8 videos only): int64 [B, T'] of
+    frame numbers into the flattened [B*T] frames - the window videos[:, offset:offset+T'] without a copy -> ids [B, T', N]"""
     if videos.dim() != 5:
-        raise ValueError(f"frames_to_tokens: expected videos [B, T, C, H, W], got {tuple(videos.shape)}")
+        raise ValueError(f"frames_to_tokens: expected videos [B, T, C, H, W] or uint8 [B, T, H, W, C], got {tuple(videos.shape)}")
     B, T = videos.shape[:2]
+    if videos.dtype == torch.uint8:
+        if index is not None:
+            if index.dim() != 2 or index.shape[0] != B:
+                raise ValueError(f"frames_to_tokens: index must be int64 [{B}, T'], got {tuple(index.shape)}")
+            T = index.shape[1]
+            index = index.reshape(-1)
+        frames = data.Frames(videos, tuple(videos.shape[2:4]), index=index)
+    elif index is not None:
+        raise ValueError("frames_to_tokens: index goes with uint8 videos; slice a float tensor instead")
+    else:
+        frames = videos.reshape(B * T, *videos.shape[2:])
     was_training = getattr(tokenizer, "training", False)
     if was_training:
         tokenizer.eval()
     try:
-        _, info = tokenizer.encode(videos.reshape(B * T, *videos.shape[2:]))
+        _, info = tokenizer.encode(frames)
     finally:
         if was_training:
             tokenizer.train()
@@ -216,8 +229,9 @@ def frames_to_tokens(tokenizer, videos):
 
 
 @torch.no_grad()
-def tokens_to_frames(tokenizer, tokens, T):
-    """flattened code ids [B, T*N] (what generate_frames returns) -> frames [B, T, 3, H, W] clamped to [0, 1] (train_videogpt.py:148-156)"""
+def tokens_to_frames(tokenizer, tokens, T, as_u8=False):
+    """flattened code ids [B, T*N] (what generate_frames returns) -> frames [B, T, 3, H, W] clamped to [0, 1] (train_videogpt.py:148-156);
+    as_u8: uint8 [B, T, H, W, 3] instead, rint(clamp * 255) in one kernel (vitamd.data.to_u8): what goes to the host or a video file"""
     if tokens.dim() != 2 or T < 1 or tokens.shape[1] % T:
         raise ValueError(f"tokens_to_frames: expected tokens [B, T*N] with T = {T}, got {tuple(tokens.shape)}")
     B = tokens.shape[0]
@@ -229,6 +243,9 @@ def tokens_to_frames(tokenizer, tokens, T):
     finally:
         if was_training:
             tokenizer.train()
+    if as_u8:
+        out = data.to_u8(frames)
+        return out.reshape(B, T, *out.shape[1:])
     return torch.clamp(frames, 0.0, 1.0).reshape(B, T, *frames.shape[1:])
 
 

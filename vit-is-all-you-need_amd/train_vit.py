@@ -87,6 +87,8 @@ def parse_args(argv=None):
     p.add_argument("--weight_decay", type=float, default=1e-2)
     p.add_argument("--warmup_steps", type=int, default=10)
     p.add_argument("--train_steps", type=int, default=50)
+    p.add_argument("--u8", action="store_true",
+                   help="feed seeded random uint8 frames through vitamd.data.DeviceLoader (the device input pipeline: random crop and flip, ImageNet normalisation) instead of one fp32 batch")
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
     return p.parse_args(argv)
@@ -109,8 +111,18 @@ def main():
     g = torch.Generator(device="cpu").manual_seed(0)
     images = torch.randn(args.bs, 3, args.image_size, args.image_size, generator=g).to(dev)
     labels = torch.randint(0, args.num_classes, (args.bs,), generator=g).to(dev)
+    feed = None
+    if args.u8:
+        from vitamd.data import IMAGENET_MEAN, IMAGENET_STD, DeviceLoader
+        side = args.image_size + args.image_size // 7           # 256 for 224: the frame the random crop is taken from
+        u8 = torch.randint(0, 256, (args.bs, side, side, 3), generator=g, dtype=torch.uint8)
+        host_labels = labels.cpu()
+        host = ((u8, host_labels) for _ in range(args.train_steps))
+        feed = DeviceLoader(host, dev, args.image_size, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)
     for step in range(args.train_steps):
         t0 = time.time()
+        if feed is not None:
+            images, labels = next(feed)
         loss = train_step(model, images, labels, optim, sched)
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} {args.bs / (time.time() - t0):.0f} img/s")

@@ -10,6 +10,7 @@ import weakref
 import torch
 
 from . import ops
+from .data import Frames
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -657,7 +658,8 @@ class PatchEmbedFn(torch.autograd.Function):
         extra = extra_w.shape[0]
         seq = n_patches + extra
         need_grad = any(ctx.needs_input_grad)
-        patches = ops.im2col(_f32c(images), patch)  # [B*np, C*p*p] bf16
+        # [B*np, C*p*p] bf16; uint8 frames (vitamd.data.Frames) come with these rows made by the input kernel - the same bits, no fp32 image read
+        patches = images.patches(patch) if isinstance(images, Frames) else ops.im2col(_f32c(images), patch)
         if patches.shape[0] != B * n_patches:
             raise ops._lib.VitamdError(f"patch grid gives {patches.shape[0] // B} patches, config says {n_patches}")
         wb, _ = WEIGHTS.get(conv_w, ctx.needs_input_grad[0])

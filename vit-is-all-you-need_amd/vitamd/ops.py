@@ -1201,3 +1201,87 @@ def resize_norm_bwd(g_rows, table_h_t, table_w_t, std, B, H, W, size):
     _lib.check(_L().vitamd_resize_norm_bwd(_p(g_rows), g_rows.shape[1], _p(table_h_t[0]), _p(table_h_t[1]), Th, _p(table_w_t[0]), _p(table_w_t[1]),
                                            Tw, _p(std), _p(dimg), B, 3, H, W, size, _stream()), f"resize_norm_bwd[B={B},H={H},W={W},S={size}]")
     return dimg
+
+
+# ------------------------------------------------------------------------------------------ device input pipeline
+def frames_prep_grid_cap():
+    """workgroups one launch of the frame kernels has at most (asked of the library); more work makes them loop"""
+    return int(_L().vitamd_frames_prep_grid_cap())
+
+
+def check_frames(src_shape, out_hw, patch=None, B=None, has_index=False):
+    """The shape rules of vitamd_frames_prep as ValueError, without looking at a device: src [Nsrc, Hs, Ws, C] -> B samples of out_hw.
+    -> (B, Nsrc, Hs, Ws, C, H, W)"""
+    if len(src_shape) != 4:
+        raise ValueError(f"frames: expected uint8 [N, Hs, Ws, C] (channels last), got shape {tuple(src_shape)}")
+    Nsrc, Hs, Ws, C = (int(v) for v in src_shape)
+    H, W = (int(v) for v in out_hw)
+    B = Nsrc if B is None else int(B)
+    if min(B, Nsrc, Hs, Ws, H, W) < 1 or not 1 <= C <= 4:
+        raise ValueError(f"frames: every size must be >= 1 and C in 1..4, got src {tuple(src_shape)}, out {(H, W)}, B {B}")
+    if H > Hs or W > Ws:
+        raise ValueError(f"frames: the output {(H, W)} does not fit the source {(Hs, Ws)} (resizing stays with the host loader)")
+    if not has_index and Nsrc < B:
+        raise ValueError(f"frames: {B} samples need {B} source frames or an index, got {Nsrc}")
+    if patch is not None and (not isinstance(patch, int) or patch < 1 or H % patch or W % patch):
+        raise ValueError(f"frames: patch {patch!r} does not tile the output {(H, W)}")
+    return B, Nsrc, Hs, Ws, C, H, W
+
+
+def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=None):
+    """uint8 frames [Nsrc, Hs, Ws, C] -> (patch rows bf16 [B*gh*gw, C*p*p] or None, image fp32 [B, C, H, W] or None) in one launch
+    (semantics, clamps and refusals: include/vitamd.h vitamd_frames_prep).  index int64 [B] or None, geom int32 [B, 3] or None,
+    table fp32 [C, 256], all on the device of src."""
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
+        raise ValueError(f"frames_prep: src must be a uint8 tensor, got {getattr(src, 'dtype', type(src).__name__)}")
+    if patch is None and not image:
+        raise ValueError("frames_prep: nothing to write (give a patch size, image=True, or both)")
+    if index is not None and (not isinstance(index, torch.Tensor) or index.dim() != 1 or index.numel() < 1):
+        raise ValueError("frames_prep: index must be a 1-d int64 tensor with one entry per output sample")
+    B, Nsrc, Hs, Ws, C, H, W = check_frames(src.shape, out_hw, patch, None if index is None else index.numel(), index is not None)
+    _need(src, torch.uint8, "src", 4); _need(table, F32, "table", 2)
+    if tuple(table.shape) != (C, 256):
+        raise _lib.VitamdError(f"table: expected [{C}, 256], got {tuple(table.shape)}")
+    if index is not None:
+        _need(index, torch.int64, "index", 1)
+    if geom is not None:
+        _need(geom, torch.int32, "geom", 2)
+        if tuple(geom.shape) != (B, 3):
+            raise _lib.VitamdError(f"geom: expected [{B}, 3], got {tuple(geom.shape)}")
+    patches = torch.empty((B * (H // patch) * (W // patch), C * patch * patch), dtype=BF16, device=src.device) if patch is not None else None
+    img = torch.empty((B, C, H, W), dtype=F32, device=src.device) if image else None
+    _lib.check(_L().vitamd_frames_prep(_p(src), _p(index), _p(geom), _p(table), _p(patches), _p(img), B, Nsrc, Hs, Ws, C, H, W,
+                                       patch if patch is not None else 0, _stream()),
+               f"frames_prep[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
+    return patches, img
+
+
+def crop_flip_draw(B, src_hw, out_hw, seed, step, flip=True, device=None, out=None):
+    """geom int32 [B, 3] = (y0, x0, flip) per sample from Philox4x32-10 keyed by `seed`, counter (b, 1, step) - include/vitamd.h
+    vitamd_crop_flip_draw.  seed and step are Python integers in [0, 2^64): nothing is read back from the device."""
+    (Hs, Ws), (H, W) = (int(v) for v in src_hw), (int(v) for v in out_hw)
+    if min(B, Hs, Ws, H, W) < 1 or H > Hs or W > Ws:
+        raise ValueError(f"crop_flip_draw: needs B >= 1 and 1 <= out {(H, W)} <= src {(Hs, Ws)}, got B {B}")
+    for name, v in (("seed", seed), ("step", step)):
+        if not isinstance(v, int) or not 0 <= v < 1 << 64:
+            raise ValueError(f"crop_flip_draw: {name} must be an integer in [0, 2^64), got {v!r}")
+    if out is None:
+        out = torch.empty((B, 3), dtype=torch.int32, device=torch.device("cuda") if device is None else device)
+    _need(out, torch.int32, "geom", 2)
+    if tuple(out.shape) != (B, 3):
+        raise _lib.VitamdError(f"geom: expected [{B}, 3], got {tuple(out.shape)}")
+    with torch.cuda.device(out.device):
+        _lib.check(_L().vitamd_crop_flip_draw(_p(out), B, Hs, Ws, H, W, int(bool(flip)), seed, step, _stream()),
+                   f"crop_flip_draw[B={B},src={Hs}x{Ws},out={H}x{W}]")
+    return out
+
+
+def frames_to_u8(img):
+    """fp32 [B, C, H, W] -> uint8 [B, H, W, C] = rint(clamp(v, 0, 1) * 255), NaN -> 0 (include/vitamd.h vitamd_frames_to_u8)"""
+    if not isinstance(img, torch.Tensor) or img.dim() != 4 or min(img.shape) < 1 or img.shape[1] > 4:
+        raise ValueError(f"frames_to_u8: needs fp32 [B, C <= 4, H, W], got shape {tuple(getattr(img, 'shape', ()))}")
+    _need(img, F32, "img", 4)
+    B, C, H, W = img.shape
+    out = torch.empty((B, H, W, C), dtype=torch.uint8, device=img.device)
+    _lib.check(_L().vitamd_frames_to_u8(_p(img), _p(out), B, C, H, W, _stream()), f"frames_to_u8[B={B},C={C},H={H},W={W}]")
+    return out
