@@ -70,6 +70,13 @@ int vitamd_init(int device, void* stream);
  * K >= 128; VITAMD_ERR_SHAPE where it does not apply).  All forms give bit-identical results.  With VITAMD_EPI_DMUL, colsum may be NULL:
  * the seam and loader forms then run without the column sums in their epilogue (the bias gradient can come from
  * vitamd_gemm_tn_bf16_ws_colsum instead); `out` is bit-identical either way.
+ * Sizes: A, out, out2 and aux may be of any size.  The kernels on 256-column tiles address their operands with 32-bit byte offsets, so a
+ * call whose A (M x K x 2 bytes) or out (M x ldo x 2, or x 4 for the fp32 outputs) reaches 2^31 bytes is run as several launches over ROW
+ * PANELS of M, each below 2^31 bytes in both, with re-based pointers (and dropout indices that stay global); panel heights are multiples
+ * of 1280 rows, so every panel but the last is cut into the tiles of one big launch: same results, bit for bit, and colsum is added to by
+ * every panel.  What a row split cannot shrink is VITAMD_ERR_SHAPE with nothing written: B (N x K x 2 bytes) of 2^31 bytes or more, a row
+ * so wide that 1280 of them do not fit, and VITAMD_EPI_PATCH_F32 with M x K x 2 or M x ldo x 4 of 2^31 bytes or more (its output row
+ * depends on the global row index).  No case was given up to refusal beyond these.
  * Forward of nn.Linear (x W^T + b): A = x, B = W.  Input gradient (dy W): A = dy, B = W^T. */
 int vitamd_gemm_nt_bf16(const void* A, const void* B, void* out, void* out2, const float* bias, const void* aux,
                         float* colsum, int M, int N, int K, int ldo, int epi, int n_patches, int seq, int extra,
@@ -77,7 +84,8 @@ int vitamd_gemm_nt_bf16(const void* A, const void* B, void* out, void* out2, con
 
 /* Which kernel the call above would launch for these arguments on the current device (nothing is launched, no pointer is needed):
  * VITAMD_NT_FORM_* | tile rows << 8, | VITAMD_NT_FORM_TAIL_SPLIT when the launch is cut into a head of whole rounds in that form and a
- * tail on 128x128 tiles; a negative value is -VITAMD_ERR_*. */
+ * tail on 128x128 tiles; a negative value is -VITAMD_ERR_*.  For a call that is cut into row panels (above) the answer is that of its
+ * full-height panels; the last, shorter panel may take another form. */
 #define VITAMD_NT_FORM_SMALL 1          /* 128x128 tiles, 4 waves */
 #define VITAMD_NT_FORM_PP 2             /* ping-pong kernel, one workgroup per tile */
 #define VITAMD_NT_FORM_PP_PERSISTENT 3  /* ping-pong kernel, one workgroup per CU walking a tile list */
@@ -87,14 +95,19 @@ int vitamd_gemm_nt_bf16(const void* A, const void* B, void* out, void* out2, con
 int vitamd_gemm_nt_plan(int M, int N, int K, int ldo, int epi, int tile);
 
 /* fc2 with dropout: out f32 = resid + dropout_p(bf16(A.B^T + bias)), mask = hash(seed, row*N+col).
- * replaces transformer.py:39-40,44 (Linear + nn.Dropout(p) + residual add) in training mode.  `tile` as for vitamd_gemm_nt_bf16. */
+ * replaces transformer.py:39-40,44 (Linear + nn.Dropout(p) + residual add) in training mode.  `tile` as for vitamd_gemm_nt_bf16 (0, 128,
+ * 256, 320, 512, 1024), and so are the size rules: out and resid (M x N x 4 bytes) of 2^31 bytes or more are served in row panels whose
+ * mask indices stay row*N+col of the whole call; B of 2^31 bytes or more is VITAMD_ERR_SHAPE. */
 int vitamd_linear_dropout_resid_bf16(const void* A, const void* B, float* out, const float* bias, const float* resid,
                                      int M, int N, int K, float dropout_p, unsigned long long seed, int tile, void* stream);
 
 /* Weight gradient: out[P,Q] (fp32) += sum_r L[r,p] * Rm[r,q]   (dW = dY^T X).  Accumulates with
  * fp32 atomics, so `out` must hold the running gradient (zeros for a fresh one).
  * replaces the autograd backward of transformer.py:21,37,39 and train_vit.py:34.
- * Requirements: ldl % 8 == 0, ldr % 8 == 0.  `splits` 0 = auto. */
+ * Requirements: ldl % 8 == 0, ldr % 8 == 0.  `splits` 0 = auto.
+ * Sizes (all three vitamd_gemm_tn_bf16* entry points): L and Rm are addressed with 32-bit byte offsets from their first element, the
+ * zero-filled stage past the last row included: (R + 64) x ldl x 2 and (R + 64) x ldr x 2 must both be below 2^31, VITAMD_ERR_SHAPE with
+ * nothing written otherwise (cut R and accumulate).  `out`, `ws` and colsum are addressed with 64-bit pointers. */
 int vitamd_gemm_tn_bf16(const void* L, const void* Rm, float* out, int R, int P, int Q, int ldl, int ldr, int ldo,
                         int splits, void* stream);
 

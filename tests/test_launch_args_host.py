@@ -132,3 +132,85 @@ def test_tn_colsum_needs_the_workspace(L):
             assert _tn(L, P, form=form, accumulate=accumulate, ws=None, ws_bytes=need) == ARG
             assert _tn(L, P, form=form, accumulate=accumulate, ws_bytes=need - 1) == ARG           # room for the tiles but not for the column sums
             assert _tn(L, P, form=form, accumulate=accumulate, ws=None, ws_bytes=need, ldl=260) == ARG   # asked before the shape
+
+
+# ---- operand sizes (include/vitamd.h, "Sizes"): every refusal below is answered before a launch
+G31 = 2**31
+EPI_BIAS, EPI_PATCH = 0, 4
+NT_TILE_CODES = (0, 128, 256, 320, 512, 1024, 2048, 4096)
+
+
+def _nt(L, M, N, K, ldo, epi, tile, n_patches=0, seq=0, extra=0):
+    return L.vitamd_gemm_nt_bf16(P, P, P, P, None, P, None, M, N, K, ldo, epi, n_patches, seq, extra, tile, None)
+
+
+def test_nt_refuses_a_weight_of_2g_bytes():
+    from vitamd import lib
+    L = lib.load()
+    K = 1024
+    n_at, n_under = G31 // (K * 2), G31 // (K * 2) - 8                # N x K x 2 = 2^31 exactly / 16 KiB less (N % 8 == 0: every form applies)
+    assert n_at * K * 2 == G31 and n_at % 4 == 0
+    for tile in NT_TILE_CODES:
+        assert L.vitamd_gemm_nt_plan(1, n_at, K, n_at, EPI_BIAS, tile) == -SHAPE, tile
+        assert _nt(L, 1, n_at, K, n_at, EPI_BIAS, tile) == SHAPE, tile
+        assert L.vitamd_gemm_nt_plan(300, n_at + 4, K, n_at + 4, EPI_BIAS, tile) == -SHAPE, tile
+    # just under: accepted (the plan answers a form; 320-row tiles, the seam and the loader form apply to this shape too)
+    for tile in NT_TILE_CODES:
+        assert L.vitamd_gemm_nt_plan(300, n_under, K, n_under, EPI_BIAS, tile) > 0, tile
+    # the argument checks still answer first
+    assert L.vitamd_gemm_nt_bf16(None, P, P, P, None, P, None, 1, n_at, K, n_at, EPI_BIAS, 0, 0, 0, 0, None) == ARG
+    assert _nt(L, 1, n_at, K + 16, n_at, EPI_BIAS, 0) == SHAPE
+
+
+def test_nt_patch_epilogue_is_refused_past_the_limit_and_other_epilogues_are_split():
+    from vitamd import lib
+    L = lib.load()
+    K, N = 1024, 64
+    m_at = G31 // (K * 2)                                              # M x K x 2 = 2^31
+    for tile in (0, 128, 256, 512, 1024):
+        assert L.vitamd_gemm_nt_plan(m_at, N, K, N, EPI_PATCH, tile) == -SHAPE, tile
+        assert _nt(L, m_at, N, K, N, EPI_PATCH, tile, n_patches=196, seq=197, extra=1) == SHAPE, tile
+        assert L.vitamd_gemm_nt_plan(m_at - 1, N, K, N, EPI_PATCH, tile) > 0, tile
+        assert L.vitamd_gemm_nt_plan(m_at, N, K, N, EPI_BIAS, tile) > 0, tile              # the same shape in row panels
+    # ... and through the fp32 output: M x ldo x 4 = 2^31 with a small A
+    m_out = G31 // (4096 * 4)
+    assert L.vitamd_gemm_nt_plan(m_out, 4096, 64, 4096, EPI_PATCH, 0) == -SHAPE
+    assert _nt(L, m_out, 4096, 64, 4096, EPI_PATCH, 0, n_patches=196, seq=197, extra=1) == SHAPE
+    assert L.vitamd_gemm_nt_plan(m_out - 1, 4096, 64, 4096, EPI_PATCH, 0) > 0
+    # a row so wide that a 1280-row panel cannot stay below 2^31 bytes
+    wide = G31 // (1280 * 2) // 8 * 8 + 8
+    assert L.vitamd_gemm_nt_plan(1281, 8, 64, wide, EPI_BIAS, 0) == -SHAPE and _nt(L, 1281, 8, 64, wide, EPI_BIAS, 0) == SHAPE
+    assert L.vitamd_gemm_nt_plan(1280, 8, 64, wide - 8, EPI_BIAS, 0) > 0
+
+
+def test_nt_plan_of_a_split_call_is_the_plan_of_its_panels():
+    """explicit tile codes (their plans do not depend on the CU count): a call past 2^31 bytes of out answers what a 1280-row multiple below it does"""
+    from vitamd import lib
+    L = lib.load()
+    N, K = 8200, 128
+    rows = (G31 - 1) // (N * 2) // 1280 * 1280
+    assert rows * N * 2 < G31 <= (rows + 1280) * N * 2
+    for tile, form in ((4096, 4 | 256 << 8), (2048, 5 | 256 << 8), (256, 2 | 256 << 8), (320, 2 | 320 << 8), (128, 1 | 128 << 8)):
+        for M in (rows, rows + 1, 2 * rows + 77, 2**18 + 77):
+            assert L.vitamd_gemm_nt_plan(M, N, K, N, EPI_BIAS, tile) == form, (tile, M)
+    # the seam / loader forms' own rules still refuse through a split: N % 8 != 0
+    assert L.vitamd_gemm_nt_plan(2**18, 8204, K, 8204, EPI_BIAS, 4096) == -SHAPE and _nt(L, 2**18, 8204, K, 8204, EPI_BIAS, 4096) == SHAPE
+
+
+def test_tn_size_guard_at_its_exact_edge():
+    """(R + 64) x ld x 2 < 2^31 for both operands, all three entry points.  The accepted side is shown without a launch: a null operand is asked for
+    only after the shape has passed."""
+    from vitamd import lib
+    L = lib.load()
+    for ld in (4096, 2304, 8):
+        r_max = (G31 - 1) // (ld * 2) - 64
+        assert (r_max + 64) * ld * 2 < G31 <= (r_max + 65) * ld * 2
+        for big in ("L", "R"):
+            pq = min(64, ld)                                            # the other operand: the narrowest stride that holds it
+            ldl, ldr = (ld, pq) if big == "L" else (pq, ld)
+            for R, want in ((r_max + 1, SHAPE), (r_max, ARG)):
+                for form in (0, 1):
+                    assert L.vitamd_gemm_tn_bf16_ws(None, None, None, R, pq, pq, ldl, ldr, 64, 1, P, 1 << 30, 1, form, None) == want, (ld, big, R)
+                    assert L.vitamd_gemm_tn_bf16_ws_colsum(None, None, None, P, R, pq, pq, ldl, ldr, 64, 1, P, 1 << 30, 1, form, None) == want, (ld, big, R)
+                assert L.vitamd_gemm_tn_bf16(None, None, None, R, pq, pq, ldl, ldr, 64, 1, None) == want, (ld, big, R)
+            assert L.vitamd_gemm_tn_bf16(P, P, P, r_max + 1, pq, pq, ldl, ldr, 64, 1, None) == SHAPE

@@ -440,45 +440,98 @@ static int check_args(const GemmNtArgs& p) {
   return VITAMD_OK;
 }
 
+// ---- operand sizes.  The 256-column kernels address A, B, out, out2 and aux through buffer descriptors: 32-bit byte offsets from the start of
+// the operand, a 32-bit num_records, and masked requests / stores sent to offset 2^31 (OOB in the kernels), which is out of range only while the
+// operand is shorter than that.  So no launch ever sees an operand of 2^31 bytes or more: vitamd_gemm_nt_impl cuts M into ROW PANELS with
+// re-based A, out, out2 and aux pointers (and row0, the dropout index of the panel's first row) such that rows x K x 2 and rows x ldo x (bytes per
+// output element) both stay below NT_SPAN.  Panels are whole multiples of NT_PANEL_ROWS = lcm(256, 320) rows, so every tile of every panel
+// but the last is a tile of the unsplit launch and the full-height panels (close to 2^31 bytes of A or out each) take the form the whole would
+// have: results are bit-identical (all forms are), colsum is added to by every panel.  What a row split cannot shrink is refused: B of NT_SPAN
+// bytes or more, and the patch epilogue past the limit (its output row is a function of the global m).  The size tests of plan_single / seam_ok
+// (written when one launch had to carry the whole operand) stay as a second line behind this.
+constexpr size_t NT_SPAN = 0x80000000ull;
+constexpr int NT_PANEL_ROWS = 1280;
+
+static size_t out_esz(const GemmNtArgs& p) { return (p.epi == EPI_RESID_F32 || p.epi == EPI_PATCH_F32 || p.epi == EPI_F32) ? 4 : 2; }
+
+// rows per panel (>= M: the call is one launch), or 0: VITAMD_ERR_SHAPE
+static int panel_rows(const GemmNtArgs& p) {
+  if ((size_t)p.N * p.K * 2 >= NT_SPAN) return 0;
+  const size_t kb = (size_t)p.K * 2, ob = (size_t)p.ldo * out_esz(p), row_bytes = kb > ob ? kb : ob;      // out2 and a per-row aux are no wider than out
+  if ((size_t)p.M * row_bytes < NT_SPAN) return p.M;
+  if (p.epi == EPI_PATCH_F32) return 0;
+  return (int)((NT_SPAN - 1) / row_bytes / NT_PANEL_ROWS) * NT_PANEL_ROWS;
+}
+
+// rows [r0, r0 + rows) of a launch as a launch of its own
+static GemmNtArgs rows_of(const GemmNtArgs& p, int r0, int rows) {
+  GemmNtArgs q = p;
+  q.M = rows;
+  q.A = (const char*)p.A + (size_t)r0 * p.K * 2;
+  q.out = (char*)p.out + (size_t)r0 * p.ldo * out_esz(p);
+  if (p.out2) q.out2 = (char*)p.out2 + (size_t)r0 * p.ldo * 2;
+  if (p.aux && p.epi != EPI_PATCH_F32) q.aux = (const char*)p.aux + (size_t)r0 * p.ldo * (p.epi == EPI_RESID_F32 ? 4 : 2);
+  q.row0 = p.row0 + r0;
+  return q;
+}
+
+// the head part of a tail-split launch, or the launch itself (rows_a = 0)
+static GemmNtArgs head_of(const GemmNtArgs& p, int rows_a, bool tall) {
+  GemmNtArgs a = p;
+  if (rows_a) {
+    a.M = rows_a;
+    a.tile = tall ? p.tile : NT_TILE_256;                                   // (auto picks the 320-row form again for the head part)
+  }
+  return a;
+}
+
+// one launch (or head + 128x128 tail) over operands below NT_SPAN
+static int launch_rows(const GemmNtArgs& p, hipStream_t stream) {
+  bool tall = false;
+  const int rows_a = tail_split_rows(p, tall);
+  if (int e = dispatch_epi(head_of(p, rows_a, tall), stream)) return e;
+  if (!rows_a) return VITAMD_OK;
+  GemmNtArgs b = rows_of(p, rows_a, p.M - rows_a);
+  b.tile = NT_TILE_128;
+  return dispatch_epi(b, stream);
+}
+
+// form | rows << 8 (| 0x80: head of whole rounds in that form and a tail on 128x128 tiles) of what launch_rows would do, or -VITAMD_ERR_*
+static int plan_rows(const GemmNtArgs& p) {
+  bool tall = false;
+  const int rows_a = tail_split_rows(p, tall);
+  const NtPlan pl = plan_single(head_of(p, rows_a, tall));
+  if (pl.err) return -pl.err;
+  return pl.form | (pl.rows << 8) | (rows_a ? 0x80 : 0);
+}
+
 int vitamd_gemm_nt_impl(const GemmNtArgs& p0, hipStream_t stream) {
   if (int e = check_args(p0)) return e;
+  const int rows = panel_rows(p0);
+  if (!rows) return VITAMD_ERR_SHAPE;
   GemmNtArgs p = p0;
   if (p.epi == EPI_GELU) {                 // ONE rounding of GELU whatever kernel the launch takes: every GELU epilogue reads the table
     p.gelu_tab = gelu_table();
     if (!p.gelu_tab) return VITAMD_ERR_INIT;
   }
-  bool tall = false;
-  const int rows_a = tail_split_rows(p, tall);
-  if (rows_a) {
-    GemmNtArgs a = p, b = p;
-    a.M = rows_a;
-    a.tile = tall ? p.tile : NT_TILE_256;                                   // (auto picks the 320-row form again for the head part)
-    const size_t esz_out = (p.epi == EPI_RESID_F32 || p.epi == EPI_F32) ? 4 : 2;
-    b.M = p.M - rows_a;
-    b.A = (const char*)p.A + (size_t)rows_a * p.K * 2;
-    b.out = (char*)p.out + (size_t)rows_a * p.ldo * esz_out;
-    if (p.out2) b.out2 = (char*)p.out2 + (size_t)rows_a * p.ldo * 2;
-    if (p.aux) b.aux = (const char*)p.aux + (size_t)rows_a * p.ldo * (p.epi == EPI_RESID_F32 ? 4 : 2);
-    b.tile = NT_TILE_128;
-    b.row0 = p.row0 + rows_a;
-    if (int e = dispatch_epi(a, stream)) return e;
-    return dispatch_epi(b, stream);
-  }
-  return dispatch_epi(p, stream);
+  if (rows >= p.M) return launch_rows(p, stream);
+  const int last = (p.M - 1) / rows * rows;                                  // every refusal comes before the first launch: the two panel heights
+  if (int e = plan_rows(rows_of(p, 0, rows)); e < 0) return -e;
+  if (int e = plan_rows(rows_of(p, last, p.M - last)); e < 0) return -e;
+  for (int r0 = 0; r0 < p.M; r0 += rows)
+    if (int e = launch_rows(rows_of(p, r0, p.M - r0 < rows ? p.M - r0 : rows), stream)) return e;
+  return VITAMD_OK;
 }
 
 // vitamd_gemm_nt_plan: the kernel form vitamd_gemm_nt_bf16 would launch for these arguments on the current device, without launching:
-// form | rows << 8 (| 0x80: the launch is cut into a head of whole rounds in that form and a tail on 128x128 tiles), or -VITAMD_ERR_*.
+// form | rows << 8 (| 0x80: the launch is cut into a head of whole rounds in that form and a tail on 128x128 tiles), or -VITAMD_ERR_*.  A call
+// that is cut into row panels answers for its full-height panels (the last, shorter one may take another form).
 int vitamd_gemm_nt_plan_impl(const GemmNtArgs& p0) {
   if (int e = check_args(p0)) return -e;
-  bool tall = false;
-  GemmNtArgs p = p0;
-  const int rows_a = tail_split_rows(p, tall);
-  if (rows_a) {
-    p.M = rows_a;
-    p.tile = tall ? p.tile : NT_TILE_256;
-  }
-  const NtPlan pl = plan_single(p);
-  if (pl.err) return -pl.err;
-  return pl.form | (pl.rows << 8) | (rows_a ? 0x80 : 0);
+  const int rows = panel_rows(p0);
+  if (!rows) return -VITAMD_ERR_SHAPE;
+  if (rows >= p0.M) return plan_rows(p0);
+  const int last = (p0.M - 1) / rows * rows;
+  if (int e = plan_rows(rows_of(p0, last, p0.M - last)); e < 0) return e;
+  return plan_rows(rows_of(p0, 0, rows));
 }
