@@ -565,6 +565,43 @@ int vitamd_resize_norm_fwd(const float* img, const int* start_h, const float* ta
 int vitamd_resize_norm_bwd(const float* g_rows, int ldg, const int* start_h, const float* taps_h, int Th, const int* start_w,
                            const float* taps_w, int Tw, const float* stdv, float* dimg, int B, int C, int Hin, int Win, int S, void* stream);
 
+/* ---- the Enhancing ViT-VQGAN tokenizer -------------------------------------
+ * The model of train_enhancing_vitvqgan.py runs on the GEMM, attention, LayerNorm and quantiser entry points above; the entry points below
+ * are the rest.  Every call only enqueues on `stream`; none allocates or synchronises; no atomics: the same inputs give the same bits.
+ * (Added to ABI 9: no signature changed.)
+ *
+ * nn.Tanh between the two Linears of FeedForward (train_enhancing_vitvqgan.py:117-121) on n bf16 elements:
+ *   out[i] = bf16(tanh(float(pre[i])))
+ * computed in fp32 (within one bf16 ulp of the exact value for every bf16 input; |x| >= 20 gives exactly +-1, +-0 gives +-0, NaN stays NaN).
+ * The fc1 bias is already in `pre` (VITAMD_EPI_BIAS_BF16).  out == pre runs in place; any other overlap is not allowed.  n >= 1 (else
+ * VITAMD_ERR_SHAPE); the pointers need 2-byte alignment only (else VITAMD_ERR_ARG): elements in front of the first 16-byte boundary and
+ * behind the last whole 16-byte piece are handled one by one, and operands that sit at different offsets within 16 bytes are handled
+ * one by one throughout.  At most 2048 workgroups of 256 threads, 8 elements per thread and sweep: 4 194 304 elements per sweep of the
+ * grid-stride loop. */
+int vitamd_tanh_bf16(const void* pre, void* out, long n, void* stream);
+/* Its backward from the SAVED OUTPUT t = tanh(pre), not from the pre-activation:
+ *   dpre[i] = bf16(float(dh[i]) * (1 - float(t[i])^2))          (t^2 is exact in fp32; exactly 0 where t = +-1)
+ * dpre == dh runs in place.  The fc1 bias gradient is the column sum of dpre (vitamd_gemm_tn_bf16_ws_colsum).  Arguments and errors as
+ * above. */
+int vitamd_tanh_bwd_bf16(const void* dh, const void* t, void* dpre, long n, void* stream);
+
+/* mean |depatchify(y) - img| for the tokens of a Linear that stands for nn.ConvTranspose2d(dim, c, kernel_size = stride = p)
+ * (train_enhancing_vitvqgan.py:221-224): the arguments of vitamd_recon_mse_fwd with the feature order (c p1 p2) of that layer's weight
+ * [dim, c, p, p],
+ *   *loss = mean over b, ch, gh, p1, gw, p2 of |float(y[b*G*G + gh*G + gw, ch*p*p + p1*p + p2]) - img[b, ch, gh*p + p1, gw*p + p2]|
+ * recon: fp32 [B, c, G*p, G*p] that receives float(y) in image layout, or NULL.  ws: ws_bytes >= vitamd_recon_mse_ws_bytes(B, G, p, c, y_bf16)
+ * bytes (the same plan: one partial per workgroup, summed in a fixed order; a smaller one is VITAMD_ERR_ARG).  Shape and alignment
+ * rules, and their errors, are those of vitamd_recon_mse_fwd (a token row that is not whole 16-byte pieces, e.g. p = 2 in bf16, is
+ * VITAMD_ERR_SHAPE, for the caller to take another route). */
+int vitamd_recon_l1_fwd(const void* y, int y_bf16, const float* img, float* loss, float* recon, float* ws, long ws_bytes, int B, int G, int p,
+                        int c, int ld, void* stream);
+/* dy = (*g_loss) * sign(float(y) - img) / (B c H W) + g_recon in token layout and in y's type (the sum is formed in fp64 and rounded once
+ * to fp32, then once to bf16), row stride ld_dy.  sign(0) = 0: at a tie dy is g_recon itself.  g_loss: DEVICE fp32 or NULL (= 1);
+ * g_recon: fp32 [B, c, G*p, G*p], the gradient that arrived on `recon`, or NULL (= 0).  dy == y (with ld_dy == ld) overwrites the tokens
+ * in place. */
+int vitamd_recon_l1_bwd(const void* y, int y_bf16, const float* img, const float* g_loss, const float* g_recon, void* dy, int B, int G, int p,
+                        int c, int ld, int ld_dy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

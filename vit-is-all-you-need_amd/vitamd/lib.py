@@ -99,6 +99,10 @@ SIGNATURES = {
     "vitamd_frames_prep_grid_cap": [],
     "vitamd_crop_flip_draw": [_P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P],
     "vitamd_frames_to_u8": [_P, _P, _I, _I, _I, _I, _P],
+    "vitamd_tanh_bf16": [_P, _P, _L, _P],
+    "vitamd_tanh_bwd_bf16": [_P, _P, _P, _L, _P],
+    "vitamd_recon_l1_fwd": [_P, _I, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    "vitamd_recon_l1_bwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
 }
 
 ERRORS = {1: "unsupported shape", 2: "bad argument", 3: "HIP launch failure", 4: "vitamd_init has not run for this device"}

@@ -1285,3 +1285,83 @@ def frames_to_u8(img):
     out = torch.empty((B, H, W, C), dtype=torch.uint8, device=img.device)
     _lib.check(_L().vitamd_frames_to_u8(_p(img), _p(out), B, C, H, W, _stream()), f"frames_to_u8[B={B},C={C},H={H},W={W}]")
     return out
+
+
+# ------------------------------------------------------------------------------------------ the Enhancing ViT-VQGAN kernels
+TANH_SWEEP_ELEMS = 2048 * 256 * 8     # include/vitamd.h vitamd_tanh_bf16: elements one sweep of the grid-stride loop covers under its grid cap
+
+
+def _need_tanh_out(out, like, what):
+    if out is None:
+        return torch.empty(like.shape, dtype=BF16, device=like.device)
+    _need(out, BF16, f"{what}: out")
+    if tuple(out.shape) != tuple(like.shape) or out.device != like.device:
+        raise _lib.VitamdError(f"{what}: out must have the input's shape {tuple(like.shape)} on its device, got {tuple(out.shape)}")
+    return out
+
+
+def tanh_bf16(pre, out=None):
+    """bf16(tanh(float(pre))) on a contiguous bf16 tensor of any shape and any element offset (include/vitamd.h vitamd_tanh_bf16).
+    out: where to write (`pre` itself = in place); None allocates."""
+    _need(pre, BF16, "tanh_bf16: pre")
+    if pre.numel() < 1:
+        raise _lib.VitamdError("tanh_bf16: needs at least one element")
+    out = _need_tanh_out(out, pre, "tanh_bf16")
+    _lib.check(_L().vitamd_tanh_bf16(_p(pre), _p(out), pre.numel(), _stream()), f"tanh_bf16[n={pre.numel()}]")
+    return out
+
+
+def tanh_bwd_bf16(dh, t, out=None):
+    """bf16(float(dh) * (1 - float(t)^2)) from the saved tanh OUTPUT t (include/vitamd.h vitamd_tanh_bwd_bf16).  out: where to write
+    (`dh` itself = in place); None allocates."""
+    _need(dh, BF16, "tanh_bwd_bf16: dh"); _need(t, BF16, "tanh_bwd_bf16: t")
+    if dh.numel() < 1 or tuple(dh.shape) != tuple(t.shape) or dh.device != t.device:
+        raise _lib.VitamdError(f"tanh_bwd_bf16: dh {tuple(dh.shape)} and t {tuple(t.shape)} must be non-empty, of one shape, on one device")
+    out = _need_tanh_out(out, dh, "tanh_bwd_bf16")
+    _lib.check(_L().vitamd_tanh_bwd_bf16(_p(dh), _p(t), _p(out), dh.numel(), _stream()), f"tanh_bwd_bf16[n={dh.numel()}]")
+    return out
+
+
+recon_l1_applies = recon_mse_applies      # the L1 tail takes what the squared-error kernels take: include/vitamd.h vitamd_recon_l1_fwd
+
+
+def _need_g(g_loss, g_recon, images):
+    if g_loss is not None:
+        _need(g_loss, F32, "g_loss")
+        if g_loss.numel() != 1:
+            raise _lib.VitamdError("g_loss: expected a one-element device fp32")
+    if g_recon is not None:
+        _need(g_recon, F32, "g_recon", 4)
+        if tuple(g_recon.shape) != tuple(images.shape):
+            raise _lib.VitamdError(f"g_recon: expected {tuple(images.shape)}, got {tuple(g_recon.shape)}")
+
+
+def recon_l1_fwd(tokens, images, grid, patch, want_recon=False):
+    """-> (mean |depatchify(tokens) - images| as a 0-dim device fp32, the depatchified tokens fp32 [B, c, H, W] or None).  tokens fp32 /
+    bf16 [B*grid*grid, c*patch*patch] in the feature order (c p1 p2) of nn.ConvTranspose2d's weight (include/vitamd.h vitamd_recon_l1_fwd).
+    Shapes outside the kernel's 16-byte path raise (recon_l1_applies tells beforehand)."""
+    B, c, ld, is_bf16 = _need_recon(tokens, images, grid, patch, "recon_l1_fwd")
+    nbytes = int(_L().vitamd_recon_mse_ws_bytes(B, grid, patch, c, is_bf16))
+    _lib.check(-nbytes if nbytes < 0 else 0, f"recon_l1_fwd[B={B},G={grid},p={patch},c={c}]")
+    ws = torch.empty((nbytes // 4,), dtype=F32, device=tokens.device)
+    loss = torch.empty((), dtype=F32, device=tokens.device)
+    recon = torch.empty(tuple(images.shape), dtype=F32, device=tokens.device) if want_recon else None
+    _lib.check(_L().vitamd_recon_l1_fwd(_p(tokens), is_bf16, _p(images), _p(loss), _p(recon), _p(ws), nbytes, B, grid, patch, c, ld, _stream()),
+               f"recon_l1_fwd[B={B},G={grid},p={patch},c={c},ld={ld}]")
+    return loss, recon
+
+
+def recon_l1_bwd(tokens, images, grid, patch, g_loss=None, g_recon=None, out=None):
+    """g_loss * sign(depatchify(tokens) - images) / images.numel() + g_recon in the tokens' layout and dtype; sign(0) = 0.  g_loss: device
+    fp32 scalar (None = 1); g_recon: fp32 [B, c, H, W] (None = 0).  out: where to write (`tokens` itself = in place); None allocates a
+    dense tensor."""
+    B, c, ld, is_bf16 = _need_recon(tokens, images, grid, patch, "recon_l1_bwd")
+    _need_g(g_loss, g_recon, images)
+    if out is None:
+        out = torch.empty(tuple(tokens.shape), dtype=tokens.dtype, device=tokens.device)
+    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != tokens.dtype or tuple(out.shape) != tuple(tokens.shape)
+            or out.stride(1) != 1 or out.stride(0) < out.shape[1]):
+        raise _lib.VitamdError("recon_l1_bwd: out must be a device tensor of the tokens' shape and dtype with unit inner stride")
+    _lib.check(_L().vitamd_recon_l1_bwd(_p(tokens), is_bf16, _p(images), _p(g_loss), _p(g_recon), _p(out), B, grid, patch, c, ld, out.stride(0),
+                                        _stream()), f"recon_l1_bwd[B={B},G={grid},p={patch},c={c},ld={ld}]")
+    return out
