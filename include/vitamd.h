@@ -33,7 +33,8 @@ extern "C" {
 #define VITAMD_ERR_INIT 4    /* vitamd_init has not run for the current device (GELU epilogues need its table) */
 
 /* ABI version of this header (bumped on any signature change): 9 (the KV-cached decoding entry points; the cross-entropy and token-embedding
- * entry points, and the multi-tensor optimiser entry points vitamd_mt_*, were added to 9 without changing an existing signature). */
+ * entry points, the multi-tensor optimiser entry points vitamd_mt_* and the table advance vitamd_sched_*, were added to 9 without changing
+ * an existing signature). */
 int vitamd_abi_version(void);
 
 /* Per-device set-up, once per device and process (idempotent; device < 0 = the current device; never inside a stream capture): builds the
@@ -459,6 +460,29 @@ int vitamd_mt_sumsq(const vitamd_mt_row* rows_host, const void* rows_dev, int n_
 int vitamd_mt_adamw(const vitamd_mt_row* rows_host, const void* rows_dev, int n_rows, int total_chunks, const float* coef, void* stream);
 /* g *= *coef in place (coef required); stores nothing when *coef == 1.  Uses g alone.  For clipping in front of another optimiser. */
 int vitamd_mt_scale(const vitamd_mt_row* rows_host, const void* rows_dev, int n_rows, int total_chunks, const float* coef, void* stream);
+
+/* ---- the step-dependent floats of the table, advanced on the device ----
+ * A table that stays in device memory from step to step, so that the optimiser step can be recorded in a graph: one schedule entry per
+ * row holds the counters and the doubles from which lr, inv_bc1 and inv_sqrt_bc2 of that row follow. */
+typedef struct vitamd_sched_row {
+  long long step;          /* optimiser steps this tensor has taken (0 before the first) */
+  long long sched_t;       /* position in the learning-rate schedule (0 before the first step) */
+  double base_lr;          /* the group's base learning rate */
+  double beta1, beta2;     /* the doubles torch.optim.AdamW holds */
+  double min_ratio;        /* min_lr / base_lr: where the cosine phase ends */
+  long long warmup_steps;  /* linear warm-up over this many steps */
+  long long train_steps;   /* cosine period and the milestone from which the factor is 1 again; 0 = constant base_lr */
+} vitamd_sched_row;        /* 64 bytes, 8-byte aligned */
+long vitamd_sched_row_bytes(void);
+/* One launch, one thread per row r, any n_rows >= 1:  k = ++sched[r].step, t = sched[r].sched_t++;  in fp64
+ *   rows[r].inv_bc1 = fp32(1 / (1 - beta1^k)), rows[r].inv_sqrt_bc2 = fp32(1 / sqrt(1 - beta2^k))   (as vitamd_adamw_step_d forms them)
+ *   rows[r].lr = fp32(base_lr * factor(t)), factor = min(1, t / warmup_steps) for t < warmup_steps, else
+ *   min_ratio + (1 - min_ratio) * (1 + cos(pi * (t - warmup_steps) / train_steps)) / 2 for t < train_steps, else 1
+ * (the reference's SequentialLR, utils.lr_factor: the cosine counts from the warm-up milestone and the rate returns to base_lr at
+ * train_steps).  No other byte of a row is written.  Both arrays are DEVICE memory, 8-byte aligned (else VITAMD_ERR_ARG; n_rows < 1:
+ * VITAMD_ERR_SHAPE); nothing is read from or allocated on the host, so the call can be recorded in a graph in front of
+ * vitamd_mt_sumsq / vitamd_mt_adamw, which then find this step's values in the table. */
+int vitamd_sched_advance(void* rows_dev, void* sched_dev, int n_rows, void* stream);
 
 /* ---- training the image tokenizers -------------------------------------
  * Every call only enqueues on `stream`; none allocates or synchronises; scalars are read from and written to device memory.

@@ -222,6 +222,43 @@ __global__ __launch_bounds__(MT_THREADS) void mt_scale_kernel(const MtRow* __res
   }
 }
 
+// The step-dependent floats of every row, derived on the device from the row's schedule entry: one thread per
+// row advances the two counters and rewrites lr, inv_bc1 and inv_sqrt_bc2, so that a table which stays in device memory - and a graph
+// that recorded the launches over it - sees every step's values without the host.  fp64 throughout, each result rounded to fp32 once: the
+// bias corrections in the order vitamd_adamw_step_d forms them, the factor in the order of utils.lr_factor (contraction off: Python fuses
+// nothing).  Every store is an ordinary per-lane store to the lane's own row.
+typedef vitamd_sched_row MtSched;
+static_assert(sizeof(MtSched) == 64, "the schedule entry is part of the ABI");
+constexpr int MT_ADVANCE_THREADS = 256;
+
+__device__ __forceinline__ double mt_lr_factor(long long t, long long warmup, long long train, double min_ratio) {
+#pragma clang fp contract(off)
+  if (train == 0) return 1.0;                                   // no schedule: constant base_lr
+  if (t < warmup) {
+    const double f = (double)t / (double)warmup;
+    return f < 1.0 ? f : 1.0;
+  }
+  if (t < train) {
+    const double tt = (double)(t - warmup);                     // the cosine counts from the warm-up milestone
+    return min_ratio + (1.0 - min_ratio) * (1.0 + cos(3.14159265358979323846 * tt / (double)train)) / 2.0;
+  }
+  return 1.0;                                                   // from train_steps on: back at base_lr
+}
+
+__global__ __launch_bounds__(MT_ADVANCE_THREADS) void mt_advance_kernel(MtRow* __restrict__ rows, MtSched* __restrict__ sched, int n_rows) {
+#pragma clang fp contract(off)
+  const long long r = (long long)blockIdx.x * MT_ADVANCE_THREADS + threadIdx.x;
+  if (r >= n_rows) return;
+  const MtSched s = sched[r];
+  const long long k = s.step + 1, t = s.sched_t;
+  sched[r].step = k;
+  sched[r].sched_t = t + 1;
+  const double bc1 = 1.0 - pow(s.beta1, (double)k), bc2 = 1.0 - pow(s.beta2, (double)k);
+  rows[r].inv_bc1 = (float)(1.0 / bc1);
+  rows[r].inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  rows[r].lr = (float)(s.base_lr * mt_lr_factor(t, s.warmup_steps, s.train_steps, s.min_ratio));
+}
+
 // The host's copy of the table is what the entry points check: the chunk plan (first_chunk is the running sum of ceil(n / MT_CHUNK), the
 // total is total_chunks, so no chunk index can reach past a tensor) and every tensor pointer, before anything is launched.
 int mt_check(const MtRow* rows, int n_rows, int total_chunks, bool with_state) {
@@ -294,6 +331,16 @@ extern "C" int vitamd_mt_adamw(const vitamd_mt_row* rows_host, const void* rows_
   const dim3 grid(mt_grid(total_chunks)), block(MT_THREADS);
   if (coef) hipLaunchKernelGGL(mt_adamw_kernel<true>, grid, block, 0, (hipStream_t)stream, (const MtRow*)rows_dev, n_rows, total_chunks, coef);
   else hipLaunchKernelGGL(mt_adamw_kernel<false>, grid, block, 0, (hipStream_t)stream, (const MtRow*)rows_dev, n_rows, total_chunks, coef);
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+extern "C" long vitamd_sched_row_bytes(void) { return (long)sizeof(MtSched); }
+
+extern "C" int vitamd_sched_advance(void* rows_dev, void* sched_dev, int n_rows, void* stream) {
+  if (n_rows < 1) return VITAMD_ERR_SHAPE;
+  if (!rows_dev || !sched_dev || (((uintptr_t)rows_dev | (uintptr_t)sched_dev) & 7)) return VITAMD_ERR_ARG;
+  const int grid = (int)(((long long)n_rows + MT_ADVANCE_THREADS - 1) / MT_ADVANCE_THREADS);      // n_rows <= 2^31 - 1: at most 2^23 workgroups
+  hipLaunchKernelGGL(mt_advance_kernel, dim3(grid), dim3(MT_ADVANCE_THREADS), 0, (hipStream_t)stream, (MtRow*)rows_dev, (MtSched*)sched_dev, n_rows);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 

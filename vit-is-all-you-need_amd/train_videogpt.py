@@ -274,6 +274,9 @@ def parse_args(argv=None):
     p.add_argument("--train_steps", type=int, default=50)
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
+    p.add_argument("--graph", action="store_true",
+                   help="one graph launch per iteration (vitamd.graph.GraphedTrainStep): forward, loss, backward, the clip, the LR schedule "
+                        "and the AdamW update, all replayed from the device; needs --dropout 0")
     p.add_argument("--tokenizer", type=str, default="none", choices=("none", "tatitok"),
                    help="none: seeded random token ids; tatitok: a random-weight train_tatitok.TiTok (latent_tokens = frame_size) tokenises "
                         "seeded random frames and decodes one generated continuation at the end")
@@ -292,9 +295,12 @@ def make_tatitok(args, device):
 
 
 def make_optim(model, args):
+    from vitamd.optim import AdamW
+    if getattr(args, "graph", False):
+        return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm, capturable=True,
+                     schedule=(args.warmup_steps, args.train_steps, args.lr / 10))
     if args.max_grad_norm is None:
         return torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
-    from vitamd.optim import AdamW
     return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
 
 
@@ -304,7 +310,7 @@ def main(argv=None):
     cfg = VideoGPTConfig(args.frame_size, args.codebook_size, args.transformer, args.max_frames, args.dropout)
     model = VideoGPT(cfg).to(dev)
     optim = make_optim(model, args)
-    sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
+    sched = None if args.graph else get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
     g = torch.Generator(device="cpu").manual_seed(0)
     titok = None
     if args.tokenizer == "tatitok":
@@ -313,9 +319,13 @@ def main(argv=None):
         tokens = frames_to_tokens(titok, videos)
     else:
         tokens = torch.randint(0, args.codebook_size, (args.bs, args.max_frames, args.frame_size), generator=g).to(dev)
+    graphed = None
+    if args.graph:
+        from vitamd.graph import GraphedTrainStep
+        graphed = GraphedTrainStep(model, lambda tok: model.loss(tok), (tokens,), optim)      # refuses dropout > 0
     for step in range(args.train_steps):
         t0 = time.time()
-        loss = train_step(model, tokens, optim, sched)
+        loss = graphed(tokens) if graphed is not None else train_step(model, tokens, optim, sched)
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} {tokens.numel() / (time.time() - t0):.0f} tokens/s")
     if titok is not None:

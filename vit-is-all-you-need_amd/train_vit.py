@@ -91,23 +91,33 @@ def parse_args(argv=None):
                    help="feed seeded random uint8 frames through vitamd.data.DeviceLoader (the device input pipeline: random crop and flip, ImageNet normalisation) instead of one fp32 batch")
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
+    p.add_argument("--dropout", type=float, default=0.0)
+    p.add_argument("--graph", action="store_true",
+                   help="one graph launch per iteration (vitamd.graph.GraphedTrainStep): forward, loss, backward, the clip, the LR schedule "
+                        "and the AdamW update, all replayed from the device; needs --dropout 0 (and not --u8)")
     return p.parse_args(argv)
 
 
 def make_optim(model, args):
+    from vitamd.optim import AdamW
+    if getattr(args, "graph", False):
+        return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm, capturable=True,
+                     schedule=(args.warmup_steps, args.train_steps, args.lr / 10))
     if args.max_grad_norm is None:
         return torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
-    from vitamd.optim import AdamW
     return AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
 
 
-def main():
-    args = parse_args()
+def main(argv=None):
+    args = parse_args(argv)
+    if args.graph and args.u8:
+        raise SystemExit("--graph with --u8: the device loader hands over vitamd.data.Frames (patch rows in buffers of its own), not tensors "
+                         "to copy into a graph's static inputs; a graph-fed loader is not built - use one or the other")
     dev = torch.device("cuda")
-    cfg = ViTConfig(args.image_size, 3, args.patch_size, args.transformer, args.extra_tokens, 0.0)
+    cfg = ViTConfig(args.image_size, 3, args.patch_size, args.transformer, args.extra_tokens, args.dropout)
     model = ViTClassifier(cfg, args.num_classes).to(dev)
     optim = make_optim(model, args)
-    sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
+    sched = None if args.graph else get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
     g = torch.Generator(device="cpu").manual_seed(0)
     images = torch.randn(args.bs, 3, args.image_size, args.image_size, generator=g).to(dev)
     labels = torch.randint(0, args.num_classes, (args.bs,), generator=g).to(dev)
@@ -119,11 +129,16 @@ def main():
         host_labels = labels.cpu()
         host = ((u8, host_labels) for _ in range(args.train_steps))
         feed = DeviceLoader(host, dev, args.image_size, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)
+    graphed = None
+    if args.graph:
+        from vitamd.graph import GraphedTrainStep
+        loss_fn = nn.functional.cross_entropy
+        graphed = GraphedTrainStep(model, lambda x, y: loss_fn(model(x), y), (images, labels), optim)      # refuses dropout > 0
     for step in range(args.train_steps):
         t0 = time.time()
         if feed is not None:
             images, labels = next(feed)
-        loss = train_step(model, images, labels, optim, sched)
+        loss = graphed(images, labels) if graphed is not None else train_step(model, images, labels, optim, sched)
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} {args.bs / (time.time() - t0):.0f} img/s")
 

@@ -17,6 +17,9 @@ captured launches) and not under vitamd.ddp.DataParallel: its per-parameter hook
 that runs DURING backward and decides, from bucket state, what to enqueue (and torch.distributed work handles are waited for on the
 host in finish()); none of that replays from a graph.  A DataParallel model is refused at construction.
 
+GraphedTrainStep records the optimiser as well: with vitamd.optim.AdamW(capturable=True) the step count, the bias corrections and the
+learning-rate schedule live on the device, so the whole iteration - the update included - is one graph launch.
+
 GraphedDecoder is the other captured form: one decode step of KV-cached generation (vitamd/decode.py) as one graph launch.  Every value
 a decode step depends on lives on the device - the cache length, the sampler's stream position, the token just picked - so a replay
 needs no host value and generation never synchronises.
@@ -77,6 +80,129 @@ class GraphedStep:
         self.y.copy_(y, non_blocking=True)
         self.graph.replay()
         F.WEIGHTS.clear()                            # host-side cache state: whatever eager call comes next must re-cast
+        for p, g in zip(self.params, self.grads):
+            p.grad = g
+        return self.loss
+
+
+class GraphedTrainStep:
+    """The whole training iteration as one graph launch: weight casts, forward, loss, backward, [gradient norm + clip], the advance of
+    the optimiser's device-resident counters and schedule, and the update.
+
+        optim = vitamd.optim.AdamW(model.parameters(), lr=..., capturable=True, schedule=(warmup_steps, train_steps, min_lr))
+        step = GraphedTrainStep(model, lambda x, y: lm.cross_entropy(model(x), y), (x_example, y_example), optim)
+        for x, y in loader:
+            loss = step(x, y)          # static tensor: read it before the next call; optim.param_groups[0]["lr"] follows on the host
+
+    step_fn(*inputs) -> 0-dim loss is free-form (`lambda tok: model.loss(tok)` for VideoGPT).  Shapes and dtypes of the inputs are frozen
+    at capture; dropout > 0 and vitamd.ddp.DataParallel are refused for GraphedStep's reasons.  Construction runs forward and backward
+    (never the optimiser) on the model, and the optimiser's launches once over a throw-away table: parameters, moments, step counts and
+    the schedule position are what they were, and the first replay is step 1.
+
+    The graph bakes in addresses: the parameters, the moments, the static gradients and the optimiser's resident table.  Every call
+    compares them with the current ones first and captures again when one moved (`captures` counts) - after optim.load_state_dict, for
+    instance, whose moments are new tensors and whose step counts re-seed the device counters."""
+
+    def __init__(self, model: torch.nn.Module, step_fn, example_inputs, optim, warmup: int = 3):
+        from . import optim as _optim
+        from .ddp import DataParallel
+        if isinstance(example_inputs, torch.Tensor):
+            example_inputs = (example_inputs,)
+        example_inputs = tuple(example_inputs)
+        if not example_inputs or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in example_inputs):
+            raise F.ops._lib.VitamdError("GraphedTrainStep needs device tensors as example inputs (there is no CPU path)")
+        for m in model.modules():
+            if float(getattr(m, "dropout", 0.0) or 0.0) > 0.0:
+                raise NotImplementedError("GraphedTrainStep with dropout > 0: the mask seed would be frozen into the graph")
+        if isinstance(model, DataParallel) or any(isinstance(m, DataParallel) for m in model.modules()):
+            raise NotImplementedError("GraphedTrainStep around vitamd.ddp.DataParallel: the bucket hooks run Python during backward (see the module docstring)")
+        if not (isinstance(optim, _optim.AdamW) and optim.capturable):
+            raise ValueError("GraphedTrainStep needs vitamd.optim.AdamW(..., capturable=True): any other optimiser step reads host values "
+                             "that a graph would freeze")
+        self.model, self.step_fn, self.optim = model, step_fn, optim
+        self.inputs = [t.detach().clone() for t in example_inputs]
+        self.params = [p for p in model.parameters() if p.requires_grad]
+        self.device = self.inputs[0].device
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.warmup = max(1, int(warmup))
+        self.graph, self.loss, self.grads, self.captures, self._table, self._table_grads = None, None, [], 0, None, []
+        with torch.cuda.device(self.device):
+            self._capture()
+
+    def _eager(self, zero=True):
+        if zero:
+            self._drop_grads()
+        F.WEIGHTS.clear()                               # the weight casts are part of every step (the update changes the weights)
+        loss = self.step_fn(*self.inputs)
+        if loss.dim() != 0:
+            raise ValueError(f"GraphedTrainStep: step_fn must return a 0-dim loss, got {tuple(loss.shape)}")
+        loss.backward()
+        return loss
+
+    def _drop_grads(self):
+        self.model.zero_grad(set_to_none=True)
+        for group in self.optim.param_groups:
+            for p in group["params"]:
+                p.grad = None
+
+    def _capture(self):
+        optim, s = self.optim, self.stream
+        self.graph = self.loss = self._table = None     # a graph being replaced is never replayed again
+        self.grads, self._table_grads = [], []
+        optim._check_lr()
+        items = [(group, p) for group in optim.param_groups for p in group["params"] if p.requires_grad]
+        # warm up ON THE CAPTURE STREAM, as GraphedStep does; the optimiser's launches too, over a table of their own
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(self.warmup):
+                self._eager()
+            missing = sum(p.grad is None for _, p in items)
+            self._drop_grads()                          # so the captured backward ASSIGNS fresh gradient tensors
+            if not missing:
+                optim.warm_launches(self.device)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        if missing or not items:
+            raise F.ops._lib.VitamdError(f"GraphedTrainStep: {missing} of the optimiser's {len(items)} parameters got no gradient from "
+                                         "step_fn; the resident table needs one for every row (freeze or drop those parameters)")
+        optim._build(items, bind=False)                 # moments (created here when missing) and device buffers: outside the capture
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=s):
+            loss = self._eager(zero=False).detach()     # detached for GraphedStep's reason
+            optim._bind()                               # host work: the static gradients' addresses, known only now
+            optim._enqueue(torch.cuda.current_stream().cuda_stream)
+        optim._upload_table()                           # the capture ran nothing: the table reaches the device before the first replay
+        self.graph, self.loss, self._table = graph, loss, optim._table
+        self.grads = [p.grad for p in self.params]
+        self._table_grads = [p.grad for _, p in items]
+        self.captures += 1
+
+    def _stale(self):
+        optim, t = self.optim, self._table
+        if self.graph is None or t is None or optim._table is not t or t.hypers != optim._hypers():
+            return True
+        now = []
+        for (_, p), g in zip(t.items, self._table_grads):
+            st = optim.state[p] if p in optim.state else {}
+            now.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr() if "exp_avg" in st else 0,
+                        st["exp_avg_sq"].data_ptr() if "exp_avg_sq" in st else 0))
+        return now != t.ptrs
+
+    def __call__(self, *inputs) -> torch.Tensor:
+        if len(inputs) != len(self.inputs) or any(not isinstance(a, torch.Tensor) or a.shape != b.shape or a.dtype != b.dtype
+                                                 for a, b in zip(inputs, self.inputs)):
+            raise F.ops._lib.VitamdError("GraphedTrainStep was captured for inputs of "
+                                         + ", ".join(f"{tuple(b.shape)} {b.dtype}" for b in self.inputs))
+        with torch.cuda.device(self.device):
+            self.optim._check_lr()
+            if self._stale():
+                self._capture()
+            for dst, src in zip(self.inputs, inputs):
+                dst.copy_(src, non_blocking=True)
+            self.graph.replay()
+        self.optim._advance_mirrors()                   # step counts, schedule position and group["lr"]: no device read
+        F.WEIGHTS.clear()                               # host-side cache state: whatever eager call comes next must re-cast
         for p, g in zip(self.params, self.grads):
             p.grad = g
         return self.loss

@@ -59,6 +59,8 @@ SIGNATURES = {
     "vitamd_mt_sumsq": [_P, _P, _I, _I, _P, _P, _F, _P],
     "vitamd_mt_adamw": [_P, _P, _I, _I, _P, _P],
     "vitamd_mt_scale": [_P, _P, _I, _I, _P, _P],
+    "vitamd_sched_row_bytes": [],
+    "vitamd_sched_advance": [_P, _P, _I, _P],
     "vitamd_kv_append": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_decode_attention_ws_bytes": [_I, _I, _I],
     "vitamd_decode_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
