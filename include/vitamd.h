@@ -227,6 +227,8 @@ int vitamd_kv_append(const void* qkv, void* k_cache, void* v_cache, const int* l
  * position *len) against cache positions 0 .. *len, scale 1/8, fp32 softmax -> o bf16 [B, H*64] (vitamd_attention_fwd's layout).
  * Long caches are split across workgroups (flash-decoding); the partials go to `ws` (vitamd_decode_attention_ws_bytes(B, H, Lmax)
  * bytes, may be NULL when that is 0) and are merged in a fixed order: results are bit-reproducible.  B*H <= 65535.
+ * *len >= Lmax is clamped to the last position (the cache is never read outside [0, Lmax)); with *len < 0 no key lies below the length and
+ * o is left untouched, whether the cache is split or not.
  * replaces transformer.py:28-29 (causal SDPA) for the last query row. */
 long vitamd_decode_attention_ws_bytes(int B, int H, int Lmax);
 int vitamd_decode_attention(const void* qkv, const void* k_cache, const void* v_cache, void* o, const int* len, int B, int H,

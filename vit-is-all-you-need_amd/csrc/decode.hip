@@ -180,6 +180,7 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(__bf16* __restr
   const int bh = blockIdx.x, d = threadIdx.x;
   const int n = *len + 1;
   const int nv = min((n + chunk - 1) / chunk, nch);
+  if (nv <= 0) return;                                // *len < 0: no chunk lies below the length, o stays as it is (as in the unsplit form)
   const float* pm = ws + (size_t)gridDim.x * nch * DH + (size_t)bh * nch * 2;
   const float* pa = ws + (size_t)bh * nch * DH + d;
   float mm = NEG_BIG;
