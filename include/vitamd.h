@@ -210,6 +210,33 @@ int vitamd_attention_fwd_keep(const void* qkv, void* o, float* lse2, int B, int 
 int vitamd_attention_bwd_keep(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta,
                               float* dbias, int B, int N, int H, int head_dim, int nq, void* stream);
 
+/* Which kernels an attention call would launch (nothing is launched, no pointer is needed).  The launchers switch on the same host
+ * function that answers here, so the two cannot disagree.  nq = 0: vitamd_attention_fwd / _fwd_resid (resid != 0) / _bwd (backward != 0;
+ * the backward has no residual form, resid is ignored); nq > 0: vitamd_attention_fwd_keep / _bwd_keep, for which causal, dropout_p and
+ * resid must be 0 (-VITAMD_ERR_ARG).
+ * The answer is  family | key tiles << 4 | query tiles << 8 | flags : the kernel family and the template arguments of the
+ * instantiation(s) launched, so two calls get the same code if and only if they launch the same machine code.  A field the family is
+ * not templated on is 0: the tile counts of VITAMD_ATTN_FWD_LOOP, _FWD_LONG, _BWD_LOOP and _BWD_LONG, the query tiles of every forward
+ * family, VITAMD_ATTN_CAUSAL where causal is read at run time (_FWD_LOOP and the long families).  VITAMD_ATTN_BWD_PIPE without
+ * VITAMD_ATTN_KEEP has query tiles = key tiles.
+ * A negative value is -VITAMD_ERR_* exactly where the entry point refuses: N <= 0, N > 16384, resid with N > 256 and a kept form that
+ * vitamd_attention_keep_forms does not serve are -VITAMD_ERR_SHAPE, and answer before a dropout_p outside [0, 1): -VITAMD_ERR_ARG. */
+#define VITAMD_ATTN_FWD_SMALL 1    /* attn_fwd_small_kernel<tiles 1..8, DROP, CAUSAL, RES>: 4 waves, register-resident score row */
+#define VITAMD_ATTN_FWD_SMALL8 2   /* attn_fwd_small8_kernel<tiles 5..8, RES, KEEP>: 8 waves; non-causal, no dropout */
+#define VITAMD_ATTN_FWD_LOOP 3     /* attn_fwd_kernel<DROP>: online softmax over 9..16 tiles */
+#define VITAMD_ATTN_FWD_LONG 4     /* attn_fwd_long_kernel<DROP>: N > 512 */
+#define VITAMD_ATTN_BWD_PIPE 5     /* attn_bwd_dq_pipe_kernel + attn_bwd_dkv_pipe_kernel<tiles 2..7, query tiles, LIM = KEEP> */
+#define VITAMD_ATTN_BWD_LOOP 6     /* attn_bwd_dq_kernel + attn_bwd_dkv_kernel<DROP, CAUSAL> */
+#define VITAMD_ATTN_BWD_LONG 7     /* attn_bwd_dq_long_kernel + attn_bwd_dkv_long_kernel<DROP>: N > 512 */
+#define VITAMD_ATTN_FAMILY(code) ((code) & 0xf)
+#define VITAMD_ATTN_TILES(code) ((code) >> 4 & 0xf)
+#define VITAMD_ATTN_QTILES(code) ((code) >> 8 & 0xf)
+#define VITAMD_ATTN_DROP 0x1000
+#define VITAMD_ATTN_CAUSAL 0x2000
+#define VITAMD_ATTN_RES 0x4000
+#define VITAMD_ATTN_KEEP 0x8000    /* KEEP of the eight-wave forward, LIM of the pipelined backward */
+int vitamd_attention_form(int N, int causal, float dropout_p, int resid, int nq, int backward);
+
 /* ---- KV-cached decoding (autoregressive generation on a causal stack) ---------------------------------
  * The reference has no cache: VideoGPT.generate (train_videogpt.py:56-65) re-runs the whole stack over the whole prefix for every new
  * token.  These entry points run one token per sequence per call against a per-layer cache instead.

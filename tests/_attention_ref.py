@@ -13,7 +13,9 @@ The distance restate <-> ref64 is the bf16 floor the kernels are held to (bounds
 (batch, head, 32-row tile), so that one wrong tile of a long sequence is not diluted.  MUTANTS are the deliberate mistakes
 test_attention_ref_host.py proves the GPU tests would catch; the probe_* / decode_* functions make every keep decision of each of the
 three dropout consumers (forward, dQ kernel, dK/dV kernel) visible in an output.  long_* are row-chunked forms for N = 16 384 that never
-hold an N x N matrix.  MATRIX / PROBE_CASES / SPIKE_CASES are the cases of tests/test_gpu_attention_matrix.py, shared with the host test."""
+hold an N x N matrix.  MATRIX / PROBE_CASES / SPIKE_CASES are the cases of tests/test_gpu_attention_matrix.py, shared with the host test.
+FORM_CASES (last section) are the cases of tests/test_gpu_attention_forms.py: every kernel instantiation a call can reach, at both edges of
+its tile count; coverage_gaps() is the rule tests/test_attention_forms_host.py proves from the library's own vitamd_attention_form."""
 import functools
 import math
 
@@ -255,7 +257,7 @@ def one_key_residue(got, ref_in):
 
 
 # ------------------------------------------------------------------------------------------ the cases
-# (B, N, H, causal, p): the kernel form each reaches is in the docstring of tests/test_gpu_attention_matrix.py
+# (B, N, H, causal, p): the kernel family each reaches is MATRIX_FAMILIES below (asked of vitamd_attention_form by the tests)
 MATRIX = [(2, 1, 2, True, 0.0), (2, 1, 2, True, 0.3), (2, 5, 1, False, 0.5), (1, 32, 2, True, 0.3),
           (2, 37, 2, True, 0.3), (2, 37, 2, False, 0.3), (1, 197, 2, True, 0.3), (1, 197, 2, False, 0.3),
           (2, 256, 1, True, 0.1), (2, 256, 1, False, 0.5),
@@ -487,3 +489,184 @@ def long_reference(N=LONG_N, tiles=LONG_TILES):
     ref.update(o=o, lse=lse)
     rs.update(o=o_rs, lse=lse)
     return {"qkv": qkv, "d_o": d_o, "ref": ref, "restate": rs, "floors": floors(ref, rs)}
+
+
+# ------------------------------------------------------------------------------------------ every instantiated form (test_gpu_attention_forms.py)
+# The codes of include/vitamd.h vitamd_attention_form: family | key tiles << 4 | query tiles << 8 | flags
+FWD_SMALL, FWD_SMALL8, FWD_LOOP, FWD_LONG, BWD_PIPE, BWD_LOOP, BWD_LONG = 1, 2, 3, 4, 5, 6, 7
+F_DROP, F_CAUSAL, F_RES, F_KEEP = 0x1000, 0x2000, 0x4000, 0x8000
+FAMILY_NAMES = {FWD_SMALL: "attn_fwd_small_kernel", FWD_SMALL8: "attn_fwd_small8_kernel", FWD_LOOP: "attn_fwd_kernel", FWD_LONG: "attn_fwd_long_kernel",
+                BWD_PIPE: "attn_bwd_*_pipe_kernel", BWD_LOOP: "attn_bwd_*_kernel", BWD_LONG: "attn_bwd_*_long_kernel"}
+TILED_FAMILIES = (FWD_SMALL, FWD_SMALL8, BWD_PIPE)          # templated on the key-tile count
+FORM_B, FORM_H, FORM_P = 2, 2, 0.3                           # B*H = 4: every wave rotation on every tile count; batch stride and head offset live
+
+
+def form_code(family, nt=0, nqt=0, drop=False, causal=False, res=False, keep=False):
+    return family | nt << 4 | nqt << 8 | (F_DROP if drop else 0) | (F_CAUSAL if causal else 0) | (F_RES if res else 0) | (F_KEEP if keep else 0)
+
+
+def code_name(code):
+    fam, nt, nqt = code & 0xf, code >> 4 & 0xf, code >> 8 & 0xf
+    flags = [n for n, b in (("DROP", F_DROP), ("CAUSAL", F_CAUSAL), ("RES", F_RES), ("KEEP", F_KEEP)) if code & b]
+    return f"{FAMILY_NAMES.get(fam, fam)}<{', '.join(([f'{nt} tiles'] if nt else []) + ([f'{nqt} query tiles'] if nqt else []) + flags)}>"
+
+
+def edges(t):
+    """the two lengths of t key tiles a form is run at: one valid key in the last tile, and the tile full"""
+    return (TILE * (t - 1) + 1, TILE * t)
+
+
+def _form_cases():
+    """-> {case: [the codes it was chosen for]}; case = (B, N, H, causal, p, resid, nq)"""
+    out = {}
+    # ordinary entry points, with the residual epilogue (the test also makes the call without it: both RES forms): every tile count x
+    # causal x dropout at both edges.  Chosen for: forward with RES, forward without, backward.
+    for t in range(1, 9):
+        for causal in (False, True):
+            for p in (0.0, FORM_P):
+                drop = p > 0
+                eight = t >= 5 and not drop and not causal
+                fwd = [form_code(FWD_SMALL8, t, res=r) if eight else form_code(FWD_SMALL, t, drop=drop, causal=causal, res=r) for r in (True, False)]
+                bwd = form_code(BWD_PIPE, t, t) if 2 <= t <= 7 and not drop and not causal else form_code(BWD_LOOP, drop=drop, causal=causal)
+                for N in edges(t):
+                    out[(FORM_B, N, FORM_H, causal, p, True, 0)] = fwd + [bwd]
+    # kept-query backward: every (key tiles, query tiles) pair; nq at its ragged edge 32(q-1)+1 and at min(32q, N, 128), one with each N edge
+    # (which with which alternates, so that all four combinations occur).  Chosen for: the kept backward, and the kept forward where served.
+    for t in range(2, 8):
+        for q in range(1, min(t, 4) + 1):
+            (n_rag, n_ex), q_rag = edges(t), TILE * (q - 1) + 1
+            pairs = ((n_rag, q_rag), (n_ex, None)) if (t + q) % 2 == 0 else ((n_rag, None), (n_ex, q_rag))
+            for N, nq in pairs:
+                nq = min(TILE * q, N, 128) if nq is None else nq
+                out[(FORM_B, N, FORM_H, False, 0.0, False, nq)] = [form_code(BWD_PIPE, t, q, keep=True)] + ([form_code(FWD_SMALL8, t, keep=True)] if t >= 5 else [])
+    # kept-query forward: nq in {1, 33, 128, N} over 5..8 tiles.  (129, 1), (161, 33) and (193, 128) are cases of the list above; 8 tiles
+    # (no kept backward there) at both edges, with nq = N and nq = 33:
+    for N, nq in ((225, 225), (256, 33)):
+        out[(FORM_B, N, FORM_H, False, 0.0, False, nq)] = [form_code(FWD_SMALL8, 8, keep=True)]
+    return out
+
+
+FORM_EXPECT = _form_cases()
+FORM_CASES = list(FORM_EXPECT)
+assert all(c in FORM_EXPECT for c in ((FORM_B, 129, FORM_H, False, 0.0, False, 1), (FORM_B, 161, FORM_H, False, 0.0, False, 33),
+                                      (FORM_B, 193, FORM_H, False, 0.0, False, 128)))
+# tile-templated forms whose range of lengths admits only one of the two edges: {code: reason}.  None: every instantiated tile count t
+# accepts 32(t-1)+1 as well as 32t, and a kept form of q = t query tiles accepts nq = N at the ragged N.
+ONE_EDGE = {}
+# the family (forward, backward) each MATRIX case reaches, as the docstring of tests/test_gpu_attention_matrix.py used to state in prose
+MATRIX_FAMILIES = [(FWD_SMALL, BWD_LOOP) if c[1] <= 256 else (FWD_LOOP, BWD_LOOP) if c[1] <= 512 else (FWD_LONG, BWD_LONG) for c in MATRIX]
+
+
+def form_case_id(c):
+    B, N, H, causal, p, resid, nq = c
+    return f"N{N}-{'causal' if causal else 'full'}-p{p}" + ("-resid" if resid else "") + (f"-nq{nq}" if nq else "")
+
+
+def form_case_calls(c, form):
+    """The (N, causal, p, resid, nq, backward) calls the GPU test of form case c makes.  form(*call) is vitamd_attention_form: it tells
+    which kept forms are served (a kept case runs those, and beside them the full-size calls they are compared with)."""
+    B, N, H, causal, p, resid, nq = c
+    if nq == 0:
+        return ([(N, causal, p, True, 0, False)] if resid else []) + [(N, causal, p, False, 0, False), (N, causal, p, False, 0, True)]
+    calls = [(N, False, 0.0, False, 0, False)]
+    if form(N, False, 0.0, False, nq, False) >= 0:
+        calls.append((N, False, 0.0, False, nq, False))
+    if form(N, False, 0.0, False, nq, True) >= 0:
+        calls += [(N, False, 0.0, False, 0, True), (N, False, 0.0, False, nq, True)]
+    return calls
+
+
+def other_case_calls():
+    """the calls of MATRIX, PROBE_CASES, SPIKE_CASES and the long-sequence case (forward and backward each)"""
+    calls = [(N, causal, p) for (B, N, H, causal, p) in MATRIX]
+    calls += [(N, causal, PROBE_P) for N, causal in PROBE_CASES]
+    calls += [(N, causal, 0.0) for N, key in SPIKE_CASES for causal in (False, True)]
+    calls += [(LONG_N, True, 0.0)]
+    return [(N, causal, p, False, 0, bwd) for N, causal, p in calls for bwd in (False, True)]
+
+
+def coverage_gaps(swept, form, cases=None):
+    """swept: the codes the library can answer.  -> [what is unreached]: a code no case's call gets, or a tile-templated code some case
+    reaches but not at both edges() of its tile count (ONE_EDGE excepted)."""
+    cases = FORM_CASES if cases is None else cases
+    reached = {}
+    for call in [call for c in cases for call in form_case_calls(c, form)] + other_case_calls():
+        reached.setdefault(form(*call), set()).add(call[0])
+    gaps = []
+    for code in sorted(swept):
+        if code not in reached:
+            gaps.append(f"{code:#x} {code_name(code)}: no case")
+        elif code & 0xf in TILED_FAMILIES:
+            missing = [N for N in edges(code >> 4 & 0xf) if N not in reached[code]]
+            if missing and code not in ONE_EDGE:
+                gaps.append(f"{code:#x} {code_name(code)}: not run at N = {missing}")
+    return gaps
+
+
+def form_inputs(c):
+    """qkv [B*N, 3*H*64], d_o [B*N, H*64] (a kept case: COMPACT [B*nq, H*64]), x0 [B*N, H*64] fp32; qkv and d_o hold bf16 values"""
+    B, N, H, causal, p, resid, nq = c
+    seed = 70000 + 64 * N + 8 * nq * 1000 + 4 * int(causal) + 2 * int(p > 0)
+    rows = B * (nq or N)
+    return r16(randn((B * N, 3 * H * 64), seed, 1.5)), r16(randn((rows, H * 64), seed + 1)), randn((B * N, H * 64), seed + 2, 2.0)
+
+
+def pad_rows(x, B, N, nq):
+    """compact [B*nq, W] -> [B*N, W] with zero rows for the tokens >= nq"""
+    out = torch.zeros((B, N, x.shape[-1]), dtype=x.dtype, device=x.device)
+    out[:, :nq] = x.view(B, nq, -1)
+    return out.view(B * N, -1)
+
+
+@functools.lru_cache(maxsize=None)
+def form_reference(c):
+    """computed once per case and shared; treat as read-only.  A kept case: ref64 and restate on d_o zero-padded to N rows"""
+    B, N, H, causal, p, resid, nq = c
+    qkv, d_o, _ = form_inputs(c)
+    return _reference(qkv, pad_rows(d_o, B, N, nq) if nq else d_o, B, N, H, causal, p, SEED)
+
+
+def keep_slice(t, nq):
+    """{name: [B, H, N, ...]} -> the kept forward's part: o and lse of the queries < nq"""
+    return {"o": t["o"][..., :nq, :], "lse": t["lse"][..., :nq]}
+
+
+# two mistakes a kept-query backward can make, as restatements: name -> d_o [B, H, N, 64] the mistaken kernel works from
+def _keep_d_o(c, row):
+    """d_o as a kernel sees it that reads row(b, t) of the compact buffer for every query t < 32 * ceil(nq / 32) (wrapping inside the buffer)"""
+    B, N, H, causal, p, resid, nq = c
+    compact = form_inputs(c)[1]
+    t_end = min(N, TILE * ((nq + TILE - 1) // TILE))
+    full = torch.zeros(B, N, H * 64)
+    for b in range(B):
+        for t in range(t_end):
+            full[b, t] = compact[row(b, t) % (B * nq)]
+    return heads(full.view(B * N, H * 64), B, N, H)
+
+
+def _keep_mutant_pad_lse(c):
+    """the padded queries nq .. 32*NQT-1 of the last kept tile keep their real lse (their P is not zero) and read on in the compact d_o"""
+    nq = c[6]
+    return _keep_d_o(c, lambda b, t: b * nq + t)
+
+
+def _keep_mutant_stride(c):
+    """d_o row b*nq + t read as b*N + t; the padded queries still contribute nothing"""
+    B, N, H, causal, p, resid, nq = c
+    g = _keep_d_o(c, lambda b, t: b * N + t).clone()
+    g[..., nq:, :] = 0
+    return g
+
+
+KEEP_MUTANTS = {"padded queries of the last kept tile keep their lse": _keep_mutant_pad_lse,
+                "compact d_o indexed with the dense batch stride": _keep_mutant_stride}
+
+
+def keep_mutant_outputs(name, c):
+    """restate() of kept case c as the mistaken kernel would compute it; the Q rows >= nq are written as zeros as in the real one"""
+    r = form_reference(c)
+    q, k, v, _ = r["in"]
+    out = dict(restate(q, k, v, KEEP_MUTANTS[name](c), None, False))
+    out["dq"] = out["dq"].clone()
+    out["dq"][..., c[6]:, :] = 0
+    return out

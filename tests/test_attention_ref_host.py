@@ -2,7 +2,8 @@
 arithmetic sits inside both bounds against the fp64 reference - the condition the cases were chosen for; (b) each listed mutation of the
 restatement breaks a bound on at least one case (or, for the mask mutations, is also seen by the probe decoders); (c) the probe decoders
 recover mask() exactly from restated outputs and see every single flipped decision; (d) mask() and ref64() agree with the definitions they
-restate (_dropout_ref.keep at hand-written indices, oracle.sdpa)."""
+restate (_dropout_ref.keep at hand-written indices, oracle.sdpa); (e) the same for tests/test_gpu_attention_forms.py: (a) on every case of
+FORM_CASES, and two mistakes a kept-query backward can make break a bound on every case with nq = 33."""
 import numpy as np
 import pytest
 import torch
@@ -193,3 +194,39 @@ def test_ref64_without_dropout_is_the_oracle_sdpa(causal):
     for n, t in (("o", o.detach()), ("dq", qd.grad), ("dk", kd.grad), ("dv", vd.grad)):
         assert R.rel_l2(ref[n], t) < 1e-13, n
     assert R.rel_l2(ref["o"], R.ref64(q, k, v, g, torch.ones(B, H, N, N), causal)["o"]) == 0.0
+
+
+# ------------------------------------------------------------------------------------------ (e) the kept-query backward (tests/test_gpu_attention_forms.py)
+KEPT_33 = [c for c in R.FORM_CASES if c[6] == 33 and 33 < c[1] <= 224]      # (N = nq = 33 has no padded query and one stride)
+
+
+@pytest.mark.parametrize("c", R.FORM_CASES, ids=R.form_case_id)
+def test_online_restatement_is_inside_the_bounds_on_every_form_case(c):
+    B, N, H, causal, p, resid, nq = c
+    _check_reference_case(R.form_reference(c), B, N, H, causal, sized=False)      # (short sequences and zero-padded d_o: other floors than the matrix)
+
+
+def test_the_restatement_of_a_kept_case_is_inside_the_bounds():
+    """zero-padded d_o: the online restatement sits inside compare's bounds, and its kept forward rows inside those of the kept rows alone"""
+    assert len(KEPT_33) >= 5
+    for c in (KEPT_33[0], KEPT_33[-1]):
+        B, N, H, causal, p, resid, nq = c
+        r = R.form_reference(c)
+        on = R.restate(*r["in"], None, False, online=True)
+        ratios, bad = R.compare({n: on[n] for n in (*R.OUTS, "lse")}, r["ref"], r["floors"])
+        assert not bad, (R.form_case_id(c), bad)
+        ref_k, rs_k = R.keep_slice(r["ref"], nq), R.keep_slice(r["restate"], nq)
+        ratios, bad = R.compare(R.keep_slice(on, nq), ref_k, R.floors(ref_k, rs_k, ("o",)))
+        assert not bad, (R.form_case_id(c), bad)
+        assert float(r["ref"]["dq"][..., nq:, :].abs().max()) == 0.0        # the reference's own Q rows >= nq are exact zeros
+
+
+@pytest.mark.parametrize("name", list(R.KEEP_MUTANTS))
+def test_compare_rejects_the_planted_mistakes_of_a_kept_backward(name):
+    for c in KEPT_33:
+        r = R.form_reference(c)
+        got = R.keep_mutant_outputs(name, c)
+        _, bad = R.compare({n: got[n] for n in (*R.OUTS, "lse")}, r["ref"], r["floors"])
+        assert bad, (name, R.form_case_id(c))
+        assert any(b.startswith(("dk", "dv")) for b in bad), bad
+        print(f"\nMUTANT {name!r}: {R.form_case_id(c)}: {[b for b in bad if b.startswith('dk: rel_l2')][:1] or bad[:1]}")

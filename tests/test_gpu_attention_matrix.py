@@ -2,14 +2,10 @@
 restatement, worst 32-row tile next to the global rel-L2; tests/test_attention_ref_host.py proves on the CPU that these checks fail for
 ten listed mistakes).
 
-Which kernels a case reaches (csrc/attention.hip, host code at the end of the file; tiles = ceil(N / 32)):
-  forward   N > 512: attn_fwd_long_kernel, 512-key chunks, grid.y = ceil(tiles / 4);  9-16 tiles: attn_fwd_kernel (online softmax);
-            <= 8 tiles: attn_fwd_small_kernel<tiles, DROP, CAUSAL, RES> (register-resident score row) - except 5-8 tiles without dropout and
-            without causal, which take the eight-wave attn_fwd_small8_kernel.  So DROPOUT with 5-8 tiles non-causal LEAVES the 8-wave
-            forward for the 4-wave one.
-  backward  N > 512: attn_bwd_dq_long_kernel + attn_bwd_dkv_long_kernel;  otherwise the plain loops attn_bwd_dq_kernel + attn_bwd_dkv_kernel
-            <DROP, CAUSAL> - except 2-7 tiles without dropout and without causal, which take the software-pipelined *_pipe_kernel forms.  So
-            DROPOUT with 2-7 tiles LEAVES the pipelined backward for the plain loops.
+Which kernels a case reaches is not restated here: vitamd_attention_form (include/vitamd.h, VITAMD_ATTN_*) answers with the function the
+launchers switch on, test_attention_matrix asserts of each case the family _attention_ref.MATRIX_FAMILIES lists for it (dropout with 5-8
+tiles leaves the eight-wave forward for the four-wave one, dropout or causal with 2-7 tiles the pipelined backward for the plain loops),
+and tests/test_gpu_attention_forms.py runs every instantiation.
 Every dropout case uses a seed with bit 40 set, so the high seed word takes part."""
 import pytest
 import torch
@@ -48,7 +44,10 @@ def _hold_to_bounds(got, r, N, record_property):
 # ------------------------------------------------------------------------------------------ 3.1 numeric matrix
 @pytest.mark.parametrize("c", R.MATRIX, ids=R.case_id)
 def test_attention_matrix(hip, c, record_property):
+    from vitamd import ops
     B, N, H, causal, p = c
+    fwd, bwd = R.MATRIX_FAMILIES[R.MATRIX.index(c)]
+    assert ops.attention_form(N, causal, p) & 0xf == fwd and ops.attention_form(N, causal, p, backward=True) & 0xf == bwd
     qkv, d_o = R.matrix_inputs(c)
     r = R.matrix_reference(c)
     drop = (p, R.SEED)

@@ -65,7 +65,7 @@ class _HostCalls:
         self.saved = {}
         for name in lib.SIGNATURES:
             fn = getattr(self.lib, name)
-            if name.endswith("_bytes") or name in ("vitamd_abi_version", "vitamd_gemm_nt_plan", "vitamd_attention_keep_forms"):
+            if name.endswith("_bytes") or name in ("vitamd_abi_version", "vitamd_gemm_nt_plan", "vitamd_attention_keep_forms", "vitamd_attention_form"):
                 continue
             self.saved[name] = fn
 

@@ -49,7 +49,7 @@ class _HostCalls:
         from vitamd import lib
         self.saved = {}
         for name in lib.SIGNATURES:
-            if name.endswith("_bytes") or name in ("vitamd_abi_version", "vitamd_init", "vitamd_gemm_nt_plan", "vitamd_attention_keep_forms"):
+            if name.endswith("_bytes") or name in ("vitamd_abi_version", "vitamd_init", "vitamd_gemm_nt_plan", "vitamd_attention_keep_forms", "vitamd_attention_form"):
                 continue
             fn = getattr(self.lib, name)
             self.saved[name] = fn

@@ -1216,42 +1216,162 @@ int launch_bwd_pipe(const AttnArgs& a, hipStream_t stream) {
   }
 }
 
+// ------------------------------------------------------------------------------------------ the form a call takes
+// THE dispatch rule: which kernel family a call launches and the template arguments it is instantiated with.  Every entry point below
+// launches what this function answers (launch_fwd / launch_bwd switch on it) and vitamd_attention_form returns the same answer as a code,
+// so the query cannot disagree with the launcher.  A template argument a family does not have stays 0 / false (attn_fwd_kernel and the
+// long kernels read causal at run time), so two calls have equal forms exactly when they launch the same instantiations.
+// (the numbers are part of the C ABI: include/vitamd.h VITAMD_ATTN_*, held equal by tests/test_attention_forms_host.py)
+enum AttnFamily { ATTN_FWD_SMALL = 1, ATTN_FWD_SMALL8 = 2, ATTN_FWD_LOOP = 3, ATTN_FWD_LONG = 4, ATTN_BWD_PIPE = 5, ATTN_BWD_LOOP = 6, ATTN_BWD_LONG = 7 };
+enum AttnFlag { ATTN_DROP = 0x1000, ATTN_CAUSAL = 0x2000, ATTN_RES = 0x4000, ATTN_KEEP = 0x8000 };
+struct AttnForm {
+  int family = 0;            // AttnFamily
+  int nt = 0, nqt = 0;       // key tiles / query tiles of the instantiation; 0 where the family is not templated on them
+  bool drop = false, causal = false, res = false, keep = false;      // DROP, CAUSAL, RES, KEEP (forward) or LIM (backward)
+  int code() const {
+    return family | nt << 4 | nqt << 8 | (drop ? ATTN_DROP : 0) | (causal ? ATTN_CAUSAL : 0) | (res ? ATTN_RES : 0) |
+           (keep ? ATTN_KEEP : 0);
+  }
+};
+
+// Only shapes are refused here (VITAMD_ERR_SHAPE), and the use of a kept-query form with a mask or the residual epilogue
+// (VITAMD_ERR_ARG); the probability itself is make_args' to judge.  res: the forward's residual epilogue (the backward has none: ignored).
+// nq = 0: the ordinary entry points; nq > 0: the kept-query ones.
+int attention_form(AttnForm& out, int N, bool causal, bool drop, bool res, int nq, bool bwd) {
+  if (N <= 0 || N > MAX_N_LONG || nq < 0 || nq > N) return VITAMD_ERR_SHAPE;
+  if (!bwd && res && N > 256) return VITAMD_ERR_SHAPE;   // the residual epilogue lives in the register-resident-softmax kernels only
+  const int nkt = (N + 31) / 32;
+  AttnForm f;
+  if (nq > 0) {                                           // kept-query forms: non-causal, no dropout, no residual epilogue
+    f.keep = true;
+    if (!bwd) {                                           // the eight-wave kernel: 129 <= N <= 256
+      if (nkt < 5 || nkt > 8) return VITAMD_ERR_SHAPE;
+      f.family = ATTN_FWD_SMALL8;
+      f.nt = nkt;
+    } else {                                              // the pipelined kernels: 33 <= N <= 224; up to 4 query tiles are instantiated
+      if (nkt < 2 || nkt > 7 || nq > 128) return VITAMD_ERR_SHAPE;
+      f.family = ATTN_BWD_PIPE;
+      f.nt = nkt;
+      f.nqt = (nq + 31) / 32;
+    }
+    if (causal || drop || res) return VITAMD_ERR_ARG;
+  } else if (!bwd) {
+    if (N > MAX_N) {
+      f.family = ATTN_FWD_LONG;
+      f.drop = drop;
+    } else if (nkt >= 5 && nkt <= 8 && !drop && !causal) {   // eight waves, one query block each
+      f.family = ATTN_FWD_SMALL8;
+      f.nt = nkt;
+      f.res = res;
+    } else if (nkt <= 8) {                                // causal / not: compile-time (fewer scalar registers: no runtime mask branches per tile)
+      f.family = ATTN_FWD_SMALL;
+      f.nt = nkt;
+      f.drop = drop;
+      f.causal = causal;
+      f.res = res;
+    } else {
+      f.family = ATTN_FWD_LOOP;
+      f.drop = drop;
+    }
+  } else {
+    if (N > MAX_N) {
+      f.family = ATTN_BWD_LONG;
+      f.drop = drop;
+    } else if (!drop && !causal && nkt >= 2 && nkt <= 7) {   // the ViT shapes: pipelined forms.  (Round 4, DESIGN.md section 8: with 8 / 9 key tiles - 256 tokens: ViT-VQGAN, 288: TiTok - the fully unrolled kernels LOSE to the plain loops, 604 against 402 us at B 256, N 256, H 12 and 597 against 440 at N 288; 2-7 tiles: equal to 13 % faster)
+      f.family = ATTN_BWD_PIPE;
+      f.nt = f.nqt = nkt;
+    } else {
+      f.family = ATTN_BWD_LOOP;
+      f.drop = drop;
+      f.causal = causal;
+    }
+  }
+  out = f;
+  return VITAMD_OK;
+}
+
+int launch_fwd(const AttnForm& f, const AttnArgs& a, hipStream_t stream) {
+  const int nkt = (a.N + 31) / 32, npad = nkt * 32;
+  const dim3 heads(a.B * a.H);
+  switch (f.family) {
+    case ATTN_FWD_LONG:
+      return with_flag(f.drop, [&](auto DR) {
+        return launch<attn_fwd_long_kernel<CONST_OF(DR)>>(dim3(a.B * a.H, (nkt + 3) / 4), dim3(256), 2 * CH * 128, stream, a);
+      });
+    case ATTN_FWD_SMALL8:
+      return with_tiles<5, 8>(f.nt, [&](auto K) {
+        if (f.keep) return launch<attn_fwd_small8_kernel<CONST_OF(K), false, true>>(heads, dim3(512), 2 * npad * 128 + 8 * 2048, stream, a);
+        return with_flag(f.res, [&](auto RES) {
+          return launch<attn_fwd_small8_kernel<CONST_OF(K), CONST_OF(RES)>>(heads, dim3(512), 2 * npad * 128 + 8 * 2048, stream, a);
+        });
+      });
+    case ATTN_FWD_SMALL:
+      return with_tiles<1, 8>(f.nt, [&](auto K) {
+        return with_flag(f.drop, [&](auto DR) {
+          return with_flag(f.causal, [&](auto CAUSAL) {
+            return with_flag(f.res, [&](auto RES) {
+              return launch<attn_fwd_small_kernel<CONST_OF(K), CONST_OF(DR), CONST_OF(CAUSAL), CONST_OF(RES)>>(heads, dim3(256), 2 * npad * 128 + 4 * 4096,
+                                                                                                           stream, a);
+            });
+          });
+        });
+      });
+    case ATTN_FWD_LOOP:
+      return with_flag(f.drop, [&](auto DR) { return launch<attn_fwd_kernel<CONST_OF(DR)>>(heads, dim3(256), 2 * npad * 128, stream, a); });
+  }
+  return VITAMD_ERR_SHAPE;
+}
+
+int launch_bwd(const AttnForm& f, const AttnArgs& a, hipStream_t stream) {
+  const int nkt = (a.N + 31) / 32, npad = nkt * 32;
+  const dim3 block(256);
+  switch (f.family) {
+    case ATTN_BWD_LONG:
+      return with_flag(f.drop, [&](auto DR) {
+        const dim3 grid(a.B * a.H, (nkt + 3) / 4);
+        if (int el = launch<attn_bwd_dq_long_kernel<CONST_OF(DR)>>(grid, block, 2 * CH * 128 + 4 * 4096, stream, a)) return el;   // also writes delta
+        return launch<attn_bwd_dkv_long_kernel<CONST_OF(DR)>>(grid, block, 2 * CH * 128 + 2 * CH * 4 + 4 * 4096, stream, a);
+      });
+    case ATTN_BWD_PIPE:
+      if (f.keep)
+        return with_tiles<2, 7>(f.nt, [&](auto K) {
+          return with_tiles<1, 4>(f.nqt, [&](auto Q) { return launch_bwd_pipe<CONST_OF(K), CONST_OF(Q), true>(a, stream); });
+        });
+      return with_tiles<2, 7>(f.nt, [&](auto K) { return launch_bwd_pipe<CONST_OF(K), CONST_OF(K), false>(a, stream); });
+    case ATTN_BWD_LOOP:
+      return with_flag(f.drop, [&](auto DR) {
+        return with_flag(f.causal, [&](auto CAUSAL) {
+          const dim3 grid(a.B * a.H);
+          if (int el = launch<attn_bwd_dq_kernel<CONST_OF(DR), CONST_OF(CAUSAL)>>(grid, block, 2 * npad * 128 + 4 * 4096, stream, a)) return el;   // also writes delta
+          return launch<attn_bwd_dkv_kernel<CONST_OF(DR), CONST_OF(CAUSAL)>>(grid, block, 2 * npad * 128 + 2 * npad * 4 + 4 * 4096, stream, a);
+        });
+      });
+  }
+  return VITAMD_ERR_SHAPE;
+}
+
 int attention_fwd_impl(const void* qkv, void* o, float* lse2, const float* resid_in, float* resid_out, int B, int N, int H, int head_dim, int causal,
                        float dropout_p, unsigned long long seed, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   AttnArgs a;
   if (int e = make_args(a, false, qkv, o, lse2, nullptr, nullptr, nullptr, nullptr, B, N, H, head_dim, causal, dropout_p, seed)) return e;
   a.resid_in = resid_in;
   a.resid_out = resid_out;
-  const bool drop = a.drop_thresh != 0u, res = resid_in != nullptr;
-  const int nkt = (N + 31) / 32, npad = nkt * 32;
-  const dim3 heads(B * H);
-  int e;
-  if (N > MAX_N)
-    e = with_flag(drop, [&](auto DR) { return launch<attn_fwd_long_kernel<CONST_OF(DR)>>(dim3(B * H, (nkt + 3) / 4), dim3(256), 2 * CH * 128, stream, a); });
-  else if (nkt >= 5 && nkt <= 8 && !drop && !causal)      // eight waves, one query block each
-    e = with_tiles<5, 8>(nkt, [&](auto K) {
-      return with_flag(res, [&](auto RES) {
-        return launch<attn_fwd_small8_kernel<CONST_OF(K), CONST_OF(RES)>>(heads, dim3(512), 2 * npad * 128 + 8 * 2048, stream, a);
-      });
-    });
-  else if (nkt <= 8)                                      // causal / not: compile-time (fewer scalar registers: no runtime mask branches per tile)
-    e = with_tiles<1, 8>(nkt, [&](auto K) {
-      return with_flag(drop, [&](auto DR) {
-        return with_flag(causal != 0, [&](auto CAUSAL) {
-          return with_flag(res, [&](auto RES) {
-            return launch<attn_fwd_small_kernel<CONST_OF(K), CONST_OF(DR), CONST_OF(CAUSAL), CONST_OF(RES)>>(heads, dim3(256), 2 * npad * 128 + 4 * 4096,
-                                                                                                         stream, a);
-          });
-        });
-      });
-    });
-  else
-    e = with_flag(drop, [&](auto DR) { return launch<attn_fwd_kernel<CONST_OF(DR)>>(heads, dim3(256), 2 * npad * 128, stream, a); });
-  return launched(e);
+  AttnForm f;
+  if (int e = attention_form(f, N, causal != 0, a.drop_thresh != 0u, resid_in != nullptr, 0, false)) return e;
+  return launched(launch_fwd(f, a, (hipStream_t)stream_));
 }
 
 }  // namespace
+
+// Which kernels a call would launch (nothing is launched, no pointer is needed): AttnForm::code(), or -VITAMD_ERR_* where the matching
+// entry point refuses - the shape first, then the probability, as make_args orders them.
+extern "C" int vitamd_attention_form(int N, int causal, float dropout_p, int resid, int nq, int backward) {
+  AttnForm f;
+  const DropoutParams d = dropout_params(dropout_p, 0ull);
+  if (int e = attention_form(f, N, causal != 0, d.ok ? d.thresh != 0u : dropout_p != 0.f, resid != 0, nq, backward != 0)) return -e;
+  if (!d.ok) return -VITAMD_ERR_ARG;
+  return f.code();
+}
 
 extern "C" int vitamd_attention_fwd(const void* qkv, void* o, float* lse2, int B, int N, int H, int head_dim, int causal,
                                     float dropout_p, unsigned long long seed, void* stream_) {
@@ -1262,37 +1382,19 @@ extern "C" int vitamd_attention_fwd(const void* qkv, void* o, float* lse2, int B
 extern "C" int vitamd_attention_fwd_resid(const void* qkv, void* o, float* lse2, const float* resid_in, float* resid_out, int B, int N,
                                           int H, int head_dim, int causal, float dropout_p, unsigned long long seed, void* stream_) {
   if (!resid_in || !resid_out) return VITAMD_ERR_ARG;
-  if (N > 256) return VITAMD_ERR_SHAPE;
+  AttnForm f;
+  if (int e = attention_form(f, N, false, false, true, 0, false)) return e;      // N <= 256: answered before make_args' pointers and probability
   return attention_fwd_impl(qkv, o, lse2, resid_in, resid_out, B, N, H, head_dim, causal, dropout_p, seed, stream_);
 }
 
 extern "C" int vitamd_attention_bwd(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta,
                                     float* dbias, int B, int N, int H, int head_dim, int causal, float dropout_p,
                                     unsigned long long seed, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   AttnArgs a;
   if (int e = make_args(a, true, qkv, o, lse2, d_o, dqkv, delta, dbias, B, N, H, head_dim, causal, dropout_p, seed)) return e;
-  const bool drop = a.drop_thresh != 0u;
-  const int nkt = (N + 31) / 32, npad = nkt * 32;
-  const dim3 block(256);
-  int e;
-  if (N > MAX_N)
-    e = with_flag(drop, [&](auto DR) {
-      const dim3 grid(B * H, (nkt + 3) / 4);
-      if (int el = launch<attn_bwd_dq_long_kernel<CONST_OF(DR)>>(grid, block, 2 * CH * 128 + 4 * 4096, stream, a)) return el;   // also writes delta
-      return launch<attn_bwd_dkv_long_kernel<CONST_OF(DR)>>(grid, block, 2 * CH * 128 + 2 * CH * 4 + 4 * 4096, stream, a);
-    });
-  else if (!drop && !causal && nkt >= 2 && nkt <= 7)      // the ViT shapes: pipelined forms.  (Round 4, DESIGN.md section 8: with 8 / 9 key tiles - 256 tokens: ViT-VQGAN, 288: TiTok - the fully unrolled kernels LOSE to the plain loops, 604 against 402 us at B 256, N 256, H 12 and 597 against 440 at N 288; 2-7 tiles: equal to 13 % faster)
-    e = with_tiles<2, 7>(nkt, [&](auto K) { return launch_bwd_pipe<CONST_OF(K), CONST_OF(K), false>(a, stream); });
-  else
-    e = with_flag(drop, [&](auto DR) {
-      return with_flag(causal != 0, [&](auto CAUSAL) {
-        const dim3 grid(B * H);
-        if (int el = launch<attn_bwd_dq_kernel<CONST_OF(DR), CONST_OF(CAUSAL)>>(grid, block, 2 * npad * 128 + 4 * 4096, stream, a)) return el;   // also writes delta
-        return launch<attn_bwd_dkv_kernel<CONST_OF(DR), CONST_OF(CAUSAL)>>(grid, block, 2 * npad * 128 + 2 * npad * 4 + 4 * 4096, stream, a);
-      });
-    });
-  return launched(e);
+  AttnForm f;
+  if (int e = attention_form(f, N, causal != 0, a.drop_thresh != 0u, false, 0, true)) return e;
+  return launched(launch_bwd(f, a, (hipStream_t)stream_));
 }
 
 // ------------------------------------------------------------------------------------------ kept-query forms
@@ -1302,29 +1404,27 @@ extern "C" int vitamd_attention_bwd(const void* qkv, const void* o, const float*
 // needs the eight-wave kernel (129 <= N <= 256), the backward the pipelined kernels (33 <= N <= 224) and nq <= 128;
 // vitamd_attention_keep_forms tells.
 extern "C" int vitamd_attention_keep_forms(int N, int nq) {
-  if (N <= 0 || nq <= 0 || nq > N) return 0;
-  const int nkt = (N + 31) / 32;
-  return (nkt >= 5 && nkt <= 8 ? 1 : 0) | (nkt >= 2 && nkt <= 7 && nq <= 128 ? 2 : 0);     // up to 4 query tiles are instantiated
+  if (nq <= 0) return 0;                                  // (nq = 0 names the ordinary forms in attention_form)
+  AttnForm f;
+  return (attention_form(f, N, false, false, false, nq, false) == VITAMD_OK ? 1 : 0) |
+         (attention_form(f, N, false, false, false, nq, true) == VITAMD_OK ? 2 : 0);
 }
 
 extern "C" int vitamd_attention_fwd_keep(const void* qkv, void* o, float* lse2, int B, int N, int H, int head_dim, int nq, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   AttnArgs a;
   if (int e = make_args(a, false, qkv, o, lse2, nullptr, nullptr, nullptr, nullptr, B, N, H, head_dim, 0, 0.f, 0ull, nq)) return e;
-  if (!(vitamd_attention_keep_forms(N, nq) & 1)) return VITAMD_ERR_SHAPE;
-  const int nkt = (N + 31) / 32;
-  return launched(with_tiles<5, 8>(nkt, [&](auto K) {
-    return launch<attn_fwd_small8_kernel<CONST_OF(K), false, true>>(dim3(B * H), dim3(512), 2 * nkt * 32 * 128 + 8 * 2048, stream, a);
-  }));
+  AttnForm f;
+  if (nq <= 0) return VITAMD_ERR_SHAPE;
+  if (int e = attention_form(f, N, false, false, false, nq, false)) return e;
+  return launched(launch_fwd(f, a, (hipStream_t)stream_));
 }
 
 extern "C" int vitamd_attention_bwd_keep(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta,
                                          float* dbias, int B, int N, int H, int head_dim, int nq, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   AttnArgs a;
   if (int e = make_args(a, true, qkv, o, lse2, d_o, dqkv, delta, dbias, B, N, H, head_dim, 0, 0.f, 0ull, nq)) return e;
-  if (!(vitamd_attention_keep_forms(N, nq) & 2)) return VITAMD_ERR_SHAPE;
-  return launched(with_tiles<2, 7>((N + 31) / 32, [&](auto K) {
-    return with_tiles<1, 4>((nq + 31) / 32, [&](auto Q) { return launch_bwd_pipe<CONST_OF(K), CONST_OF(Q), true>(a, stream); });
-  }));
+  AttnForm f;
+  if (nq <= 0) return VITAMD_ERR_SHAPE;
+  if (int e = attention_form(f, N, false, false, false, nq, true)) return e;
+  return launched(launch_bwd(f, a, (hipStream_t)stream_));
 }

@@ -74,6 +74,7 @@ SIGNATURES = {
     "vitamd_attention_keep_forms": [_I, _I],
     "vitamd_attention_fwd_keep": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_attention_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vitamd_attention_form": [_I, _I, _F, _I, _I, _I],
     "vitamd_cross_entropy_grid_rows": [_I],
     "vitamd_cross_entropy_fwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _LL, _P],
     "vitamd_cross_entropy_bwd": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _P],

@@ -362,6 +362,27 @@ def attention_bwd(qkv, o, lse, d_o, B, N, H, causal=False, dbias=None, dropout=(
     return dqkv
 
 
+# include/vitamd.h VITAMD_ATTN_* (vitamd_attention_form): family | key tiles << 4 | query tiles << 8 | flags
+ATTN_FWD_SMALL, ATTN_FWD_SMALL8, ATTN_FWD_LOOP, ATTN_FWD_LONG, ATTN_BWD_PIPE, ATTN_BWD_LOOP, ATTN_BWD_LONG = 1, 2, 3, 4, 5, 6, 7
+ATTN_DROP, ATTN_CAUSAL, ATTN_RES, ATTN_KEEP = 0x1000, 0x2000, 0x4000, 0x8000
+
+
+def attention_form(N, causal=False, dropout_p=0.0, resid=False, nq=0, backward=False):
+    """The kernels attention_fwd (resid=: its residual form) / attention_bwd (backward=True) would launch at this length, or with nq > 0
+    attention_fwd_keep / attention_bwd_keep: the code of include/vitamd.h (family, tile counts and flags of the instantiation; equal codes
+    = the same machine code).  Nothing is launched.  A call the entry point would refuse raises VitamdError."""
+    code = int(_L().vitamd_attention_form(int(N), int(causal), float(dropout_p), int(bool(resid)), int(nq), int(backward)))
+    if code < 0:
+        raise _lib.VitamdError(f"attention_form[N={N},causal={int(causal)},p={dropout_p},resid={int(bool(resid))},nq={nq},backward={int(backward)}]: "
+                               f"{_lib.ERRORS.get(-code, code)}")
+    return code
+
+
+def attention_form_fields(code):
+    """code -> (family, key tiles, query tiles, flags)"""
+    return code & 0xf, code >> 4 & 0xf, code >> 8 & 0xf, code & 0xf000
+
+
 KEEP_FWD, KEEP_BWD = 1, 2          # include/vitamd.h vitamd_attention_keep_forms
 
 
@@ -383,9 +404,10 @@ def attention_fwd_keep(qkv, B, N, H, nq):
     return o, lse
 
 
-def attention_bwd_keep(qkv, o, lse, d_o, B, N, H, nq, dbias=None):
+def attention_bwd_keep(qkv, o, lse, d_o, B, N, H, nq, dbias=None, delta=None):
     """Kept-query backward: o, d_o bf16 COMPACT [B*nq, H*64]; lse fp32 [B, H, N] (entries [..., :nq] read) -> dense dqkv bf16 [B*N, 3*H*64]
-    whose Q rows >= nq are zeros; equal to attention_bwd given d_o zero-padded to N rows.  dbias as in attention_bwd."""
+    whose Q rows >= nq are zeros; equal to attention_bwd given d_o zero-padded to N rows.  dbias as in attention_bwd.
+    delta: the caller's own scratch fp32 [B, H, N] (entries [..., :nq] are written, the rest left alone); allocated here when None."""
     _need(qkv, BF16, "qkv", 2); _need(o, BF16, "o", 2); _need(d_o, BF16, "d_o", 2); _need(lse, F32, "lse")
     D = H * 64
     if tuple(qkv.shape) != (B * N, 3 * D) or tuple(o.shape) != (B * nq, D) or tuple(d_o.shape) != (B * nq, D) or lse.numel() != B * H * N:
@@ -393,7 +415,12 @@ def attention_bwd_keep(qkv, o, lse, d_o, B, N, H, nq, dbias=None):
     if dbias is not None:
         _need(dbias, F32, "dbias", 1)
     dqkv = torch.empty_like(qkv)
-    delta = torch.empty_like(lse)
+    if delta is None:
+        delta = torch.empty_like(lse)
+    else:
+        _need(delta, F32, "delta")
+        if delta.numel() != B * H * N:
+            raise _lib.VitamdError("attention_bwd_keep: delta must be [B, H, N]")
     _lib.check(_L().vitamd_attention_bwd_keep(_p(qkv), _p(o), _p(lse), _p(d_o), _p(dqkv), _p(delta), _p(dbias), B, N, H, 64, nq, _stream()),
                f"attention_bwd_keep[B={B},N={N},H={H},nq={nq}]")
     return dqkv
