@@ -107,6 +107,17 @@ def test_transformer_layer_b_vs_reference_golden(hip):
         assert abs(float(grads[k].double().norm()) - ref["norm"]) / ref["norm"] < 1e-2, k
 
 
+def classifier_grad_bound(floor, k):
+    """what a parameter gradient of the classifier may be away from the reference golden (tests/test_gpu_poison.py holds the gradients of
+    its poisoned run to the same bound)"""
+    return 2 * floor["grads"][k] + 5e-3
+
+
+def tokenizer_grad_bound(floor, k):
+    """the same for the tokenizer models (this file, test_gpu_tatitok.py, test_gpu_code_titok.py, test_gpu_enhancing.py)"""
+    return 2 * floor["grads"][k] + 1e-2
+
+
 def _run_classifier(g):
     import train_vit as TV
     c = g["cfg"]
@@ -136,8 +147,8 @@ def test_classifier_vs_reference_golden(hip, name):
     worst = 0.0
     for k, ref in g["grads"].items():
         e = _err(grads[k], ref)
-        worst = max(worst, e / (2 * floor["grads"][k] + 5e-3))
-        assert e < 2 * floor["grads"][k] + 5e-3, (k, e, floor["grads"][k])
+        worst = max(worst, e / classifier_grad_bound(floor, k))
+        assert e < classifier_grad_bound(floor, k), (k, e, floor["grads"][k])
     for k, ref in g.get("full_grads", {}).items():
         assert O.rel_l2(grads[k], ref) < 2 * floor["grads"][k] + 5e-3, k
 
@@ -282,7 +293,7 @@ def test_tokenizer_vs_reference_golden(hip, name):
             continue
         assert torch.isfinite(p.grad).all(), k
         e = _err(p.grad, ref)
-        if e > 2 * floor["grads"][k] + 1e-2:          # (round 4: tightened from 3 x floor + 2e-2; worst measured 5.2e-2 where the reference's own autocast floor is 3.6e-2)
+        if e > tokenizer_grad_bound(floor, k):          # 2 x floor + 1e-2 (round 4: tightened from 3 x floor + 2e-2; worst measured 5.2e-2 where the reference's own autocast floor is 3.6e-2)
             bad.append((k, round(e, 4), round(floor["grads"][k], 4)))
     assert not bad, bad[:8]
 
