@@ -208,7 +208,9 @@ def check_l1(got, ref, t32, tie, g_img, dtype, label=""):
     return fails
 
 
-L1_SHAPES = [(3, 2, 4, 3), (3, 3, 8, 3), (3, 1, 16, 3)]       # (B, G, p, c) of the kernel cases; patch 2 (a 12-feature row) is a case of its own
+# (B, G, p, c) of the kernel cases; patch 2 (a 12-feature row) is a case of its own.  The last cuts its grid row into strips: 8 + 1 tokens
+# in bf16 (6 KiB each), 4 + 4 + 1 in fp32
+L1_SHAPES = [(3, 2, 4, 3), (3, 3, 8, 3), (3, 1, 16, 3), (1, 9, 32, 3)]
 
 
 # ------------------------------------------------------------------------------------------------ the MLP

@@ -241,9 +241,10 @@ def check_recon_bf16(got_bf16, ref, t32, label=""):
 
 # ------------------------------------------------------------------------------------------------ the cases both test files use
 VQ_SHAPES = [(1, 1, 1), (255, 2, 1), (257, 257, 17), (600, 513, 12), (300, 300, 64)]      # (M, K, d)
-# (B, G, p, c): the last two take the kernel's other paths - 12-KiB fp32 tokens cut a grid row of 5 into strips of 4 + 1; a patch of 2
-# has no four consecutive pixels in one token (the image is then read pixel by pixel)
-RECON_SHAPES = [(2, 1, 4, 3), (1, 2, 16, 3), (2, 16, 16, 3), (1, 3, 8, 1), (1, 5, 32, 3), (1, 3, 2, 2)]
+# (B, G, p, c): the last three take the kernel's other paths - 12-KiB fp32 tokens cut a grid row of 5 into strips of 4 + 1; a patch of 2
+# has no four consecutive pixels in one token (the image is then read pixel by pixel); a grid row of 9 is the shortest that is cut in bf16
+# too (6-KiB tokens: strips of 8 + 1, fp32 4 + 4 + 1)
+RECON_SHAPES = [(2, 1, 4, 3), (1, 2, 16, 3), (2, 16, 16, 3), (1, 3, 8, 1), (1, 5, 32, 3), (1, 3, 2, 2), (1, 9, 32, 3)]
 G_LOSS, G_UP = 2.5, 2.5          # upstream gradients other than 1
 
 

@@ -193,6 +193,42 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// sum of the four waves' values in wave order, returned to thread 0 (red: 4 floats of LDS)
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// The final fixed-order sum of the loss kernels: out[0] = scale * sum(partials[0 .. n)), one workgroup: every thread sums its strided share
+// in fp64, then lanes, then waves.  A template in an unnamed namespace: a translation unit that never launches it emits nothing, and one that
+// does has its own copy.
+namespace {
+template <int SUM_THREADS>
+__global__ __launch_bounds__(SUM_THREADS) void sum_partials_kernel(const float* __restrict__ partials, float* __restrict__ out, long n, double scale) {
+  __shared__ double part[SUM_THREADS / 64];
+  double a = 0.0;
+  for (long i = threadIdx.x; i < n; i += SUM_THREADS) a += (double)partials[i];
+  a = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  a = 0.0;
+  for (int i = 0; i < SUM_THREADS / 64; ++i) a += part[i];
+  out[0] = (float)(a * scale);
+}
+template <int SUM_THREADS = 1024>
+void launch_sum_partials(const float* partials, float* out, long n, double scale, hipStream_t s) {
+  hipLaunchKernelGGL(sum_partials_kernel<SUM_THREADS>, dim3(1), dim3(SUM_THREADS), 0, s, partials, out, n, scale);
+}
+}  // namespace
 
 // linear tile id -> (tile_m, tile_n).  Plain order walks N fastest.  Grouped order (wide N): blocks
 // of GROUP_M row panels x all N tiles, M fastest inside a block, so the ~32 tiles an XCD works on at a

@@ -6,21 +6,16 @@
 // Every element is read and written by the same lane, a piece as a whole before it is stored: both kernels may run in place.
 //
 // The L1 pixel tail: mean |depatchify(tokens) - images| on the tokens as the head GEMM wrote them, in the feature order of
-// nn.ConvTranspose2d(dim, c, kernel = stride = p), (c p1 p2).  The structure is recon_mse_kernel's (csrc/tokenizer.hip): a workgroup owns
-// a strip of whole tokens of one grid row, stages it in LDS in 16-byte pieces and walks the matching image rows; in this feature order
-// the four pixels of a 16-byte image load are four CONSECUTIVE token elements.  The forward also writes the image when asked to; the
-// backward writes g sign(diff) / N + g_image over the staged tokens and the strip back in 16-byte pieces, so it may run in place.
-// Per-thread sums, then lanes, waves, workgroups in a fixed order: no float atomics, the same bits on every call.
-#include <type_traits>
-
+// nn.ConvTranspose2d(dim, c, kernel = stride = p), (c p1 p2).  It is the strip kernel of csrc/recon_strip.h with L1Term below: in this
+// feature order the four pixels of a 16-byte image load are four CONSECUTIVE token elements.  The forward also writes the image when asked
+// to; the backward writes g sign(diff) / N + g_image over the staged tokens, so it may run in place.
 #include "common.h"
+#include "recon_strip.h"
 #include "../../include/vitamd.h"
 
 namespace {
 
 constexpr int TANH_GRID_CAP = 2048;           // workgroups per launch (8 per CU); further pieces are reached by the stride loop
-constexpr int RECON_LDS_BYTES = 48 * 1024;    // the staged strip; three workgroups per CU
-constexpr int SUM_THREADS = 1024;
 
 // tanh in fp32, |error| well inside half a bf16 ulp of the result for every bf16 input:
 //   |x| <  1/16: x (1 - x^2/3 + 2 x^4/15), the series (next term 17 x^6 / 315 < 4e-9 relative); +-0 and tiny values keep sign and value
@@ -87,169 +82,22 @@ int launch_tanh(const void* a, const void* t, void* out, long n, void* stream) {
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
-// out[0] = scale * sum(partials[0 .. n)), one workgroup: every thread sums its strided share in fp64, then lanes, then waves, in a fixed order
-__global__ __launch_bounds__(SUM_THREADS) void l1_sum_partials_kernel(const float* __restrict__ partials, float* __restrict__ out, long n, double scale) {
-  __shared__ double part[SUM_THREADS / 64];
-  double a = 0.0;
-  for (long i = threadIdx.x; i < n; i += SUM_THREADS) a += (double)partials[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  a = 0.0;
-  for (int i = 0; i < SUM_THREADS / 64; ++i) a += part[i];
-  out[0] = (float)(a * scale);
-}
-
-template <bool BF16>
-__device__ __forceinline__ float lds_elem(const char* strip, int i) {
-  if constexpr (BF16) return bf2f(((const __bf16*)strip)[i]);
-  else return ((const float*)strip)[i];
-}
-template <bool BF16>
-__device__ __forceinline__ void lds_store(char* strip, int i, float v) {
-  if constexpr (BF16) ((__bf16*)strip)[i] = f2bf(v);
-  else ((float*)strip)[i] = v;
-}
-
 // one element of the backward: sign(df) * scale + g_image, summed in fp64 and rounded once; sign(0) = 0, so a tie gives g_image itself
 __device__ __forceinline__ float l1_grad(float df, double scale, float gi) {
   const double s = (double)((df > 0.f) - (df < 0.f));
   return (float)(s * scale + (double)gi);
 }
 
-// Strip s of the grid: (b, gh) = s / chunks, tokens gw0 .. gw0 + nt of that grid row.  LDS: the strip, compact ([token][F]), then 4 floats.
-// Image items: VEC_IMG (p % 4 == 0, aligned image buffers): 4 consecutive pixels of one image row = 4 consecutive elements of one token;
-// else single pixels.  Token element of pixel (ch, p1, p2): ch p^2 + p1 p + p2.
-template <bool BF16, bool BWD, bool VEC_IMG>
-__global__ __launch_bounds__(256) void recon_l1_kernel(const void* y, const float* __restrict__ img, const float* __restrict__ g_loss,
-                                                       const float* __restrict__ g_img, void* dy, float* __restrict__ recon,
-                                                       float* __restrict__ partials, int G, int p, int c, int ld, int ldo, int nt_max, int chunks,
-                                                       double inv_e) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ES = BF16 ? 2 : 4;
-  constexpr int W = 16 / ES;                            // elements per 16-byte piece
-  typedef typename std::conditional<BF16, __bf16, float>::type T;
-  const int F = p * p * c;
-  const long strip = blockIdx.x;
-  const long bg = strip / chunks;                       // b * G + gh
-  const int gw0 = (int)(strip - bg * chunks) * nt_max;
-  const int nt = min(nt_max, G - gw0);
-  const long b = bg / G;
-  const int gh = (int)(bg - b * G);
-  const size_t row0 = (size_t)bg * G + gw0;             // first token row of the strip
-  char* strip_lds = smem;
-  float* red = (float*)(smem + (size_t)nt_max * F * ES);   // F * ES is a multiple of 16
-
-  const int ppr = F / W;                                // pieces per token
-  const int npieces = nt * ppr;
-  for (int i = threadIdx.x; i < npieces; i += 256) {
-    const int t = i / ppr, j = i - t * ppr;
-    *(u32x4*)(strip_lds + (size_t)i * 16) = *(const u32x4*)((const T*)y + (row0 + t) * (size_t)ld + (size_t)j * W);
-  }
-  __syncthreads();
-
-  const int Wimg = G * p, pp = p * p;
-  const size_t img_b = (size_t)b * c * Wimg * Wimg;
-  const double scale = BWD ? (double)(g_loss ? *g_loss : 1.f) * inv_e : 0.0;
-  const int run = nt * p;                               // pixels of one image row inside the strip
-  float a = 0.f;
-  if constexpr (VEC_IMG) {
-    const int qpr = run / 4;
-    const int nitems = c * p * qpr;
-    for (int i = threadIdx.x; i < nitems; i += 256) {
-      const int r = i / qpr, xq = (i - r * qpr) * 4;    // r = ch * p + p1
-      const int ch = r / p, p1 = r - ch * p;
-      const int t = xq / p, p2 = xq - t * p;
-      const size_t at = img_b + ((size_t)ch * Wimg + (size_t)gh * p + p1) * Wimg + (size_t)gw0 * p + xq;
-      const f32x4 v = *(const f32x4*)(img + at);
-      const int e0 = t * F + ch * pp + p1 * p + p2;
-      if constexpr (BWD) {
-        f32x4 gi = {0.f, 0.f, 0.f, 0.f};
-        if (g_img) gi = *(const f32x4*)(g_img + at);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lds_store<BF16>(strip_lds, e0 + k, l1_grad(lds_elem<BF16>(strip_lds, e0 + k) - v[k], scale, gi[k]));
-      } else {
-        f32x4 rv;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          rv[k] = lds_elem<BF16>(strip_lds, e0 + k);
-          a += __builtin_fabsf(rv[k] - v[k]);
-        }
-        if (recon) *(f32x4*)(recon + at) = rv;
-      }
-    }
-  } else {
-    const int nitems = c * p * run;
-    for (int i = threadIdx.x; i < nitems; i += 256) {
-      const int r = i / run, xp = i - r * run;
-      const int ch = r / p, p1 = r - ch * p;
-      const int t = xp / p, p2 = xp - t * p;
-      const size_t at = img_b + ((size_t)ch * Wimg + (size_t)gh * p + p1) * Wimg + (size_t)gw0 * p + xp;
-      const int e0 = t * F + ch * pp + p1 * p + p2;
-      const float rv = lds_elem<BF16>(strip_lds, e0);
-      const float df = rv - img[at];
-      if constexpr (BWD) {
-        lds_store<BF16>(strip_lds, e0, l1_grad(df, scale, g_img ? g_img[at] : 0.f));
-      } else {
-        a += __builtin_fabsf(df);
-        if (recon) recon[at] = rv;
-      }
-    }
-  }
-  if constexpr (BWD) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < npieces; i += 256) {
-      const int t = i / ppr, j = i - t * ppr;
-      *(u32x4*)((T*)dy + (row0 + t) * (size_t)ldo + (size_t)j * W) = *(const u32x4*)(strip_lds + (size_t)i * 16);
-    }
-  } else {
-    a = wave_sum(a);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[strip] = (red[0] + red[1]) + (red[2] + red[3]);
-  }
-}
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-struct L1Plan { int nt, chunks; long strips; size_t lds; };
-
-// shape rules shared by the forward and the backward (those of vitamd_recon_mse_*: the workspace is the same size); false = VITAMD_ERR_SHAPE
-inline bool l1_plan(int B, int G, int p, int c, int bf16, L1Plan& pl) {
-  if (B < 1 || G < 1 || p < 1 || c < 1) return false;
-  const long F = (long)p * p * c;
-  const int es = bf16 ? 2 : 4;
-  if (F % (16 / es) != 0 || F * es > RECON_LDS_BYTES) return false;
-  if ((long)G * p > 46340 || (long)B * G * G > 0x7fffffffL) return false;      // image plane and token rows within int
-  pl.nt = (int)(RECON_LDS_BYTES / (F * es));
-  if (pl.nt > G) pl.nt = G;
-  pl.chunks = (G + pl.nt - 1) / pl.nt;
-  pl.strips = (long)B * G * pl.chunks;
-  if (pl.strips > 0x7fffffffL) return false;
-  pl.lds = (size_t)pl.nt * F * es + 16;
-  return true;
-}
-
-template <bool BF16, bool BWD, bool VEC_IMG>
-int launch_l1_form(const L1Plan& pl, const void* y, const float* img, const float* g_loss, const float* g_img, void* dy, float* recon, float* partials,
-                   int G, int p, int c, int ld, int ldo, double inv_e, hipStream_t s) {
-  if (int e = set_lds(recon_l1_kernel<BF16, BWD, VEC_IMG>, (int)pl.lds)) return e;
-  hipLaunchKernelGGL((recon_l1_kernel<BF16, BWD, VEC_IMG>), dim3((unsigned)pl.strips), dim3(256), pl.lds, s, y, img, g_loss, g_img, dy, recon, partials, G,
-                     p, c, ld, ldo, pl.nt, pl.chunks, inv_e);
-  return VITAMD_OK;
-}
-
-template <bool BWD>
-int launch_l1(bool bf16, bool vec_img, const L1Plan& pl, const void* y, const float* img, const float* g_loss, const float* g_img, void* dy, float* recon,
-              float* partials, int G, int p, int c, int ld, int ldo, double inv_e, hipStream_t s) {
-  if (bf16)
-    return vec_img ? launch_l1_form<true, BWD, true>(pl, y, img, g_loss, g_img, dy, recon, partials, G, p, c, ld, ldo, inv_e, s)
-                   : launch_l1_form<true, BWD, false>(pl, y, img, g_loss, g_img, dy, recon, partials, G, p, c, ld, ldo, inv_e, s);
-  return vec_img ? launch_l1_form<false, BWD, true>(pl, y, img, g_loss, g_img, dy, recon, partials, G, p, c, ld, ldo, inv_e, s)
-                 : launch_l1_form<false, BWD, false>(pl, y, img, g_loss, g_img, dy, recon, partials, G, p, c, ld, ldo, inv_e, s);
-}
+// The absolute-error term of recon_strip_kernel; the backward's scale is a double (l1_grad)
+struct L1Term {
+  typedef double Scale;
+  static constexpr bool IMG_GRAD = true, IMG_OUT = true;
+  static __device__ __forceinline__ int elem(int t, int ch, int p1, int p2, int F, int pp, int p, int) { return t * F + ch * pp + p1 * p + p2; }
+  static __device__ __forceinline__ int step(int) { return 1; }
+  static __device__ __forceinline__ double scale(float g, double inv_e) { return (double)g * inv_e; }
+  static __device__ __forceinline__ float fwd(float df) { return __builtin_fabsf(df); }
+  static __device__ __forceinline__ float bwd(float df, double scale, float gi) { return l1_grad(df, scale, gi); }
+};
 
 }  // namespace
 
@@ -261,8 +109,8 @@ extern "C" int vitamd_tanh_bwd_bf16(const void* dh, const void* t, void* dpre, l
 
 extern "C" int vitamd_recon_l1_fwd(const void* y, int y_bf16, const float* img, float* loss, float* recon, float* ws, long ws_bytes, int B, int G,
                                    int p, int c, int ld, void* stream) {
-  L1Plan pl;
-  if (!l1_plan(B, G, p, c, y_bf16, pl)) return VITAMD_ERR_SHAPE;
+  ReconPlan pl;
+  if (!recon_plan(B, G, p, c, y_bf16, pl)) return VITAMD_ERR_SHAPE;
   const int W = y_bf16 ? 8 : 4;
   if (ld < p * p * c || ld % W != 0) return VITAMD_ERR_SHAPE;
   if (!y || !img || !loss || !ws || ws_bytes < pl.strips * (long)sizeof(float)) return VITAMD_ERR_ARG;
@@ -270,15 +118,15 @@ extern "C" int vitamd_recon_l1_fwd(const void* y, int y_bf16, const float* img, 
   hipStream_t s = (hipStream_t)stream;
   const bool vec_img = p % 4 == 0 && aligned16(img) && aligned16(recon);
   const double E = (double)B * c * G * p * G * p;
-  if (int e = launch_l1<false>(y_bf16 != 0, vec_img, pl, y, img, nullptr, nullptr, nullptr, recon, ws, G, p, c, ld, ld, 0.0, s)) return e;
-  hipLaunchKernelGGL(l1_sum_partials_kernel, dim3(1), dim3(SUM_THREADS), 0, s, (const float*)ws, loss, pl.strips, 1.0 / E);
+  if (int e = launch_recon_strip<L1Term>(y_bf16 != 0, false, vec_img, pl, y, img, nullptr, nullptr, nullptr, recon, ws, G, p, c, ld, ld, 0.0, s)) return e;
+  launch_sum_partials(ws, loss, pl.strips, 1.0 / E, s);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
 extern "C" int vitamd_recon_l1_bwd(const void* y, int y_bf16, const float* img, const float* g_loss, const float* g_recon, void* dy, int B, int G,
                                    int p, int c, int ld, int ld_dy, void* stream) {
-  L1Plan pl;
-  if (!l1_plan(B, G, p, c, y_bf16, pl)) return VITAMD_ERR_SHAPE;
+  ReconPlan pl;
+  if (!recon_plan(B, G, p, c, y_bf16, pl)) return VITAMD_ERR_SHAPE;
   const int W = y_bf16 ? 8 : 4;
   if (ld < p * p * c || ld % W != 0 || ld_dy < p * p * c || ld_dy % W != 0) return VITAMD_ERR_SHAPE;
   if (!y || !img || !dy) return VITAMD_ERR_ARG;
@@ -287,6 +135,7 @@ extern "C" int vitamd_recon_l1_bwd(const void* y, int y_bf16, const float* img, 
   hipStream_t s = (hipStream_t)stream;
   const bool vec_img = p % 4 == 0 && aligned16(img) && aligned16(g_recon);
   const double inv_e = 1.0 / ((double)B * c * G * p * G * p);
-  if (int e = launch_l1<true>(y_bf16 != 0, vec_img, pl, y, img, g_loss, g_recon, dy, nullptr, nullptr, G, p, c, ld, ld_dy, inv_e, s)) return e;
+  if (int e = launch_recon_strip<L1Term>(y_bf16 != 0, true, vec_img, pl, y, img, g_loss, g_recon, dy, nullptr, nullptr, G, p, c, ld, ld_dy, inv_e, s))
+    return e;
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }

@@ -2,6 +2,7 @@
 // column sums (bias gradients) and the patch-embed backward reduction.
 #include "common.h"
 #include "vitamd_internal.h"
+#include "vq_scan.h"
 
 namespace {
 
@@ -276,27 +277,17 @@ __global__ __launch_bounds__(256) void vq_nearest_kernel(const float* __restrict
   float xr[DMAX];
 #pragma unroll
   for (int c = 0; c < DMAX; ++c) xr[c] = (m < M && c < d) ? x[(size_t)m * d + c] : 0.f;
-  float best = 3.0e38f;
-  int besti = 0;
+  VqBest best = {3.0e38f, 0};
   for (int k0 = 0; k0 < K; k0 += 256) {
     const int nk = min(256, K - k0);
     __syncthreads();
-    for (int i = threadIdx.x; i < nk * d; i += 256) ce[(i / d) * DMAX + (i % d)] = e[(size_t)k0 * d + i];
-    __syncthreads();
-    for (int k = 0; k < nk; ++k) {
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < DMAX; ++c) {
-        if (c < d) { const float t = xr[c] - ce[k * DMAX + c]; s += t * t; }
-      }
-      if (s < best) { best = s; besti = k0 + k; }
-    }
+    best = vq_scan_chunk<DMAX>(ce, xr, e, k0, nk, d, best);
   }
-  if (m < M) idx[m] = besti;
+  if (m < M) idx[m] = best.index;
 }
 
 // The same search cut over the codebook too (round 4): grid = (row blocks) x (256-code chunks); every thread scans ONE chunk for its row with the
-// arithmetic of vq_nearest_kernel and folds (distance bits << 32 | index) into its row's slot of the index buffer with a 64-bit atomicMin - a
+// loop of vq_nearest_kernel (vq_scan.h) and folds (distance bits << 32 | index) into its row's slot of the index buffer with a 64-bit atomicMin - a
 // non-negative float orders like its bit pattern, so the minimum of the packed words is the smallest distance and, among equal distances, the
 // smallest index: exactly the first-minimum tie-break of the sequential scan, whatever order the chunks arrive in.  vq_unpack_kernel then keeps the low
 // half.  TiTok-S (8 192 tokens x 2 048 codes x 12) ran on 32 workgroups for 1.08 ms with one thread per row; 256 workgroups now.
@@ -309,19 +300,8 @@ __global__ __launch_bounds__(256) void vq_nearest_chunk_kernel(const float* __re
   float xr[DMAX];
 #pragma unroll
   for (int c = 0; c < DMAX; ++c) xr[c] = (m < M && c < d) ? x[(size_t)m * d + c] : 0.f;
-  for (int i = threadIdx.x; i < nk * d; i += 256) ce[(i / d) * DMAX + (i % d)] = e[(size_t)k0 * d + i];
-  __syncthreads();
-  float best = 3.0e38f;
-  int besti = k0;
-  for (int k = 0; k < nk; ++k) {
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < DMAX; ++c) {
-      if (c < d) { const float t = xr[c] - ce[k * DMAX + c]; s += t * t; }
-    }
-    if (s < best) { best = s; besti = k0 + k; }
-  }
-  if (m < M) atomicMin(packed + m, ((unsigned long long)__builtin_bit_cast(unsigned, best) << 32) | (unsigned)besti);
+  const VqBest best = vq_scan_chunk<DMAX>(ce, xr, e, k0, nk, d, VqBest{3.0e38f, k0});
+  if (m < M) atomicMin(packed + m, ((unsigned long long)__builtin_bit_cast(unsigned, best.dist) << 32) | (unsigned)best.index);
 }
 __global__ __launch_bounds__(256) void vq_unpack_kernel(unsigned long long* __restrict__ packed, int M) {
   const int m = blockIdx.x * 256 + threadIdx.x;

@@ -933,45 +933,62 @@ def _need_vq(x, codebook, what):
     return M, K, d
 
 
-def vq_quantize_fwd(x, codebook, return_unit_codes=False):
-    """The cosine-similarity quantiser forward (include/vitamd.h vitamd_vq_quantize_fwd): x fp32 [M, d], codebook fp32 [K, d] ->
-    (unit [M, d], rnorm [M], q [M, d], idx int64 [M], loss fp32 0-dim); return_unit_codes: the unit codebook the search used as a sixth."""
-    M, K, d = _need_vq(x, codebook, "vq_quantize_fwd")
+def _need_g(g_loss, g_recon=None, images=None, name="g_loss"):
+    """the upstream gradients of a loss tail: g_loss a one-element device fp32 or None, g_recon fp32 of the images' shape or None"""
+    if g_loss is not None:
+        _need(g_loss, F32, name)
+        if g_loss.numel() != 1:
+            raise _lib.VitamdError(f"{name}: expected a one-element device fp32")
+    if g_recon is not None:
+        _need(g_recon, F32, "g_recon", 4)
+        if tuple(g_recon.shape) != tuple(images.shape):
+            raise _lib.VitamdError(f"g_recon: expected {tuple(images.shape)}, got {tuple(g_recon.shape)}")
+
+
+def _vq_quantize_fwd(what, x, codebook, return_unit_codes):
+    M, K, d = _need_vq(x, codebook, what)
     dev = x.device
     unit, q = torch.empty((M, d), dtype=F32, device=dev), torch.empty((M, d), dtype=F32, device=dev)
     rnorm = torch.empty((M,), dtype=F32, device=dev)
     idx = torch.empty((M,), dtype=torch.int64, device=dev)
     loss = torch.empty((), dtype=F32, device=dev)
     ws = torch.empty((int(_L().vitamd_vq_quantize_ws_bytes(M, K, d)) // 4,), dtype=F32, device=dev)
-    _lib.check(_L().vitamd_vq_quantize_fwd(_p(x), _p(codebook), _p(unit), _p(rnorm), _p(q), _p(idx), _p(loss), _p(ws), M, K, d, _stream()),
-               f"vq_quantize_fwd[M={M},K={K},d={d}]")
+    _lib.check(getattr(_L(), "vitamd_" + what)(_p(x), _p(codebook), _p(unit), _p(rnorm), _p(q), _p(idx), _p(loss), _p(ws), M, K, d, _stream()),
+               f"{what}[M={M},K={K},d={d}]")
     return (unit, rnorm, q, idx, loss) + ((ws[:K * d].view(K, d),) if return_unit_codes else ())
 
 
-def vq_quantize_bwd(g_q, g_loss, unit, rnorm, idx, codebook, dcodebook=None):
-    """-> (dx fp32 [M, d], dcodebook fp32 [K, d]).  g_q fp32 [M, d] or None, g_loss device fp32 scalar or None; dcodebook is accumulated
-    into when given (else a zeroed one is made).  Semantics: include/vitamd.h vitamd_vq_quantize_bwd."""
-    M, K, d = _need_vq(unit, codebook, "vq_quantize_bwd")
+def _vq_quantize_bwd(what, g_q, g_loss, unit, rnorm, idx, codebook, dcodebook):
+    M, K, d = _need_vq(unit, codebook, what)
     _need(rnorm, F32, "rnorm", 1); _need(idx, torch.int64, "idx", 1)
     if rnorm.numel() != M or idx.numel() != M:
-        raise _lib.VitamdError(f"vq_quantize_bwd: expected rnorm [{M}] and idx [{M}]")
+        raise _lib.VitamdError(f"{what}: expected rnorm [{M}] and idx [{M}]")
     if g_q is not None:
         _need(g_q, F32, "g_q", 2)
         if tuple(g_q.shape) != (M, d):
             raise _lib.VitamdError(f"g_q: expected [{M}, {d}], got {tuple(g_q.shape)}")
-    if g_loss is not None:
-        _need(g_loss, F32, "g_loss")
-        if g_loss.numel() != 1:
-            raise _lib.VitamdError("g_loss: expected a one-element device fp32")
+    _need_g(g_loss)
     if dcodebook is None:
         dcodebook = torch.zeros((K, d), dtype=F32, device=unit.device)
     _need(dcodebook, F32, "dcodebook", 2)
     if tuple(dcodebook.shape) != (K, d):
         raise _lib.VitamdError(f"dcodebook: expected [{K}, {d}], got {tuple(dcodebook.shape)}")
     dx = torch.empty((M, d), dtype=F32, device=unit.device)
-    _lib.check(_L().vitamd_vq_quantize_bwd(_p(g_q), _p(g_loss), _p(unit), _p(rnorm), _p(idx), _p(codebook), _p(dx), _p(dcodebook), M, K, d,
-                                           _stream()), f"vq_quantize_bwd[M={M},K={K},d={d}]")
+    _lib.check(getattr(_L(), "vitamd_" + what)(_p(g_q), _p(g_loss), _p(unit), _p(rnorm), _p(idx), _p(codebook), _p(dx), _p(dcodebook), M, K, d,
+                                               _stream()), f"{what}[M={M},K={K},d={d}]")
     return dx, dcodebook
+
+
+def vq_quantize_fwd(x, codebook, return_unit_codes=False):
+    """The cosine-similarity quantiser forward (include/vitamd.h vitamd_vq_quantize_fwd): x fp32 [M, d], codebook fp32 [K, d] ->
+    (unit [M, d], rnorm [M], q [M, d], idx int64 [M], loss fp32 0-dim); return_unit_codes: the unit codebook the search used as a sixth."""
+    return _vq_quantize_fwd("vq_quantize_fwd", x, codebook, return_unit_codes)
+
+
+def vq_quantize_bwd(g_q, g_loss, unit, rnorm, idx, codebook, dcodebook=None):
+    """-> (dx fp32 [M, d], dcodebook fp32 [K, d]).  g_q fp32 [M, d] or None, g_loss device fp32 scalar or None; dcodebook is accumulated
+    into when given (else a zeroed one is made).  Semantics: include/vitamd.h vitamd_vq_quantize_bwd."""
+    return _vq_quantize_bwd("vq_quantize_bwd", g_q, g_loss, unit, rnorm, idx, codebook, dcodebook)
 
 
 def recon_mse_applies(tokens, F=None):
@@ -1014,19 +1031,22 @@ def recon_mse_fwd(tokens, images, grid, patch):
     return loss
 
 
-def recon_mse_bwd(tokens, images, grid, patch, grad_out=None, out=None):
-    """d loss / d tokens = 2 (tokens - pixel_unshuffle(images)) * grad_out / images.numel(), in the tokens' layout and dtype.  grad_out:
-    device fp32 scalar (None = 1).  out: where to write (`tokens` itself = in place); None allocates a dense tensor."""
-    B, c, ld, is_bf16 = _need_recon(tokens, images, grid, patch, "recon_mse_bwd")
-    if grad_out is not None:
-        _need(grad_out, F32, "grad_out")
-        if grad_out.numel() != 1:
-            raise _lib.VitamdError("grad_out: expected a one-element device fp32")
+def _need_tail_out(out, tokens, what):
+    """where a tail's backward writes the token gradient: a device tensor of the tokens' shape and dtype; None allocates a dense one"""
     if out is None:
         out = torch.empty(tuple(tokens.shape), dtype=tokens.dtype, device=tokens.device)
     if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != tokens.dtype or tuple(out.shape) != tuple(tokens.shape)
             or out.stride(1) != 1 or out.stride(0) < out.shape[1]):
-        raise _lib.VitamdError("recon_mse_bwd: out must be a device tensor of the tokens' shape and dtype with unit inner stride")
+        raise _lib.VitamdError(f"{what}: out must be a device tensor of the tokens' shape and dtype with unit inner stride")
+    return out
+
+
+def recon_mse_bwd(tokens, images, grid, patch, grad_out=None, out=None):
+    """d loss / d tokens = 2 (tokens - pixel_unshuffle(images)) * grad_out / images.numel(), in the tokens' layout and dtype.  grad_out:
+    device fp32 scalar (None = 1).  out: where to write (`tokens` itself = in place); None allocates a dense tensor."""
+    B, c, ld, is_bf16 = _need_recon(tokens, images, grid, patch, "recon_mse_bwd")
+    _need_g(grad_out, name="grad_out")
+    out = _need_tail_out(out, tokens, "recon_mse_bwd")
     _lib.check(_L().vitamd_recon_mse_bwd(_p(tokens), is_bf16, _p(images), _p(grad_out), _p(out), B, grid, patch, c, ld, out.stride(0), _stream()),
                f"recon_mse_bwd[B={B},G={grid},p={patch},c={c},ld={ld}]")
     return out
@@ -1036,42 +1056,13 @@ def recon_mse_bwd(tokens, images, grid, patch, grad_out=None, out=None):
 def vq_quantize_unit_fwd(x, codebook, return_unit_codes=False):
     """vq_quantize_fwd with UNIT codes (include/vitamd.h vitamd_vq_quantize_unit_fwd: blocks.VectorQuantizer(use_l2_norm=True)): q and
     the loss are taken on the normalised code rows.  Same arguments and results."""
-    M, K, d = _need_vq(x, codebook, "vq_quantize_unit_fwd")
-    dev = x.device
-    unit, q = torch.empty((M, d), dtype=F32, device=dev), torch.empty((M, d), dtype=F32, device=dev)
-    rnorm = torch.empty((M,), dtype=F32, device=dev)
-    idx = torch.empty((M,), dtype=torch.int64, device=dev)
-    loss = torch.empty((), dtype=F32, device=dev)
-    ws = torch.empty((int(_L().vitamd_vq_quantize_ws_bytes(M, K, d)) // 4,), dtype=F32, device=dev)
-    _lib.check(_L().vitamd_vq_quantize_unit_fwd(_p(x), _p(codebook), _p(unit), _p(rnorm), _p(q), _p(idx), _p(loss), _p(ws), M, K, d, _stream()),
-               f"vq_quantize_unit_fwd[M={M},K={K},d={d}]")
-    return (unit, rnorm, q, idx, loss) + ((ws[:K * d].view(K, d),) if return_unit_codes else ())
+    return _vq_quantize_fwd("vq_quantize_unit_fwd", x, codebook, return_unit_codes)
 
 
 def vq_quantize_unit_bwd(g_q, g_loss, unit, rnorm, idx, codebook, dcodebook=None):
     """vq_quantize_bwd with UNIT codes: the codebook gradient goes through the normalisation (include/vitamd.h vitamd_vq_quantize_unit_bwd).
     `codebook` is the raw codebook.  -> (dx fp32 [M, d], dcodebook fp32 [K, d])"""
-    M, K, d = _need_vq(unit, codebook, "vq_quantize_unit_bwd")
-    _need(rnorm, F32, "rnorm", 1); _need(idx, torch.int64, "idx", 1)
-    if rnorm.numel() != M or idx.numel() != M:
-        raise _lib.VitamdError(f"vq_quantize_unit_bwd: expected rnorm [{M}] and idx [{M}]")
-    if g_q is not None:
-        _need(g_q, F32, "g_q", 2)
-        if tuple(g_q.shape) != (M, d):
-            raise _lib.VitamdError(f"g_q: expected [{M}, {d}], got {tuple(g_q.shape)}")
-    if g_loss is not None:
-        _need(g_loss, F32, "g_loss")
-        if g_loss.numel() != 1:
-            raise _lib.VitamdError("g_loss: expected a one-element device fp32")
-    if dcodebook is None:
-        dcodebook = torch.zeros((K, d), dtype=F32, device=unit.device)
-    _need(dcodebook, F32, "dcodebook", 2)
-    if tuple(dcodebook.shape) != (K, d):
-        raise _lib.VitamdError(f"dcodebook: expected [{K}, {d}], got {tuple(dcodebook.shape)}")
-    dx = torch.empty((M, d), dtype=F32, device=unit.device)
-    _lib.check(_L().vitamd_vq_quantize_unit_bwd(_p(g_q), _p(g_loss), _p(unit), _p(rnorm), _p(idx), _p(codebook), _p(dx), _p(dcodebook), M, K, d,
-                                                _stream()), f"vq_quantize_unit_bwd[M={M},K={K},d={d}]")
-    return dx, dcodebook
+    return _vq_quantize_bwd("vq_quantize_unit_bwd", g_q, g_loss, unit, rnorm, idx, codebook, dcodebook)
 
 
 def conv_recon_mse_applies(tokens, patch):
@@ -1117,19 +1108,8 @@ def conv_recon_mse_bwd(tokens, w, bias, images, grid, patch, g_loss=None, g_reco
     + g_recon.  g_loss: device fp32 scalar (None = 1); g_recon: fp32 [B, 3, H, W] (None = 0).  out: where dtokens go (never the tokens
     themselves); None allocates a dense tensor.  The same bits on every call."""
     B, ld, is_bf16 = _need_conv_recon(tokens, w, bias, images, grid, patch, "conv_recon_mse_bwd")
-    if g_loss is not None:
-        _need(g_loss, F32, "g_loss")
-        if g_loss.numel() != 1:
-            raise _lib.VitamdError("g_loss: expected a one-element device fp32")
-    if g_recon is not None:
-        _need(g_recon, F32, "g_recon", 4)
-        if tuple(g_recon.shape) != tuple(images.shape):
-            raise _lib.VitamdError(f"g_recon: expected {tuple(images.shape)}, got {tuple(g_recon.shape)}")
-    if out is None:
-        out = torch.empty(tuple(tokens.shape), dtype=tokens.dtype, device=tokens.device)
-    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != tokens.dtype or tuple(out.shape) != tuple(tokens.shape)
-            or out.stride(1) != 1 or out.stride(0) < out.shape[1]):
-        raise _lib.VitamdError("conv_recon_mse_bwd: out must be a device tensor of the tokens' shape and dtype with unit inner stride")
+    _need_g(g_loss, g_recon, images)
+    out = _need_tail_out(out, tokens, "conv_recon_mse_bwd")
     if out.data_ptr() == tokens.data_ptr():
         raise _lib.VitamdError("conv_recon_mse_bwd: the gradient cannot overwrite the tokens (neighbouring tiles re-read them)")
     ws = _conv_recon_ws(B, grid, patch, is_bf16, 1, tokens.device, "conv_recon_mse_bwd")
@@ -1352,17 +1332,6 @@ def tanh_bwd_bf16(dh, t, out=None):
 recon_l1_applies = recon_mse_applies      # the L1 tail takes what the squared-error kernels take: include/vitamd.h vitamd_recon_l1_fwd
 
 
-def _need_g(g_loss, g_recon, images):
-    if g_loss is not None:
-        _need(g_loss, F32, "g_loss")
-        if g_loss.numel() != 1:
-            raise _lib.VitamdError("g_loss: expected a one-element device fp32")
-    if g_recon is not None:
-        _need(g_recon, F32, "g_recon", 4)
-        if tuple(g_recon.shape) != tuple(images.shape):
-            raise _lib.VitamdError(f"g_recon: expected {tuple(images.shape)}, got {tuple(g_recon.shape)}")
-
-
 def recon_l1_fwd(tokens, images, grid, patch, want_recon=False):
     """-> (mean |depatchify(tokens) - images| as a 0-dim device fp32, the depatchified tokens fp32 [B, c, H, W] or None).  tokens fp32 /
     bf16 [B*grid*grid, c*patch*patch] in the feature order (c p1 p2) of nn.ConvTranspose2d's weight (include/vitamd.h vitamd_recon_l1_fwd).
@@ -1384,11 +1353,7 @@ def recon_l1_bwd(tokens, images, grid, patch, g_loss=None, g_recon=None, out=Non
     dense tensor."""
     B, c, ld, is_bf16 = _need_recon(tokens, images, grid, patch, "recon_l1_bwd")
     _need_g(g_loss, g_recon, images)
-    if out is None:
-        out = torch.empty(tuple(tokens.shape), dtype=tokens.dtype, device=tokens.device)
-    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != tokens.dtype or tuple(out.shape) != tuple(tokens.shape)
-            or out.stride(1) != 1 or out.stride(0) < out.shape[1]):
-        raise _lib.VitamdError("recon_l1_bwd: out must be a device tensor of the tokens' shape and dtype with unit inner stride")
+    out = _need_tail_out(out, tokens, "recon_l1_bwd")
     _lib.check(_L().vitamd_recon_l1_bwd(_p(tokens), is_bf16, _p(images), _p(g_loss), _p(g_recon), _p(out), B, grid, patch, c, ld, out.stride(0),
                                         _stream()), f"recon_l1_bwd[B={B},G={grid},p={patch},c={c},ld={ld}]")
     return out

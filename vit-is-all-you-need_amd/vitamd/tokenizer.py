@@ -38,14 +38,17 @@ def vq_quantize_torch(x, codebook_weight):
 
 
 class VQQuantizeFn(torch.autograd.Function):
+    """the quantiser kernels, forward and backward; unit_codes: q and the loss on the normalised code rows, the codebook gradient through
+    the normalisation"""
+
     @staticmethod
-    def forward(ctx, x, codebook):
+    def forward(ctx, x, codebook, unit_codes):
         lead, d = x.shape[:-1], x.shape[-1]
         x2 = x.detach().reshape(-1, d).contiguous()
         cb = codebook.detach().contiguous()
-        unit, rnorm, q, idx, loss = ops.vq_quantize_fwd(x2, cb)
+        unit, rnorm, q, idx, loss = (ops.vq_quantize_unit_fwd if unit_codes else ops.vq_quantize_fwd)(x2, cb)
         ctx.save_for_backward(unit, rnorm, idx, cb)
-        ctx.lead = tuple(lead)
+        ctx.lead, ctx.unit_codes = tuple(lead), unit_codes
         ids = idx.view(lead)
         ctx.mark_non_differentiable(ids)
         return q.view(*lead, d), ids, loss
@@ -55,8 +58,8 @@ class VQQuantizeFn(torch.autograd.Function):
         unit, rnorm, idx, cb = ctx.saved_tensors
         gq = None if g_q is None else g_q.detach().to(F32).reshape(unit.shape).contiguous()
         gl = None if g_loss is None else _scalar(g_loss)
-        dx, dcb = ops.vq_quantize_bwd(gq, gl, unit, rnorm, idx, cb)
-        return dx.view(*ctx.lead, unit.shape[1]), dcb
+        dx, dcb = (ops.vq_quantize_unit_bwd if ctx.unit_codes else ops.vq_quantize_bwd)(gq, gl, unit, rnorm, idx, cb)
+        return dx.view(*ctx.lead, unit.shape[1]), dcb, None
 
 
 def vq_quantize_unit_torch(x, codebook_weight):
@@ -71,30 +74,6 @@ def vq_quantize_unit_torch(x, codebook_weight):
     sq = lambda t: t.pow(2).mean()
     loss = 0.25 * sq(picked.detach() - unit) + sq(picked - unit.detach())
     return unit + (picked - unit).detach(), ids, loss
-
-
-class VQQuantizeUnitFn(torch.autograd.Function):
-    """VQQuantizeFn on the unit-code kernels: q and the loss on the normalised rows, the codebook gradient through the normalisation"""
-
-    @staticmethod
-    def forward(ctx, x, codebook):
-        lead, d = x.shape[:-1], x.shape[-1]
-        x2 = x.detach().reshape(-1, d).contiguous()
-        cb = codebook.detach().contiguous()
-        unit, rnorm, q, idx, loss = ops.vq_quantize_unit_fwd(x2, cb)
-        ctx.save_for_backward(unit, rnorm, idx, cb)
-        ctx.lead = tuple(lead)
-        ids = idx.view(lead)
-        ctx.mark_non_differentiable(ids)
-        return q.view(*lead, d), ids, loss
-
-    @staticmethod
-    def backward(ctx, g_q, _g_ids, g_loss):
-        unit, rnorm, idx, cb = ctx.saved_tensors
-        gq = None if g_q is None else g_q.detach().to(F32).reshape(unit.shape).contiguous()
-        gl = None if g_loss is None else _scalar(g_loss)
-        dx, dcb = ops.vq_quantize_unit_bwd(gq, gl, unit, rnorm, idx, cb)
-        return dx.view(*ctx.lead, unit.shape[1]), dcb
 
 
 def vq_quantize(x, codebook_weight, unit_codes=False):
@@ -112,7 +91,7 @@ def vq_quantize(x, codebook_weight, unit_codes=False):
         raise ops._lib.VitamdError("vq_quantize: expected ROCm device tensors (the HIP kernels are the only implementation)")
     if x.shape[-1] > ops.VQ_MAX_D:
         return vq_quantize_unit_torch(x, codebook_weight) if unit_codes else vq_quantize_torch(x, codebook_weight)
-    return VQQuantizeUnitFn.apply(x, codebook_weight) if unit_codes else VQQuantizeFn.apply(x, codebook_weight)
+    return VQQuantizeFn.apply(x, codebook_weight, bool(unit_codes))
 
 
 # ------------------------------------------------------------------------------------------------ reconstruction loss
