@@ -329,6 +329,30 @@ int vitamd_cross_entropy_grid_rows(int V);
 int vitamd_cross_entropy_bwd(const void* logits, int logits_bf16, const long long* target, const float* lse, const float* stats,
                              const float* grad_out, void* dlogits, int dlogits_bf16, int M, int V, int ld, int ldo,
                              long long ignore_index, void* stream);
+/* Soft-target cross-entropy: the loss of Mixup / CutMix and label smoothing, timm's SoftTargetCrossEntropy on
+ * the target t[m, v] = (1-e) (l [v == ya] + (1-l) [v == yb]) + e / V, with ya = target_a[m], yb = target_b[m], l = lam[m] and
+ * e = smoothing, without the [M, V] target ever existing:
+ *   loss_row[m] = lse[m] - ( (1-e) (l x[m, ya] + (1-l) x[m, yb]) + (e / V) sum_v x[m, v] )
+ *   stats = {sum_m loss_row[m] / M, 1 / M}: the mean is over ALL M rows, there is no ignore_index.
+ * lam fp32 [M] on the device, NULL: l = 1 and target_b is not looked at (it may be NULL); with lam, target_b is required
+ * (VITAMD_ERR_ARG).  ya == yb adds the two weights.  A target term whose weight l or 1-l is zero is not formed (its logit may be -inf).
+ * e == 0 forms no sum_v term, so -inf logits stay legal as in vitamd_cross_entropy_fwd; with e > 0 every logit must be finite (the
+ * caller's contract: inf or NaN comes out, never a fault).  sum_v x is carried by the single pass over the row that keeps the running
+ * maximum and sum, lanes and waves are merged in the same fixed order, the mean is taken by the same single-workgroup launch: no
+ * float atomics, the same bits on every call.  A target outside [0, V) (ya always, yb when lam is given): nothing is read for it, its
+ * loss_row is NaN (so is the mean), its gradient row is zeros.  With smoothing == 0 and lam == NULL every output has the bits
+ * vitamd_cross_entropy_fwd gives when no row is ignored (the same row walk).  logits, ld, the 16-byte rule and the shape refusals as
+ * vitamd_cross_entropy_fwd; smoothing outside [0, 1] (or NaN) or a missing pointer: VITAMD_ERR_ARG (after the shape check).
+ * replaces timm's Mixup target + SoftTargetCrossEntropy / LabelSmoothingCrossEntropy of the DeiT recipe (the reference trains without). */
+int vitamd_soft_cross_entropy_fwd(const void* logits, int logits_bf16, const long long* target_a, const long long* target_b,
+                                  const float* lam, float smoothing, float* loss_row, float* lse, float* stats, int M, int V, int ld,
+                                  void* stream);
+/* dlogits[m, v] = (exp(x[m,v] - lse[m]) - t[m, v]) * (*grad_out) * stats[1] with t as above; a row with a target outside [0, V) is
+ * written as zeros.  grad_out, dlogits, ldo, the in-place rule and the refusals as vitamd_cross_entropy_bwd; target_b, lam and
+ * smoothing as the forward's.  With smoothing == 0 and lam == NULL: the bits of vitamd_cross_entropy_bwd. */
+int vitamd_soft_cross_entropy_bwd(const void* logits, int logits_bf16, const long long* target_a, const long long* target_b,
+                                  const float* lam, float smoothing, const float* lse, const float* stats, const float* grad_out,
+                                  void* dlogits, int dlogits_bf16, int M, int V, int ld, int ldo, void* stream);
 /* x fp32 [B*S, D]: x[b*S+s, :] = tok_table[ids[b*S+s], :] + pos_table[s, :] (one fp32 add: bit-equal to the framework's gather-and-add).
  * D % 4 == 0, 1 <= S <= pos_rows, else VITAMD_ERR_SHAPE.  An id outside [0, tok_rows) leaves that row of x untouched; no table is read
  * out of bounds.  replaces train_videogpt.py:49 (tok_embed(x) + pos_embed(arange)). */
@@ -384,6 +408,26 @@ int vitamd_assemble_tokens_grid_cap(void);
 int vitamd_frames_prep(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16,
                        float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, void* stream);
 int vitamd_frames_prep_grid_cap(void);
+/* vitamd_frames_prep with Mixup / CutMix applied on the way: every argument of vitamd_frames_prep, then
+ * rec int32 [B, 6] = (partner, mode, yl, yh, xl, xh) per output sample and lam fp32 [B], both on the device.  With
+ *   img_j[c, y, x] = table[c][ src[index[j], y0_j + y, x0_j + (flip_j ? W-1-x : x), c] ]
+ * (each sample cut with ITS OWN index and geom rows), output sample b with q = partner[b] is
+ *   mode 0, or q == b:  img_b                                              (the bits of vitamd_frames_prep)
+ *   mode 1 (Mixup):     fl(fl(img_b * l) + fl(img_q * m)),  l = lam[b], m = fl(1 - l)     three separately rounded fp32 operations,
+ *                       never a fused multiply-add: bit-equal to torch's CPU a.mul(l).add(p.mul(1 - l))
+ *   mode 2 (CutMix):    img_q where yl <= y < yh and xl <= x < xh, else img_b; lam is not read (the box decides per pixel, also
+ *                       inside the 4 pixels a lane of the fast form owns)
+ * image holds that fp32 value, patches_bf16 its round-to-nearest-even in vitamd_im2col_bf16's layout: the bits that kernel makes of
+ * the mixed image.  Either output may be NULL, not both.  The forms, lane ownership, LDS table, grid cap and source fetch are those of
+ * vitamd_frames_prep (one fetch for b and, where a pixel of the lane needs it, one for q).
+ * CLAMPS, before any address forms: those of vitamd_frames_prep for both samples; partner into [0, B); yl, yh into [0, H] and
+ * xl, xh into [0, W]; a mode outside {1, 2} counts as 0.
+ * lam may be NULL only if the caller promises that no row has mode 1: a NULL lam is taken as l = 1.
+ * Refusals as vitamd_frames_prep; NULL rec: VITAMD_ERR_ARG.  No backward.
+ * replaces timm's Mixup (mixup_alpha / cutmix_alpha, partner = the batch reversed) on the fp32 batch and the im2col behind it. */
+int vitamd_frames_prep_mix(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16,
+                           float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, const int* rec, const float* lam,
+                           void* stream);
 /* Fills geom int32 [B, 3] on the device for vitamd_frames_prep.  Sample b takes the words w0, w1, w2 of Philox4x32-10 with key
  * (seed low, seed high) and counter (b, 1, step low, step high) - c1 = 1 keeps it off vitamd_sample_logits' stream, which uses c1 = 0:
  *   y0 = (w0 * (Hs-H+1)) >> 32     x0 = (w1 * (Ws-W+1)) >> 32     flip = flip_enabled ? w2 >> 31 : 0       (64-bit products)

@@ -47,11 +47,76 @@ __device__ __forceinline__ Placement place(const unsigned char* src, const long 
   return pl;
 }
 
+// the 12 source bytes behind the 4 output pixels from column x of row y of a placed sample, as three little-endian words: the four
+// ALIGNED dwords that enclose them where the window lies inside src (DWORDS: src itself is 4-byte aligned), twelve byte loads otherwise.
+// The 4 source pixels are neighbours either way; under a flip output pixel j takes source pixel 3 - j.
 template <bool DWORDS>
+__device__ __forceinline__ void fetch12(const unsigned char* src, const Placement& pl, int y, int x, int Ws, int W, size_t src_bytes,
+                                        unsigned (&w)[3]) {
+  const int sx = pl.x0 + (pl.flip ? W - 4 - x : x);
+  const unsigned char* s = pl.frame + ((size_t)(pl.y0 + y) * Ws + sx) * 3;
+  const size_t off = (size_t)(s - src);
+  if (DWORDS && (off & ~(size_t)3) + 16 <= src_bytes) {
+    const unsigned* q = (const unsigned*)(src + (off & ~(size_t)3));
+    const unsigned d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
+    const unsigned sh = (unsigned)(off & 3) * 8;
+    w[0] = (unsigned)((((uint64_t)d1 << 32) | d0) >> sh);
+    w[1] = (unsigned)((((uint64_t)d2 << 32) | d1) >> sh);
+    w[2] = (unsigned)((((uint64_t)d3 << 32) | d2) >> sh);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w[k] = s[4 * k] | (s[4 * k + 1] << 8) | (s[4 * k + 2] << 16) | ((unsigned)s[4 * k + 3] << 24);
+  }
+}
+
+// channel c of those 4 pixels, in OUTPUT order
+__device__ __forceinline__ f32x4 lookup4(const float* tab, const unsigned (&w)[3], int c, int flip) {
+  f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = 3 * j + c;                                       // byte of source pixel j, channel c
+    const float val = tab[c * 256 + ((w[k >> 2] >> (8 * (k & 3))) & 0xffu)];
+    if (flip) v[3 - j] = val; else v[j] = val;
+  }
+  return v;
+}
+
+// The mix record of output sample b (vitamd_frames_prep_mix), clamped: partner into [0, B), the box into the image, a mode outside
+// {1, 2} or a sample that is its own partner = mode 0.  lam is read for mode 1 only (NULL: l = 1).
+struct MixRow { int q, mode, yl, yh, xl, xh; float l, m; };
+
+__device__ __forceinline__ MixRow mix_row(const int* rec, const float* lam, int b, int B, int H, int W) {
+  const int* r = rec + (size_t)b * 6;
+  MixRow mr;
+  mr.q = min(max(r[0], 0), B - 1);
+  const int mode = r[1];
+  mr.mode = (mode == 1 || mode == 2) && mr.q != b ? mode : 0;
+  mr.yl = min(max(r[2], 0), H);
+  mr.yh = min(max(r[3], 0), H);
+  mr.xl = min(max(r[4], 0), W);
+  mr.xh = min(max(r[5], 0), W);
+  mr.l = mr.mode == 1 && lam ? lam[b] : 1.f;
+  mr.m = __fsub_rn(1.f, mr.l);
+  return mr;
+}
+
+// fl(fl(a * l) + fl(p * m)): three roundings, the bits of torch's a.mul(l).add(p.mul(m)).  hipcc would contract a * l + p * m into a
+// fused multiply-add (one rounding fewer), also through __fmul_rn / __fadd_rn, which are the plain operators: the empty asm statements
+// make each product a value of its own before the sum.
+__device__ __forceinline__ float blend(float a, float p, float l, float m) {
+  float al = __fmul_rn(a, l), pm = __fmul_rn(p, m);
+  asm volatile("" : "+v"(al), "+v"(pm));
+  return __fadd_rn(al, pm);
+}
+
+// MIX: vitamd_frames_prep_mix.  The partner's 12 bytes are fetched only by the lanes one of whose pixels takes them (every lane of a
+// mode-1 sample, the lanes whose 4 pixels meet the box of a mode-2 sample); a sample's mode is uniform over its lanes.
+template <bool DWORDS, bool MIX>
 __global__ __launch_bounds__(256) void frames_prep_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ index,
                                                           const int* __restrict__ geom, const float* __restrict__ table,
                                                           __bf16* __restrict__ patches, float* __restrict__ image, int B, int Nsrc, int Hs,
-                                                          int Ws, int H, int W, int p, size_t src_bytes) {
+                                                          int Ws, int H, int W, int p, size_t src_bytes, const int* __restrict__ rec,
+                                                          const float* __restrict__ lam) {
   __shared__ float tab[3 * 256];
   for (int i = threadIdx.x; i < 3 * 256; i += 256) tab[i] = table[i];
   __syncthreads();
@@ -79,30 +144,38 @@ __global__ __launch_bounds__(256) void frames_prep_kernel(const unsigned char* _
       y = (int)(t / (unsigned)w4);
     }
     const Placement pl = place(src, index, geom, b, Nsrc, Hs, Ws, 3, H, W);
-    // the 4 source pixels are neighbours either way; under a flip output pixel j takes source pixel 3 - j
-    const int sx = pl.x0 + (pl.flip ? W - 4 - x : x);
-    const unsigned char* s = pl.frame + ((size_t)(pl.y0 + y) * Ws + sx) * 3;
-    const size_t off = (size_t)(s - src);
     unsigned w[3];
-    if (DWORDS && (off & ~(size_t)3) + 16 <= src_bytes) {
-      const unsigned* q = (const unsigned*)(src + (off & ~(size_t)3));
-      const unsigned d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
-      const unsigned sh = (unsigned)(off & 3) * 8;
-      w[0] = (unsigned)((((uint64_t)d1 << 32) | d0) >> sh);
-      w[1] = (unsigned)((((uint64_t)d2 << 32) | d1) >> sh);
-      w[2] = (unsigned)((((uint64_t)d3 << 32) | d2) >> sh);
-    } else {
+    fetch12<DWORDS>(src, pl, y, x, Ws, W, src_bytes, w);
+    MixRow mr = {};
+    Placement plq = pl;
+    unsigned wq[3] = {0u, 0u, 0u};
+    bool take[4] = {false, false, false, false};                    // mode 2: which of the 4 pixels lie in the box
+    if constexpr (MIX) {
+      mr = mix_row(rec, lam, b, B, H, W);
+      bool any = mr.mode == 1;
+      if (mr.mode == 2) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k) w[k] = s[4 * k] | (s[4 * k + 1] << 8) | (s[4 * k + 2] << 16) | ((unsigned)s[4 * k + 3] << 24);
+        for (int j = 0; j < 4; ++j) {
+          take[j] = y >= mr.yl && y < mr.yh && x + j >= mr.xl && x + j < mr.xh;
+          any |= take[j];
+        }
+      }
+      if (any) {
+        plq = place(src, index, geom, mr.q, Nsrc, Hs, Ws, 3, H, W);
+        fetch12<DWORDS>(src, plq, y, x, Ws, W, src_bytes, wq);
+      } else {
+        mr.mode = 0;
+      }
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      f32x4 v;
+      f32x4 v = lookup4(tab, w, c, pl.flip);
+      if constexpr (MIX) {
+        if (mr.mode != 0) {
+          const f32x4 u = lookup4(tab, wq, c, plq.flip);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int k = 3 * j + c;                                   // byte of source pixel j, channel c
-        const float val = tab[c * 256 + ((w[k >> 2] >> (8 * (k & 3))) & 0xffu)];
-        if (pl.flip) v[3 - j] = val; else v[j] = val;
+          for (int j = 0; j < 4; ++j) v[j] = mr.mode == 1 ? blend(v[j], u[j], mr.l, mr.m) : (take[j] ? u[j] : v[j]);
+        }
       }
       if (image) *(f32x4*)(image + (((size_t)b * 3 + c) * H + y) * W + x) = v;
       if (patches) {
@@ -113,10 +186,18 @@ __global__ __launch_bounds__(256) void frames_prep_kernel(const unsigned char* _
   }
 }
 
+// one table value: element (c, y, x) of a placed sample
+__device__ __forceinline__ float fetch1(const float* tab, const Placement& pl, int c, int y, int x, int Ws, int C, int W) {
+  const int sx = pl.x0 + (pl.flip ? W - 1 - x : x);
+  return tab[c * 256 + pl.frame[((size_t)(pl.y0 + y) * Ws + sx) * C + c]];
+}
+
+template <bool MIX>
 __global__ __launch_bounds__(256) void frames_prep_generic_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ index,
                                                                   const int* __restrict__ geom, const float* __restrict__ table,
                                                                   __bf16* __restrict__ patches, float* __restrict__ image, int B, int Nsrc,
-                                                                  int Hs, int Ws, int C, int H, int W, int p) {
+                                                                  int Hs, int Ws, int C, int H, int W, int p, const int* __restrict__ rec,
+                                                                  const float* __restrict__ lam) {
   __shared__ float tab[4 * 256];
   for (int i = threadIdx.x; i < C * 256; i += 256) tab[i] = table[i];
   __syncthreads();
@@ -128,9 +209,14 @@ __global__ __launch_bounds__(256) void frames_prep_generic_kernel(const unsigned
     const int y = (int)(t % H); t /= H;
     const int c = (int)(t % C);
     const int b = (int)(t / C);
-    const Placement pl = place(src, index, geom, b, Nsrc, Hs, Ws, C, H, W);
-    const int sx = pl.x0 + (pl.flip ? W - 1 - x : x);
-    const float v = tab[c * 256 + pl.frame[((size_t)(pl.y0 + y) * Ws + sx) * C + c]];
+    float v = fetch1(tab, place(src, index, geom, b, Nsrc, Hs, Ws, C, H, W), c, y, x, Ws, C, W);
+    if constexpr (MIX) {
+      const MixRow mr = mix_row(rec, lam, b, B, H, W);
+      if (mr.mode == 1 || (mr.mode == 2 && y >= mr.yl && y < mr.yh && x >= mr.xl && x < mr.xh)) {
+        const float u = fetch1(tab, place(src, index, geom, mr.q, Nsrc, Hs, Ws, C, H, W), c, y, x, Ws, C, W);
+        v = mr.mode == 1 ? blend(v, u, mr.l, mr.m) : u;
+      }
+    }
     if (image) image[i] = v;
     if (patches) {
       const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
@@ -186,33 +272,46 @@ inline dim3 capped_grid(size_t items) {
   return dim3((unsigned)(wgs < (size_t)PREP_GRID_CAP ? wgs : (size_t)PREP_GRID_CAP));
 }
 
+// the two entries: rec == nullptr launches the plain kernels
+template <bool MIX>
+int frames_prep(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16, float* image, int B,
+                int Nsrc, int Hs, int Ws, int C, int H, int W, int p, const int* rec, const float* lam, void* stream) {
+  if (B < 1 || Nsrc < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || C < 1 || C > 4 || H > Hs || W > Ws) return VITAMD_ERR_SHAPE;
+  if (patches_bf16 && (p < 1 || H % p != 0 || W % p != 0)) return VITAMD_ERR_SHAPE;
+  if (!index && Nsrc < B) return VITAMD_ERR_SHAPE;
+  const long long n_src = count(Nsrc, Hs, Ws, C), n_out = count(B, C, H, W);
+  if (n_src < 0 || n_out < 0) return VITAMD_ERR_SHAPE;
+  if (!src || !table || (!patches_bf16 && !image) || (MIX && !rec)) return VITAMD_ERR_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool aligned = ((uintptr_t)image & 15) == 0 && ((uintptr_t)patches_bf16 & 7) == 0;      // of the 16- and 8-byte stores
+  if (C == 3 && W % 4 == 0 && (!patches_bf16 || p % 4 == 0) && aligned && (long long)H * W / 4 < 0x7fffffffll) {
+    const dim3 grid = capped_grid((size_t)n_out / 12);
+    if (((uintptr_t)src & 3) == 0)
+      hipLaunchKernelGGL((frames_prep_kernel<true, MIX>), grid, dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16, image, B, Nsrc,
+                         Hs, Ws, H, W, p, (size_t)n_src, rec, lam);
+    else
+      hipLaunchKernelGGL((frames_prep_kernel<false, MIX>), grid, dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16, image, B, Nsrc,
+                         Hs, Ws, H, W, p, (size_t)n_src, rec, lam);
+  } else {
+    hipLaunchKernelGGL(frames_prep_generic_kernel<MIX>, capped_grid((size_t)n_out), dim3(256), 0, st, src, index, geom, table,
+                       (__bf16*)patches_bf16, image, B, Nsrc, Hs, Ws, C, H, W, p, rec, lam);
+  }
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" int vitamd_frames_prep_grid_cap(void) { return PREP_GRID_CAP; }
 
 extern "C" int vitamd_frames_prep(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16,
                                   float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, void* stream) {
-  if (B < 1 || Nsrc < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || C < 1 || C > 4 || H > Hs || W > Ws) return VITAMD_ERR_SHAPE;
-  if (patches_bf16 && (p < 1 || H % p != 0 || W % p != 0)) return VITAMD_ERR_SHAPE;
-  if (!index && Nsrc < B) return VITAMD_ERR_SHAPE;
-  const long long n_src = count(Nsrc, Hs, Ws, C), n_out = count(B, C, H, W);
-  if (n_src < 0 || n_out < 0) return VITAMD_ERR_SHAPE;
-  if (!src || !table || (!patches_bf16 && !image)) return VITAMD_ERR_ARG;
-  const hipStream_t st = (hipStream_t)stream;
-  const bool aligned = ((uintptr_t)image & 15) == 0 && ((uintptr_t)patches_bf16 & 7) == 0;      // of the 16- and 8-byte stores
-  if (C == 3 && W % 4 == 0 && (!patches_bf16 || p % 4 == 0) && aligned && (long long)H * W / 4 < 0x7fffffffll) {
-    const dim3 grid = capped_grid((size_t)n_out / 12);
-    if (((uintptr_t)src & 3) == 0)
-      hipLaunchKernelGGL(frames_prep_kernel<true>, grid, dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16, image, B, Nsrc, Hs, Ws,
-                         H, W, p, (size_t)n_src);
-    else
-      hipLaunchKernelGGL(frames_prep_kernel<false>, grid, dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16, image, B, Nsrc, Hs, Ws,
-                         H, W, p, (size_t)n_src);
-  } else {
-    hipLaunchKernelGGL(frames_prep_generic_kernel, capped_grid((size_t)n_out), dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16,
-                       image, B, Nsrc, Hs, Ws, C, H, W, p);
-  }
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return frames_prep<false>(src, index, geom, table, patches_bf16, image, B, Nsrc, Hs, Ws, C, H, W, p, nullptr, nullptr, stream);
+}
+
+extern "C" int vitamd_frames_prep_mix(const unsigned char* src, const long long* index, const int* geom, const float* table,
+                                      void* patches_bf16, float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p,
+                                      const int* rec, const float* lam, void* stream) {
+  return frames_prep<true>(src, index, geom, table, patches_bf16, image, B, Nsrc, Hs, Ws, C, H, W, p, rec, lam, stream);
 }
 
 extern "C" int vitamd_crop_flip_draw(int* geom, int B, int Hs, int Ws, int H, int W, int flip, unsigned long long seed, unsigned long long step,

@@ -9,6 +9,8 @@
 // launch that sums the per-row losses in a fixed order and counts the rows with an integer: no float atomics, the same bits every call.
 // The backward is one pass: dlogits = (exp(x - lse) - onehot) * (*grad_out / count), each lane writing the piece it has just read, so
 // it may run in place.  Rows whose target is ignore_index (or outside [0, V)) are written as zeros without being read.
+// The soft-target pair (Mixup / CutMix / label smoothing) is the SOFT form of the same two kernels: the row walk
+// also carries the plain sum of the row, and the one-hot becomes (1-e) (l [ya] + (1-l) [yb]) + e / V.
 #include "common.h"
 #include "../../include/vitamd.h"
 
@@ -75,29 +77,38 @@ __device__ __forceinline__ void merge(float& m, float& s, float m2, float s2) {
 }
 
 // ------------------------------------------------------------------------------------------------ cross-entropy forward
+// The soft target of vitamd_soft_cross_entropy_fwd / _bwd: t[v] = (1-e) (l [v == ya] + (1-l) [v == yb]) + e / V, ya = the kernels'
+// `target`.  lam == nullptr: l = 1 and target_b is not looked at.
+struct Soft { const long long* target_b; const float* lam; float smoothing; };
+
 // VEC: base and row stride allow 16-byte loads; the V % W columns after the last whole piece are read one by one.  WIDE: one row per
-// workgroup (256 lanes) instead of one per wave.
-template <bool BF16, bool VEC, bool WIDE>
+// workgroup (256 lanes) instead of one per wave.  SOFT: the same walk also carries the plain sum of the row (the smoothing term), merged
+// over lanes and waves beside (m, s), and the row's loss is the soft-target one; no row is ignored.
+template <bool BF16, bool VEC, bool WIDE, bool SOFT>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* logits, const long long* __restrict__ target, float* __restrict__ loss_row,
-                                                    float* __restrict__ lse_out, int M, int V, int ld, long long ignore_index) {
+                                                    float* __restrict__ lse_out, int M, int V, int ld, long long ignore_index, Soft soft) {
   constexpr int W = BF16 ? 8 : 4;
   constexpr int TPR = WIDE ? 256 : 64;      // lanes per row
   constexpr int RPW = 256 / TPR;            // rows per workgroup
   typedef typename Elem<BF16>::type T;
-  __shared__ float red[2][4];
+  __shared__ float red[3][4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int t = WIDE ? (int)threadIdx.x : lane;
   for (long row0 = (long)blockIdx.x * RPW; row0 < M; row0 += (long)gridDim.x * RPW) {
     const long row = row0 + (WIDE ? 0 : w);
     if (row >= M) continue;                 // wave-uniform (never taken when WIDE: no barrier is skipped)
     const T* xr = (const T*)logits + (size_t)row * ld;
-    float m = NEG_BIG, s = 0.f;
+    float m = NEG_BIG, s = 0.f, sx = 0.f;     // sx: the sum of the row's logits (SOFT)
     if constexpr (VEC) {
       const int nvec = V / W;
 #pragma unroll 2
       for (int i = t; i < nvec; i += TPR) {
         float f[W];
         load_piece<BF16, W>(xr, i, f);
+        if constexpr (SOFT) {
+#pragma unroll
+          for (int j = 0; j < W; ++j) sx += f[j];
+        }
         float vm = f[0];
 #pragma unroll
         for (int j = 1; j < W; ++j) vm = fmaxf(vm, f[j]);
@@ -109,32 +120,61 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* logits, const l
         m = mn;
       }
       const int c = nvec * W + t;
-      if (c < V) merge(m, s, load_one<BF16>(xr, c), 1.f);
+      if (c < V) {
+        const float x = load_one<BF16>(xr, c);
+        merge(m, s, x, 1.f);
+        if constexpr (SOFT) sx += x;
+      }
     } else {
-      for (int c = t; c < V; c += TPR) merge(m, s, load_one<BF16>(xr, c), 1.f);
+      for (int c = t; c < V; c += TPR) {
+        const float x = load_one<BF16>(xr, c);
+        merge(m, s, x, 1.f);
+        if constexpr (SOFT) sx += x;
+      }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+    for (int o = 32; o > 0; o >>= 1) {
+      merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+      if constexpr (SOFT) sx += __shfl_xor(sx, o, 64);
+    }
     if constexpr (WIDE) {
-      if (lane == 0) { red[0][w] = m; red[1][w] = s; }
+      if (lane == 0) { red[0][w] = m; red[1][w] = s; red[2][w] = sx; }
       __syncthreads();
-      m = red[0][0]; s = red[1][0];
+      m = red[0][0]; s = red[1][0]; sx = red[2][0];
 #pragma unroll
-      for (int i = 1; i < 4; ++i) merge(m, s, red[0][i], red[1][i]);
+      for (int i = 1; i < 4; ++i) { merge(m, s, red[0][i], red[1][i]); sx += red[2][i]; }
       __syncthreads();                      // red is rewritten by the next row
     }
     if (t == 0) {
       const float lse = m + __builtin_amdgcn_logf(s) * LN2;
       const long long tg = target[row];
       float loss = 0.f;
-      if (tg != ignore_index) loss = (tg >= 0 && tg < V) ? lse - load_one<BF16>(xr, (int)tg) : __builtin_nanf("");
+      if constexpr (SOFT) {
+        const float e = soft.smoothing, l = soft.lam ? soft.lam[row] : 1.f;
+        const long long tb = soft.lam ? soft.target_b[row] : tg;
+        if (tg >= 0 && tg < V && tb >= 0 && tb < V) {
+          float hard = load_one<BF16>(xr, (int)tg);                 // lam == nullptr: x[ya] itself, so that e == 0 gives lse - x[ya]
+          if (soft.lam) {
+            const float lb = 1.f - l;                               // a zero weight forms no term: its logit may be -inf
+            hard = (l != 0.f ? l * hard : 0.f) + (lb != 0.f ? lb * load_one<BF16>(xr, (int)tb) : 0.f);
+          }
+          float inner = (1.f - e) * hard;
+          if (e != 0.f) inner += e / (float)V * sx;
+          loss = lse - inner;
+        } else {
+          loss = __builtin_nanf("");
+        }
+      } else {
+        if (tg != ignore_index) loss = (tg >= 0 && tg < V) ? lse - load_one<BF16>(xr, (int)tg) : __builtin_nanf("");
+      }
       lse_out[row] = lse;
       loss_row[row] = loss;
     }
   }
 }
 
-// stats = {sum(loss_row) / count, 1 / count}, count = the rows whose target is not ignore_index: one workgroup, a fixed order
+// stats = {sum(loss_row) / count, 1 / count}, count = the rows whose target is not ignore_index (target == nullptr: every row): one
+// workgroup, a fixed order
 __global__ __launch_bounds__(1024) void ce_mean_kernel(const float* __restrict__ loss_row, const long long* __restrict__ target,
                                                       float* __restrict__ stats, int M, long long ignore_index) {
   __shared__ float ssum[16];
@@ -143,7 +183,7 @@ __global__ __launch_bounds__(1024) void ce_mean_kernel(const float* __restrict__
   int n = 0;
   for (int i = threadIdx.x; i < M; i += 1024) {
     a += loss_row[i];
-    n += target[i] != ignore_index ? 1 : 0;
+    n += !target || target[i] != ignore_index ? 1 : 0;
   }
   a = wave_sum(a);
 #pragma unroll
@@ -159,10 +199,21 @@ __global__ __launch_bounds__(1024) void ce_mean_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------ cross-entropy backward
 // tpr = lanes per row (64 or 256).  logits and dlogits may be the same buffer: a lane writes the piece it has just read.
-template <bool IN_BF16, bool OUT_BF16, bool VEC>
+// What is subtracted from the softmax at column c is hot_weight(c): 1 at the target's column, or the soft target (SOFT).
+struct Hot {
+  int a, b;                 // the columns of ya and yb (-1: none)
+  float wa, wb, u;          // (1-e) l, (1-e) (1-l), e / V
+  template <bool SOFT>
+  __device__ __forceinline__ float weight(int c) const {
+    if constexpr (SOFT) return (c == a ? wa : 0.f) + (c == b ? wb : 0.f) + u;
+    else return c == a ? 1.f : 0.f;
+  }
+};
+
+template <bool IN_BF16, bool OUT_BF16, bool VEC, bool SOFT>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const void* logits, const long long* __restrict__ target, const float* __restrict__ lse,
                                                     const float* __restrict__ stats, const float* __restrict__ grad_out, void* dlogits, int M,
-                                                    int V, int ld, int ldo, long long ignore_index, int tpr) {
+                                                    int V, int ld, int ldo, long long ignore_index, int tpr, Soft soft) {
   constexpr int W = (IN_BF16 || OUT_BF16) ? 8 : 4;
   typedef typename Elem<IN_BF16>::type TI;
   typedef typename Elem<OUT_BF16>::type TO;
@@ -170,8 +221,23 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const void* logits, const l
   const float scale = (grad_out ? *grad_out : 1.f) * stats[1];
   for (long row = (long)blockIdx.x * rpw + r; row < M; row += (long)gridDim.x * rpw) {
     const long long tg = target[row];
-    const bool live = tg != ignore_index && tg >= 0 && tg < V;
-    const int hot = live ? (int)tg : -1;
+    bool live = tg >= 0 && tg < V;
+    Hot hot = {live ? (int)tg : -1, -1, 1.f, 0.f, 0.f};
+    if constexpr (SOFT) {
+      const float e = soft.smoothing;
+      hot.wa = 1.f - e;
+      hot.u = e / (float)V;
+      if (soft.lam) {
+        const long long tb = soft.target_b[row];
+        const float lm = soft.lam[row];
+        live = live && tb >= 0 && tb < V;
+        hot.b = live ? (int)tb : -1;
+        hot.wa = (1.f - e) * lm;
+        hot.wb = (1.f - e) * (1.f - lm);
+      }
+    } else {
+      live = live && tg != ignore_index;
+    }
     const float l = lse[row];
     const TI* xr = (const TI*)logits + (size_t)row * ld;
     TO* dr = (TO*)dlogits + (size_t)row * ldo;
@@ -183,7 +249,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const void* logits, const l
         if (live) {
           load_piece<IN_BF16, W>(xr, i, f);
 #pragma unroll
-          for (int j = 0; j < W; ++j) f[j] = (ex2(f[j] - l) - (i * W + j == hot ? 1.f : 0.f)) * scale;
+          for (int j = 0; j < W; ++j) f[j] = (ex2(f[j] - l) - hot.weight<SOFT>(i * W + j)) * scale;
         } else {
 #pragma unroll
           for (int j = 0; j < W; ++j) f[j] = 0.f;
@@ -191,10 +257,10 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const void* logits, const l
         store_piece<OUT_BF16, W>(dr, i, f);
       }
       const int c = nvec * W + t;
-      if (c < V) store_one<OUT_BF16>(dr, c, live ? (ex2(load_one<IN_BF16>(xr, c) - l) - (c == hot ? 1.f : 0.f)) * scale : 0.f);
+      if (c < V) store_one<OUT_BF16>(dr, c, live ? (ex2(load_one<IN_BF16>(xr, c) - l) - hot.weight<SOFT>(c)) * scale : 0.f);
     } else {
       for (int c = t; c < V; c += tpr)
-        store_one<OUT_BF16>(dr, c, live ? (ex2(load_one<IN_BF16>(xr, c) - l) - (c == hot ? 1.f : 0.f)) * scale : 0.f);
+        store_one<OUT_BF16>(dr, c, live ? (ex2(load_one<IN_BF16>(xr, c) - l) - hot.weight<SOFT>(c)) * scale : 0.f);
     }
   }
 }
@@ -205,26 +271,69 @@ inline int ce_grid(int M, int rows_per_wg) {
   return (int)(g < CE_GRID_CAP ? g : CE_GRID_CAP);
 }
 
-template <bool BF16, bool VEC>
+template <bool BF16, bool VEC, bool SOFT>
 void launch_ce_fwd(const void* logits, const long long* target, float* loss_row, float* lse, int M, int V, int ld, long long ignore_index,
-                   hipStream_t s) {
+                   Soft soft, hipStream_t s) {
   if (V > CE_WIDE_V)
-    hipLaunchKernelGGL((ce_fwd_kernel<BF16, VEC, true>), dim3(ce_grid(M, 1)), dim3(256), 0, s, logits, target, loss_row, lse, M, V, ld, ignore_index);
+    hipLaunchKernelGGL((ce_fwd_kernel<BF16, VEC, true, SOFT>), dim3(ce_grid(M, 1)), dim3(256), 0, s, logits, target, loss_row, lse, M, V, ld,
+                       ignore_index, soft);
   else
-    hipLaunchKernelGGL((ce_fwd_kernel<BF16, VEC, false>), dim3(ce_grid(M, 4)), dim3(256), 0, s, logits, target, loss_row, lse, M, V, ld, ignore_index);
+    hipLaunchKernelGGL((ce_fwd_kernel<BF16, VEC, false, SOFT>), dim3(ce_grid(M, 4)), dim3(256), 0, s, logits, target, loss_row, lse, M, V, ld,
+                       ignore_index, soft);
 }
 
-template <bool IN_BF16, bool OUT_BF16>
+template <bool IN_BF16, bool OUT_BF16, bool SOFT>
 void launch_ce_bwd(bool vec, const void* logits, const long long* target, const float* lse, const float* stats, const float* grad_out,
-                   void* dlogits, int M, int V, int ld, int ldo, long long ignore_index, hipStream_t s) {
+                   void* dlogits, int M, int V, int ld, int ldo, long long ignore_index, Soft soft, hipStream_t s) {
   const int tpr = V > CE_WIDE_V ? 256 : 64;
   const dim3 grid(ce_grid(M, 256 / tpr));
   if (vec)
-    hipLaunchKernelGGL((ce_bwd_kernel<IN_BF16, OUT_BF16, true>), grid, dim3(256), 0, s, logits, target, lse, stats, grad_out, dlogits, M, V, ld,
-                       ldo, ignore_index, tpr);
+    hipLaunchKernelGGL((ce_bwd_kernel<IN_BF16, OUT_BF16, true, SOFT>), grid, dim3(256), 0, s, logits, target, lse, stats, grad_out, dlogits, M, V,
+                       ld, ldo, ignore_index, tpr, soft);
   else
-    hipLaunchKernelGGL((ce_bwd_kernel<IN_BF16, OUT_BF16, false>), grid, dim3(256), 0, s, logits, target, lse, stats, grad_out, dlogits, M, V, ld,
-                       ldo, ignore_index, tpr);
+    hipLaunchKernelGGL((ce_bwd_kernel<IN_BF16, OUT_BF16, false, SOFT>), grid, dim3(256), 0, s, logits, target, lse, stats, grad_out, dlogits, M, V,
+                       ld, ldo, ignore_index, tpr, soft);
+}
+
+// the soft target's own argument rules (after the shape check): smoothing in [0, 1], target_b wherever lam is given
+inline bool soft_ok(const Soft& soft) { return soft.smoothing >= 0.f && soft.smoothing <= 1.f && (!soft.lam || soft.target_b); }
+
+// the bodies of the two pairs of entries; SOFT: the mean is over every row (no target is handed to the mean kernel)
+template <bool SOFT>
+int ce_fwd(const void* logits, int logits_bf16, const long long* target, float* loss_row, float* lse, float* stats, int M, int V, int ld,
+           long long ignore_index, Soft soft, void* stream) {
+  if (M < 1 || V < 2 || V > CE_MAX_V || ld < V) return VITAMD_ERR_SHAPE;
+  if (!logits || !target || !loss_row || !lse || !stats || (SOFT && !soft_ok(soft))) return VITAMD_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = aligned16(logits) && ld % (logits_bf16 ? 8 : 4) == 0;
+  if (logits_bf16) {
+    if (vec) launch_ce_fwd<true, true, SOFT>(logits, target, loss_row, lse, M, V, ld, ignore_index, soft, s);
+    else launch_ce_fwd<true, false, SOFT>(logits, target, loss_row, lse, M, V, ld, ignore_index, soft, s);
+  } else {
+    if (vec) launch_ce_fwd<false, true, SOFT>(logits, target, loss_row, lse, M, V, ld, ignore_index, soft, s);
+    else launch_ce_fwd<false, false, SOFT>(logits, target, loss_row, lse, M, V, ld, ignore_index, soft, s);
+  }
+  hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(1024), 0, s, (const float*)loss_row, SOFT ? nullptr : target, stats, M, ignore_index);
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+template <bool SOFT>
+int ce_bwd(const void* logits, int logits_bf16, const long long* target, const float* lse, const float* stats, const float* grad_out,
+           void* dlogits, int dlogits_bf16, int M, int V, int ld, int ldo, long long ignore_index, Soft soft, void* stream) {
+  if (M < 1 || V < 2 || V > CE_MAX_V || ld < V || ldo < V) return VITAMD_ERR_SHAPE;
+  if (!logits || !target || !lse || !stats || !dlogits || (SOFT && !soft_ok(soft))) return VITAMD_ERR_ARG;
+  if (logits == dlogits && (!logits_bf16 != !dlogits_bf16 || ld != ldo)) return VITAMD_ERR_ARG;   // in place: same type and stride only
+  hipStream_t s = (hipStream_t)stream;
+  // a piece is 8 elements when either side is bf16, else 4: fp32 rows then need a stride that keeps both 16-byte halves aligned
+  const bool vec = aligned16(logits) && aligned16(dlogits) && ld % (logits_bf16 ? 8 : 4) == 0 && ldo % (dlogits_bf16 ? 8 : 4) == 0;
+  if (logits_bf16) {
+    if (dlogits_bf16) launch_ce_bwd<true, true, SOFT>(vec, logits, target, lse, stats, grad_out, dlogits, M, V, ld, ldo, ignore_index, soft, s);
+    else launch_ce_bwd<true, false, SOFT>(vec, logits, target, lse, stats, grad_out, dlogits, M, V, ld, ldo, ignore_index, soft, s);
+  } else {
+    if (dlogits_bf16) launch_ce_bwd<false, true, SOFT>(vec, logits, target, lse, stats, grad_out, dlogits, M, V, ld, ldo, ignore_index, soft, s);
+    else launch_ce_bwd<false, false, SOFT>(vec, logits, target, lse, stats, grad_out, dlogits, M, V, ld, ldo, ignore_index, soft, s);
+  }
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
 // ------------------------------------------------------------------------------------------------ token + position embedding
@@ -274,38 +383,27 @@ extern "C" int vitamd_cross_entropy_grid_rows(int V) {
 
 extern "C" int vitamd_cross_entropy_fwd(const void* logits, int logits_bf16, const long long* target, float* loss_row, float* lse, float* stats,
                                         int M, int V, int ld, long long ignore_index, void* stream) {
-  if (M < 1 || V < 2 || V > CE_MAX_V || ld < V) return VITAMD_ERR_SHAPE;
-  if (!logits || !target || !loss_row || !lse || !stats) return VITAMD_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = aligned16(logits) && ld % (logits_bf16 ? 8 : 4) == 0;
-  if (logits_bf16) {
-    if (vec) launch_ce_fwd<true, true>(logits, target, loss_row, lse, M, V, ld, ignore_index, s);
-    else launch_ce_fwd<true, false>(logits, target, loss_row, lse, M, V, ld, ignore_index, s);
-  } else {
-    if (vec) launch_ce_fwd<false, true>(logits, target, loss_row, lse, M, V, ld, ignore_index, s);
-    else launch_ce_fwd<false, false>(logits, target, loss_row, lse, M, V, ld, ignore_index, s);
-  }
-  hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(1024), 0, s, (const float*)loss_row, target, stats, M, ignore_index);
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return ce_fwd<false>(logits, logits_bf16, target, loss_row, lse, stats, M, V, ld, ignore_index, Soft{nullptr, nullptr, 0.f}, stream);
 }
 
 extern "C" int vitamd_cross_entropy_bwd(const void* logits, int logits_bf16, const long long* target, const float* lse, const float* stats,
                                         const float* grad_out, void* dlogits, int dlogits_bf16, int M, int V, int ld, int ldo,
                                         long long ignore_index, void* stream) {
-  if (M < 1 || V < 2 || V > CE_MAX_V || ld < V || ldo < V) return VITAMD_ERR_SHAPE;
-  if (!logits || !target || !lse || !stats || !dlogits) return VITAMD_ERR_ARG;
-  if (logits == dlogits && (!logits_bf16 != !dlogits_bf16 || ld != ldo)) return VITAMD_ERR_ARG;   // in place: same type and stride only
-  hipStream_t s = (hipStream_t)stream;
-  // a piece is 8 elements when either side is bf16, else 4: fp32 rows then need a stride that keeps both 16-byte halves aligned
-  const bool vec = aligned16(logits) && aligned16(dlogits) && ld % (logits_bf16 ? 8 : 4) == 0 && ldo % (dlogits_bf16 ? 8 : 4) == 0;
-  if (logits_bf16) {
-    if (dlogits_bf16) launch_ce_bwd<true, true>(vec, logits, target, lse, stats, grad_out, dlogits, M, V, ld, ldo, ignore_index, s);
-    else launch_ce_bwd<true, false>(vec, logits, target, lse, stats, grad_out, dlogits, M, V, ld, ldo, ignore_index, s);
-  } else {
-    if (dlogits_bf16) launch_ce_bwd<false, true>(vec, logits, target, lse, stats, grad_out, dlogits, M, V, ld, ldo, ignore_index, s);
-    else launch_ce_bwd<false, false>(vec, logits, target, lse, stats, grad_out, dlogits, M, V, ld, ldo, ignore_index, s);
-  }
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return ce_bwd<false>(logits, logits_bf16, target, lse, stats, grad_out, dlogits, dlogits_bf16, M, V, ld, ldo, ignore_index,
+                       Soft{nullptr, nullptr, 0.f}, stream);
+}
+
+extern "C" int vitamd_soft_cross_entropy_fwd(const void* logits, int logits_bf16, const long long* target_a, const long long* target_b,
+                                             const float* lam, float smoothing, float* loss_row, float* lse, float* stats, int M, int V,
+                                             int ld, void* stream) {
+  return ce_fwd<true>(logits, logits_bf16, target_a, loss_row, lse, stats, M, V, ld, 0, Soft{target_b, lam, smoothing}, stream);
+}
+
+extern "C" int vitamd_soft_cross_entropy_bwd(const void* logits, int logits_bf16, const long long* target_a, const long long* target_b,
+                                             const float* lam, float smoothing, const float* lse, const float* stats, const float* grad_out,
+                                             void* dlogits, int dlogits_bf16, int M, int V, int ld, int ldo, void* stream) {
+  return ce_bwd<true>(logits, logits_bf16, target_a, lse, stats, grad_out, dlogits, dlogits_bf16, M, V, ld, ldo, 0,
+                      Soft{target_b, lam, smoothing}, stream);
 }
 
 extern "C" int vitamd_embed_tokens_fwd(const float* tok_table, const float* pos_table, const long long* ids, float* x, int B, int S, int D,

@@ -92,6 +92,12 @@ def parse_args(argv=None):
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
     p.add_argument("--dropout", type=float, default=0.0)
+    p.add_argument("--mixup", type=float, default=0.0, help="Mixup: the alpha of its Beta draw (0 = off); needs --u8 (vitamd.mix.MixLoader)")
+    p.add_argument("--cutmix", type=float, default=0.0, help="CutMix: the alpha of its Beta draw (0 = off); needs --u8")
+    p.add_argument("--mix_prob", type=float, default=1.0, help="the chance that a batch is mixed at all")
+    p.add_argument("--mix_switch_prob", type=float, default=0.5, help="the chance of CutMix when both --mixup and --cutmix are on")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="label smoothing of the soft-target loss (vitamd.lm.soft_cross_entropy); also works on the fp32 batch")
     p.add_argument("--graph", action="store_true",
                    help="one graph launch per iteration (vitamd.graph.GraphedTrainStep): forward, loss, backward, the clip, the LR schedule "
                         "and the AdamW update, all replayed from the device; needs --dropout 0 (and not --u8)")
@@ -113,6 +119,11 @@ def main(argv=None):
     if args.graph and args.u8:
         raise SystemExit("--graph with --u8: the device loader hands over vitamd.data.Frames (patch rows in buffers of its own), not tensors "
                          "to copy into a graph's static inputs; a graph-fed loader is not built - use one or the other")
+    mixing = args.mixup > 0 or args.cutmix > 0
+    if mixing and not args.u8:
+        raise SystemExit("--mixup / --cutmix mix inside the device input feed (vitamd.mix.MixLoader): they need --u8")
+    if args.graph and args.label_smoothing > 0:
+        raise SystemExit("--graph with --label_smoothing: the graphed step is built on the hard-label loss - use one or the other")
     dev = torch.device("cuda")
     cfg = ViTConfig(args.image_size, 3, args.patch_size, args.transformer, args.extra_tokens, args.dropout)
     model = ViTClassifier(cfg, args.num_classes).to(dev)
@@ -128,17 +139,26 @@ def main(argv=None):
         u8 = torch.randint(0, 256, (args.bs, side, side, 3), generator=g, dtype=torch.uint8)
         host_labels = labels.cpu()
         host = ((u8, host_labels) for _ in range(args.train_steps))
-        feed = DeviceLoader(host, dev, args.image_size, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)
+        if mixing:
+            from vitamd.mix import Mix, MixLoader
+            mix = Mix(args.mixup, args.cutmix, args.mix_prob, args.mix_switch_prob, label_smoothing=args.label_smoothing, seed=0)
+            feed = MixLoader(host, dev, args.image_size, mix, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)
+        else:
+            feed = DeviceLoader(host, dev, args.image_size, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)
+    loss_fn = None                                              # train_step's default: the route a run without these flags takes today
+    if mixing or args.label_smoothing > 0:
+        from vitamd.mix import SoftTargetLoss
+        loss_fn = SoftTargetLoss(args.label_smoothing)
     graphed = None
     if args.graph:
         from vitamd.graph import GraphedTrainStep
-        loss_fn = nn.functional.cross_entropy
-        graphed = GraphedTrainStep(model, lambda x, y: loss_fn(model(x), y), (images, labels), optim)      # refuses dropout > 0
+        hard_loss = nn.functional.cross_entropy
+        graphed = GraphedTrainStep(model, lambda x, y: hard_loss(model(x), y), (images, labels), optim)      # refuses dropout > 0
     for step in range(args.train_steps):
         t0 = time.time()
         if feed is not None:
             images, labels = next(feed)
-        loss = graphed(images, labels) if graphed is not None else train_step(model, images, labels, optim, sched)
+        loss = graphed(images, labels) if graphed is not None else train_step(model, images, labels, optim, sched, loss_fn)
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} {args.bs / (time.time() - t0):.0f} img/s")
 

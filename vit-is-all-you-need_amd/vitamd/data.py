@@ -270,9 +270,18 @@ class DeviceLoader:
             else:
                 geom = center_geom(n, src_hw, self.out_hw).to(self.device)
             table = norm_table(self.mean, self.std, channels=src.shape[3], device=self.device)
-            frames = Frames(src, self.out_hw, geom=geom, table=table).materialise(self.patch, self.image).release_source()
+            frames = self._frames(src, geom, table).materialise(self.patch, self.image).release_source()
+            labels = self._labels(labels)
         consumed = torch.cuda.Event()
         consumed.record(cur)
         s["consumed"] = consumed
         self.step += 1
         return frames, labels
+
+    def _frames(self, src, geom, table):
+        """the batch object of this step, before it is materialised (vitamd.mix.MixLoader overrides it; self.step is this batch's)"""
+        return Frames(src, self.out_hw, geom=geom, table=table)
+
+    def _labels(self, labels):
+        """what is handed out beside the frames: the labels on the device as they came (or None)"""
+        return labels

@@ -26,11 +26,38 @@ needs no host value and generation never synchronises.
 """
 from __future__ import annotations
 
+import contextlib
+import gc
+
 import torch
 
 from . import decode as _decode
 from . import functions as F
 from . import ops as _ops
+
+
+@contextlib.contextmanager
+def quiet_collector():
+    """Around every capture.  Cyclic garbage may hold a torch.cuda.CUDAGraph - a model that keeps its GraphedDecoder is such a cycle, the
+    decoder's head being a bound method of the model - and on ROCm that object's destructor synchronises the device: refused while a
+    stream captures, and fatal (an exception out of a destructor) when the cyclic collector happens to run it there.  torch.cuda.graph no
+    longer collects before it captures, so: collect now, and hold the automatic collector until the capture is over."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
+
+def _fresh_workspace(device, stream):
+    """Before the warm-up of a capture: forget the split-K workspace of the capture stream (ops._WORKSPACES), so that the warm-up
+    allocates one that this graph alone bakes and, through the reference its owner takes after the capture, keeps alive.  Streams are
+    handles out of a pool of 32, so an entry found here was left by an older graph or by eager work on a recycled handle, and
+    ops._workspace replaces an entry that is too small - which would free memory that older graph still writes on replay."""
+    _ops._WORKSPACES.pop((device, stream.cuda_stream), None)
 
 
 class GraphedStep:
@@ -51,6 +78,7 @@ class GraphedStep:
         # AccumulateGrad nodes remember the stream they were created on, and nodes created on another stream than the capturing one
         # made every replayed backward warn about (and potentially synchronise on) a stream mismatch
         s = torch.cuda.Stream()
+        _fresh_workspace(self.x.device, s)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(max(1, warmup)):
@@ -59,10 +87,11 @@ class GraphedStep:
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=s):
+        with quiet_collector(), torch.cuda.graph(self.graph, stream=s):
             # detached: the static loss tensor must not keep the captured step's autograd graph (and with it the parameters'
             # AccumulateGrad nodes, bound to the capture stream) alive - an eager backward on another stream afterwards would warn
             self.loss = self._eager(zero=False).detach()
+        self._ws = _ops._WORKSPACES.get((self.x.device, s.cuda_stream))      # kept alive: its address is in the graph
         self.grads = [p.grad for p in self.params]
 
     def _eager(self, zero=True):
@@ -152,6 +181,7 @@ class GraphedTrainStep:
         optim._check_lr()
         items = [(group, p) for group in optim.param_groups for p in group["params"] if p.requires_grad]
         # warm up ON THE CAPTURE STREAM, as GraphedStep does; the optimiser's launches too, over a table of their own
+        _fresh_workspace(self.device, s)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(self.warmup):
@@ -168,12 +198,13 @@ class GraphedTrainStep:
         optim._build(items, bind=False)                 # moments (created here when missing) and device buffers: outside the capture
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=s):
+        with quiet_collector(), torch.cuda.graph(graph, stream=s):
             loss = self._eager(zero=False).detach()     # detached for GraphedStep's reason
             optim._bind()                               # host work: the static gradients' addresses, known only now
             optim._enqueue(torch.cuda.current_stream().cuda_stream)
         optim._upload_table()                           # the capture ran nothing: the table reaches the device before the first replay
         self.graph, self.loss, self._table = graph, loss, optim._table
+        self._ws = _ops._WORKSPACES.get((self.device, s.cuda_stream))        # kept alive: its address is in the graph
         self.grads = [p.grad for p in self.params]
         self._table_grads = [p.grad for _, p in items]
         self.captures += 1
@@ -281,6 +312,7 @@ class GraphedDecoder:
         baked = self._refresh()
         # warm up ON THE CAPTURE STREAM (as GraphedStep does): vitamd_init, code-object loading, the first hipFuncSetAttribute of each skinny GEMM form, the
         # allocator and that stream's split-K / attention workspace all happen here, none of them inside the capture
+        _fresh_workspace(cache.device, s)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             _ops.init(cache.device)
@@ -291,7 +323,7 @@ class GraphedDecoder:
         torch.cuda.synchronize()
         self._ws = _ops._WORKSPACES.get((cache.device, s.cuda_stream))      # kept alive: its address is in the graph
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=s):
+        with quiet_collector(), torch.cuda.graph(graph, stream=s):
             out = self._body()
         # the capture ran nothing on the device, but the host mirrors moved
         cache.len = 0

@@ -78,6 +78,8 @@ SIGNATURES = {
     "vitamd_cross_entropy_grid_rows": [_I],
     "vitamd_cross_entropy_fwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _LL, _P],
     "vitamd_cross_entropy_bwd": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _P],
+    "vitamd_soft_cross_entropy_fwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
+    "vitamd_soft_cross_entropy_bwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_embed_tokens_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_embed_tokens_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vitamd_assemble_tokens_grid_cap": [],
@@ -99,6 +101,7 @@ SIGNATURES = {
     "vitamd_resize_norm_fwd": [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_resize_norm_bwd": [_P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_frames_prep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vitamd_frames_prep_mix": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "vitamd_frames_prep_grid_cap": [],
     "vitamd_crop_flip_draw": [_P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P],
     "vitamd_frames_to_u8": [_P, _P, _I, _I, _I, _I, _P],

@@ -2,6 +2,7 @@
 token + position embedding (csrc/loss.hip).
 
     loss = lm.cross_entropy(logits, target)                       # F.cross_entropy(logits.float(), target), mean, on the device
+    loss = lm.soft_cross_entropy(logits, ya, yb, lam, 0.1)        # Mixup / CutMix label pairs + label smoothing
     loss = lm.linear_cross_entropy(h, proj.weight, proj.bias, y)  # head GEMM -> bf16 logits -> loss, nothing in fp32 in between
     x = lm.token_embed(ids, tok_embed.weight, pos_embed.weight)   # tok[ids] + pos[:S], fp32
     x = lm.prefixed_token_embed(ids, tok, pos, prefix)            # cat([prefix rows, tok[ids] + pos[:S]], 1), one kernel (csrc/assemble.hip)
@@ -66,6 +67,45 @@ def cross_entropy(logits, target, ignore_index=-100):
     in fp32 on the logits as stored: the 0-dim fp32 loss.  Its gradient comes back in the logits' dtype.  A drop-in `loss_fn` for
     train_vit.train_step and vitamd.graph.GraphedStep."""
     return CrossEntropyFn.apply(logits, target, ignore_index)
+
+
+class SoftCrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, target_b, lam, smoothing):
+        if not isinstance(logits, torch.Tensor) or logits.dim() < 1:
+            raise ops._lib.VitamdError("logits: expected a tensor [..., V]")
+        x = _rows(logits)
+        M = x.shape[0]
+        t = _target(target, M)
+        if lam is not None:
+            if not isinstance(lam, torch.Tensor) or lam.numel() != M:
+                raise ops._lib.VitamdError(f"lam: expected a tensor of {M} elements (one per row of logits)")
+            tb, lam = _target(target_b, M), lam.detach().reshape(-1).to(F32).contiguous()
+        else:
+            tb = None
+        soft = (tb, lam, float(smoothing))
+        _, lse, stats = ops.cross_entropy_fwd(x, t, soft=soft)
+        ctx.save_for_backward(x, t, lse, stats, *(() if lam is None else (tb, lam)))
+        ctx.meta = (tuple(logits.shape), float(smoothing))
+        return stats[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, lse, stats, *pair = ctx.saved_tensors
+        shape, smoothing = ctx.meta
+        tb, lam = pair if pair else (None, None)
+        d = ops.cross_entropy_bwd(x, t, lse, stats, _scalar(g), soft=(tb, lam, smoothing))           # dense, the logits' dtype
+        return d.view(shape), None, None, None, None
+
+
+def soft_cross_entropy(logits, target, target_b=None, lam=None, smoothing=0.0):
+    """Mean soft-target cross-entropy of logits [..., V] (fp32 or bf16, device) against the target
+    (1 - smoothing) * (lam * onehot(target) + (1 - lam) * onehot(target_b)) + smoothing / V per row - Mixup / CutMix label pairs and
+    label smoothing (timm's SoftTargetCrossEntropy on its mixup_target) without the [M, V] target tensor: the 0-dim fp32 loss, the mean
+    over all rows.  lam: device fp32 [...] read by the kernels (None: target alone, target_b is not looked at).  With smoothing 0 and
+    lam None it is cross_entropy without ignored rows, bit for bit.  A drop-in loss for train_vit.train_step through
+    vitamd.mix.SoftTargetLoss."""
+    return SoftCrossEntropyFn.apply(logits, target, target_b, lam, smoothing)
 
 
 def fused_head_applies(V, D):

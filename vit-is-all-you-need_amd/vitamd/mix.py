@@ -1,0 +1,195 @@
+"""Mixup, CutMix and label smoothing for ViT training: the second half of the DeiT / timm recipe, fused into the
+device input feed (csrc/input.hip, vitamd_frames_prep_mix) and the loss (csrc/loss.hip, vitamd_soft_cross_entropy_fwd / _bwd).
+
+    mix = Mix(mixup_alpha=0.8, cutmix_alpha=1.0, label_smoothing=0.1)
+    loader = MixLoader(host_iter, "cuda", 224, mix, patch=16, image=False)     # yields (MixedFrames, MixedLabels)
+    loss_fn = SoftTargetLoss(mix.label_smoothing)
+    for frames, labels in loader:
+        loss = train_vit.train_step(model, frames, labels, optim, loss_fn=loss_fn)
+
+What is mixed is decided on the HOST, from a counter-based generator keyed by (seed, step): a record of six integers and one float
+per sample, which crosses to the device through a pinned buffer.  The prep kernel then cuts sample b and its partner, each with its
+own crop and flip, and blends or pastes them on the way to the patch rows: the fp32 batch, the three torch passes over it and the
+im2col behind them do not exist.  The loss takes the two label vectors and lam as they are; no [B, classes] target is built."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import data, lm, ops
+from . import lib as _lib
+
+MODE_NONE, MODE_MIXUP, MODE_CUTMIX = 0, 1, 2
+
+
+class Mix:
+    """The draw of timm's Mixup: mixup_alpha / cutmix_alpha are the Beta parameters (0 disables that mode), prob the chance that a
+    batch (or, per_sample=True, a sample) is mixed at all, switch_prob the chance of CutMix when both modes are enabled.  The partner
+    of sample b is sample B-1-b (the batch reversed).  label_smoothing is carried for the loss (SoftTargetLoss); the draw ignores it."""
+
+    def __init__(self, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, per_sample=False, label_smoothing=0.1, seed=0):
+        for name, v in (("mixup_alpha", mixup_alpha), ("cutmix_alpha", cutmix_alpha)):
+            if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"Mix: {name} must be a finite number >= 0, got {v!r}")
+        for name, v in (("prob", prob), ("switch_prob", switch_prob), ("label_smoothing", label_smoothing)):
+            if not isinstance(v, (int, float)) or isinstance(v, bool) or not 0.0 <= v <= 1.0:
+                raise ValueError(f"Mix: {name} must lie in [0, 1], got {v!r}")
+        if not isinstance(seed, int) or isinstance(seed, bool) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"Mix: seed must be an integer in [0, 2^64), got {seed!r}")
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob, self.per_sample = float(prob), float(switch_prob), bool(per_sample)
+        self.label_smoothing, self.seed = float(label_smoothing), seed
+
+    @property
+    def enabled(self):
+        return self.prob > 0 and (self.mixup_alpha > 0 or self.cutmix_alpha > 0)
+
+    def _decide(self, rng, H, W):
+        """one decision -> (mode, yl, yh, xl, xh, lam as a Python float); all in float64 / Python integers"""
+        u_mix, u_switch = rng.random(), rng.random()
+        if not self.enabled or not u_mix < self.prob:
+            return MODE_NONE, 0, 0, 0, 0, 1.0
+        if self.mixup_alpha > 0 and self.cutmix_alpha > 0:
+            mode = MODE_CUTMIX if u_switch < self.switch_prob else MODE_MIXUP
+        else:
+            mode = MODE_MIXUP if self.mixup_alpha > 0 else MODE_CUTMIX
+        alpha = self.mixup_alpha if mode == MODE_MIXUP else self.cutmix_alpha
+        lam0 = float(rng.beta(alpha, alpha))
+        if mode == MODE_MIXUP:
+            return mode, 0, 0, 0, 0, lam0
+        r = math.sqrt(1.0 - lam0)
+        ch, cw = int(H * r), int(W * r)
+        cy, cx = int(rng.integers(0, H)), int(rng.integers(0, W))
+        yl, yh = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
+        xl, xh = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
+        return mode, yl, yh, xl, xh, 1.0 - (yh - yl) * (xh - xl) / (H * W)
+
+    def draw(self, B, hw, step):
+        """-> (rec int32 [B, 6] = (partner, mode, yl, yh, xl, xh), lam fp32 [B]) on the CPU, from numpy's Philox keyed by (seed, step):
+        the same (seed, step) gives the same record, and no device value is read.  Mixup rows: lam ~ Beta(alpha, alpha), the box is
+        zeros.  CutMix rows: the box of timm's rand_bbox around a uniform centre, clipped to the image, and lam = 1 - its area / (H W)
+        (rounded once, to fp32).  Unmixed rows: mode 0, lam = 1."""
+        H, W = data._hw(hw)
+        if not isinstance(B, int) or isinstance(B, bool) or B < 1:
+            raise ValueError(f"Mix.draw: B must be a positive integer, got {B!r}")
+        if not isinstance(step, int) or isinstance(step, bool) or not 0 <= step < 1 << 64:
+            raise ValueError(f"Mix.draw: step must be an integer in [0, 2^64), got {step!r}")
+        rng = np.random.Generator(np.random.Philox(key=np.array([self.seed, step], dtype=np.uint64)))
+        rows = [self._decide(rng, H, W) for _ in range(B)] if self.per_sample else [self._decide(rng, H, W)] * B
+        rec = torch.tensor([[B - 1 - b, *row[:5]] for b, row in enumerate(rows)], dtype=torch.int32)
+        lam = torch.tensor([row[5] for row in rows], dtype=torch.float64).to(torch.float32)
+        return rec, lam
+
+
+class MixedLabels:
+    """The labels of a mixed batch: a, b int64 [B] (b = a[partner]) and lam fp32 [B] on the device; row m's target is
+    lam[m] * onehot(a[m]) + (1 - lam[m]) * onehot(b[m])."""
+
+    def __init__(self, a, b, lam):
+        self.a, self.b, self.lam = a, b, lam
+
+    def __iter__(self):
+        return iter((self.a, self.b, self.lam))
+
+
+class SoftTargetLoss:
+    """loss_fn of train_vit.train_step: lm.soft_cross_entropy with this label smoothing, on an int64 label tensor or on MixedLabels."""
+
+    def __init__(self, smoothing=0.0):
+        if not isinstance(smoothing, (int, float)) or isinstance(smoothing, bool) or not 0.0 <= smoothing <= 1.0:
+            raise ValueError(f"SoftTargetLoss: smoothing must lie in [0, 1], got {smoothing!r}")
+        self.smoothing = float(smoothing)
+
+    def __call__(self, logits, labels):
+        if isinstance(labels, MixedLabels):
+            return lm.soft_cross_entropy(logits, labels.a, labels.b, labels.lam, self.smoothing)
+        return lm.soft_cross_entropy(logits, labels, smoothing=self.smoothing)
+
+
+class MixedFrames(data.Frames):
+    """data.Frames whose samples are mixed with their partners on the way out of the prep kernel.  mix = (rec int32 [B, 6], lam fp32
+    [B]) on the device (Mix.draw brought over): what images() and patches(p) return is the mixed batch."""
+
+    def __init__(self, src_u8, size, index=None, geom=None, table=None, *, mix):
+        super().__init__(src_u8, size, index=index, geom=geom, table=table)
+        if not (isinstance(mix, (tuple, list)) and len(mix) == 2):
+            raise ValueError("MixedFrames: mix must be (rec int32 [B, 6], lam fp32 [B])")
+        rec, lam = mix
+        B = self.shape[0]
+        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.int32 or tuple(rec.shape) != (B, 6):
+            raise ValueError(f"MixedFrames: rec must be int32 [{B}, 6]")
+        if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or tuple(lam.shape) != (B,):
+            raise ValueError(f"MixedFrames: lam must be fp32 [{B}]")
+        self._mix = (rec.to(self.device).contiguous(), lam.to(self.device).contiguous())
+
+    @property
+    def mix(self):
+        """(rec, lam) on the device, as this batch is mixed"""
+        return self._mix
+
+    def materialise(self, patch=None, image=True):
+        """as Frames.materialise, through the mixing form of the kernel"""
+        want_p = patch is not None and patch not in self._patches
+        want_i = bool(image) and self._image is None
+        if patch is not None and (not isinstance(patch, int) or isinstance(patch, bool) or patch < 1 or self.shape[2] % patch or self.shape[3] % patch):
+            raise ValueError(f"Frames: patch {patch!r} does not tile the output {tuple(self.shape[2:])}")
+        if want_p or want_i:
+            if self._src is None:
+                raise _lib.VitamdError(f"Frames: this batch was materialised by its loader and its source slot is reused; patch={patch}, "
+                                       f"image={image} was not asked of the loader")
+            patches, img = ops.frames_prep(self._src, self.shape[2:], self._table, patch if want_p else None, want_i, self._index, self._geom,
+                                           mix=self._mix)
+            if want_p:
+                self._patches[patch] = patches
+            if want_i:
+                self._image = img
+        return self
+
+
+class MixLoader(data.DeviceLoader):
+    """DeviceLoader that mixes: with train=True every batch is cut as DeviceLoader cuts it (the same crops and flips under the same
+    (seed, step)), mixed by `mix.draw(B, size, step)` with the loader's own step, and handed out as (MixedFrames, MixedLabels) with
+    b = labels[partner].  With train=False it is DeviceLoader.  host_iter must yield int64 labels [B].
+
+    The record crosses through `depth` pinned staging buffers with non_blocking copies on the current stream; a staging buffer is
+    rewritten only behind the event of the copy that last read it (recorded `depth` batches earlier), as the frame slots are."""
+
+    def __init__(self, host_iter, device, size, mix, **kwargs):
+        super().__init__(host_iter, device, size, **kwargs)
+        if not isinstance(mix, Mix):
+            raise ValueError(f"MixLoader: mix must be a vitamd.mix.Mix, got {type(mix).__name__}")
+        self.mix = mix
+        self._stage = [None] * self.depth
+        self._pair = None                  # (rec, lam) on the device, of the batch being handed out
+
+    def _staged(self, rec, lam):
+        """the host record -> the device, through the staging buffer of this step"""
+        B = rec.shape[0]
+        st = self._stage[self.step % self.depth]
+        if st is None or st["rec"].shape[0] < B:
+            st = {"rec": torch.zeros((B, 6), dtype=torch.int32).pin_memory(), "lam": torch.zeros((B,), dtype=torch.float32).pin_memory(),
+                  "done": torch.cuda.Event()}
+            self._stage[self.step % self.depth] = st
+        st["done"].synchronize()           # host: the copy that last read these buffers is over (no-op when never recorded)
+        st["rec"][:B].copy_(rec)
+        st["lam"][:B].copy_(lam)
+        rec_dev = st["rec"][:B].to(self.device, non_blocking=True)
+        lam_dev = st["lam"][:B].to(self.device, non_blocking=True)
+        st["done"].record(torch.cuda.current_stream(self.device))
+        return rec_dev, lam_dev
+
+    def _frames(self, src, geom, table):
+        if not self.train:
+            return super()._frames(src, geom, table)
+        self._pair = self._staged(*self.mix.draw(src.shape[0], self.out_hw, self.step))
+        return MixedFrames(src, self.out_hw, geom=geom, table=table, mix=self._pair)
+
+    def _labels(self, labels):
+        if not self.train:
+            return super()._labels(labels)
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() != 1:
+            raise ValueError("MixLoader: a mixed batch needs int64 labels [B] from host_iter")
+        rec, lam = self._pair
+        return MixedLabels(labels, labels[rec[:, 0].long()], lam)

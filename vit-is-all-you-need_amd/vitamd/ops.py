@@ -761,27 +761,55 @@ def _need_logits(logits, name="logits"):
     return logits.shape[0], logits.shape[1], logits.stride(0), int(logits.dtype == BF16)
 
 
-def cross_entropy_fwd(logits, target, ignore_index=-100):
+def _need_soft(soft, M):
+    """soft = (target_b int64 [M] or None, lam fp32 [M] or None, smoothing) of the soft-target entries -> the same, checked"""
+    if not (isinstance(soft, (tuple, list)) and len(soft) == 3):
+        raise ValueError("soft: expected (target_b or None, lam or None, smoothing)")
+    target_b, lam, smoothing = soft
+    smoothing = float(smoothing)
+    if not 0.0 <= smoothing <= 1.0:
+        raise ValueError(f"soft: smoothing must lie in [0, 1], got {smoothing!r}")
+    if lam is not None:
+        _need(lam, F32, "lam", 1); _need(target_b, torch.int64, "target_b", 1)
+        if lam.numel() != M or target_b.numel() != M:
+            raise _lib.VitamdError(f"soft: expected lam [{M}] and target_b [{M}]")
+    else:
+        target_b = None
+    return target_b, lam, smoothing
+
+
+def cross_entropy_fwd(logits, target, ignore_index=-100, soft=None):
     """Mean cross-entropy of logits fp32 / bf16 [M, V] (unit inner stride) against target int64 [M] over the rows whose target is not
     ignore_index, fp32 arithmetic -> (loss_row fp32 [M], lse fp32 [M], stats fp32 [2] = (mean loss, 1 / count)); semantics:
-    include/vitamd.h vitamd_cross_entropy_fwd.  Nothing synchronises: a target outside [0, V) shows as a NaN mean."""
+    include/vitamd.h vitamd_cross_entropy_fwd.  Nothing synchronises: a target outside [0, V) shows as a NaN mean.
+    soft = (target_b int64 [M] or None, lam fp32 [M] or None, smoothing): the soft-target loss of vitamd_soft_cross_entropy_fwd
+    instead (Mixup / CutMix pairs and label smoothing; the mean is over all rows, ignore_index is not looked at)."""
     M, V, ld, is_bf16 = _need_logits(logits)
     _need(target, torch.int64, "target", 1)
     if target.numel() != M:
         raise _lib.VitamdError(f"target: expected {M} elements, got {target.numel()}")
+    if soft is not None:
+        soft = _need_soft(soft, M)
     loss_row = torch.empty((M,), dtype=F32, device=logits.device)
     lse = torch.empty((M,), dtype=F32, device=logits.device)
     stats = torch.empty((2,), dtype=F32, device=logits.device)
+    if soft is not None:
+        _lib.check(_L().vitamd_soft_cross_entropy_fwd(_p(logits), is_bf16, _p(target), _p(soft[0]), _p(soft[1]), soft[2], _p(loss_row), _p(lse),
+                                                      _p(stats), M, V, ld, _stream()), f"soft_cross_entropy_fwd[M={M},V={V},ld={ld}]")
+        return loss_row, lse, stats
     _lib.check(_L().vitamd_cross_entropy_fwd(_p(logits), is_bf16, _p(target), _p(loss_row), _p(lse), _p(stats), M, V, ld, int(ignore_index),
                                              _stream()), f"cross_entropy_fwd[M={M},V={V},ld={ld}]")
     return loss_row, lse, stats
 
 
-def cross_entropy_bwd(logits, target, lse, stats, grad_out=None, ignore_index=-100, out=None, out_dtype=None):
+def cross_entropy_bwd(logits, target, lse, stats, grad_out=None, ignore_index=-100, out=None, out_dtype=None, soft=None):
     """dlogits = (softmax(logits) - onehot(target)) * grad_out / count from the forward's lse and stats; ignored rows are zeros.
     grad_out: device fp32 scalar (None = 1).  out: where to write (fp32 or bf16 [M, V], unit inner stride; `logits` itself = in place);
-    None allocates a dense tensor of out_dtype (default: the logits' dtype)."""
+    None allocates a dense tensor of out_dtype (default: the logits' dtype).  soft: as cross_entropy_fwd's (the forward's own): the
+    soft target takes the one-hot's place (vitamd_soft_cross_entropy_bwd)."""
     M, V, ld, is_bf16 = _need_logits(logits)
+    if soft is not None:
+        soft = _need_soft(soft, M)
     _need(target, torch.int64, "target", 1); _need(lse, F32, "lse", 1); _need(stats, F32, "stats", 1)
     if target.numel() != M or lse.numel() != M or stats.numel() != 2:
         raise _lib.VitamdError(f"cross_entropy_bwd: expected target [{M}], lse [{M}] and stats [2]")
@@ -796,6 +824,11 @@ def cross_entropy_bwd(logits, target, lse, stats, grad_out=None, ignore_index=-1
         raise _lib.VitamdError(f"out: expected [{M}, {V}], got {tuple(out.shape)}")
     if out.data_ptr() == logits.data_ptr() and (out_bf16 != is_bf16 or ldo != ld):
         raise _lib.VitamdError("cross_entropy_bwd: in place needs the logits' own dtype and stride")
+    if soft is not None:
+        _lib.check(_L().vitamd_soft_cross_entropy_bwd(_p(logits), is_bf16, _p(target), _p(soft[0]), _p(soft[1]), soft[2], _p(lse), _p(stats),
+                                                      _p(grad_out), _p(out), out_bf16, M, V, ld, ldo, _stream()),
+                   f"soft_cross_entropy_bwd[M={M},V={V},ld={ld},ldo={ldo}]")
+        return out
     _lib.check(_L().vitamd_cross_entropy_bwd(_p(logits), is_bf16, _p(target), _p(lse), _p(stats), _p(grad_out), _p(out), out_bf16, M, V, ld,
                                              ldo, int(ignore_index), _stream()), f"cross_entropy_bwd[M={M},V={V},ld={ld},ldo={ldo}]")
     return out
@@ -1235,10 +1268,11 @@ def check_frames(src_shape, out_hw, patch=None, B=None, has_index=False):
     return B, Nsrc, Hs, Ws, C, H, W
 
 
-def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=None):
+def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=None, mix=None):
     """uint8 frames [Nsrc, Hs, Ws, C] -> (patch rows bf16 [B*gh*gw, C*p*p] or None, image fp32 [B, C, H, W] or None) in one launch
     (semantics, clamps and refusals: include/vitamd.h vitamd_frames_prep).  index int64 [B] or None, geom int32 [B, 3] or None,
-    table fp32 [C, 256], all on the device of src."""
+    table fp32 [C, 256], all on the device of src.  mix = (rec int32 [B, 6], lam fp32 [B] or None) on that device: Mixup / CutMix on the
+    way (vitamd_frames_prep_mix; lam None promises that no row of rec has mode 1)."""
     if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
         raise ValueError(f"frames_prep: src must be a uint8 tensor, got {getattr(src, 'dtype', type(src).__name__)}")
     if patch is None and not image:
@@ -1255,8 +1289,24 @@ def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=Non
         _need(geom, torch.int32, "geom", 2)
         if tuple(geom.shape) != (B, 3):
             raise _lib.VitamdError(f"geom: expected [{B}, 3], got {tuple(geom.shape)}")
+    if mix is not None:
+        if not (isinstance(mix, (tuple, list)) and len(mix) == 2):
+            raise ValueError("frames_prep: mix must be (rec int32 [B, 6], lam fp32 [B] or None)")
+        rec, lam = mix
+        _need(rec, torch.int32, "rec", 2)
+        if tuple(rec.shape) != (B, 6):
+            raise _lib.VitamdError(f"rec: expected [{B}, 6], got {tuple(rec.shape)}")
+        if lam is not None:
+            _need(lam, F32, "lam", 1)
+            if lam.numel() != B:
+                raise _lib.VitamdError(f"lam: expected [{B}], got {tuple(lam.shape)}")
     patches = torch.empty((B * (H // patch) * (W // patch), C * patch * patch), dtype=BF16, device=src.device) if patch is not None else None
     img = torch.empty((B, C, H, W), dtype=F32, device=src.device) if image else None
+    if mix is not None:
+        _lib.check(_L().vitamd_frames_prep_mix(_p(src), _p(index), _p(geom), _p(table), _p(patches), _p(img), B, Nsrc, Hs, Ws, C, H, W,
+                                               patch if patch is not None else 0, _p(mix[0]), _p(mix[1]), _stream()),
+                   f"frames_prep_mix[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
+        return patches, img
     _lib.check(_L().vitamd_frames_prep(_p(src), _p(index), _p(geom), _p(table), _p(patches), _p(img), B, Nsrc, Hs, Ws, C, H, W,
                                        patch if patch is not None else 0, _stream()),
                f"frames_prep[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
