@@ -403,8 +403,8 @@ int vitamd_assemble_tokens_grid_cap(void);
  * table, both outputs NULL.  Nothing is launched in either case.  The grid is capped at vitamd_frames_prep_grid_cap() workgroups of
  * 256 lanes with a stride loop beyond (a lane owns 4 pixels x 3 channels in the fast form, one element in the generic one).
  * Only enqueues on `stream`; no backward (a uint8 input takes no gradient).
- * replaces the CPU-side transforms of the reference's loaders (datasets.py: ToTensor, Normalize, crop, flip; Resize stays on the
- * CPU workers) and vitamd_im2col_bf16's read of the fp32 image. */
+ * replaces the CPU-side transforms of the reference's loaders (datasets.py: ToTensor, Normalize, crop, flip; with a Resize in
+ * front: vitamd_frames_prep_resize) and vitamd_im2col_bf16's read of the fp32 image. */
 int vitamd_frames_prep(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16,
                        float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, void* stream);
 int vitamd_frames_prep_grid_cap(void);
@@ -428,6 +428,38 @@ int vitamd_frames_prep_grid_cap(void);
 int vitamd_frames_prep_mix(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16,
                            float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, const int* rec, const float* lam,
                            void* stream);
+/* vitamd_frames_prep with an antialiased bilinear resize in front of the crop.  src, index, the two outputs and
+ * their layouts as vitamd_frames_prep.  box int32 [B, 10] on the device holds per output sample
+ *   (y0, h, Hv, oy,  x0, w, Wv, ox,  flip, 0)
+ * The rectangle [y0, y0+h) x [x0, x0+w) of frame index[b] is resized (bilinear, antialiased, align_corners = false) to a virtual
+ * image Hv x Wv; the output H x W is the window of that image at (oy, ox), mirrored under a flip (out[x] = window[W-1-x]).
+ * RandomResizedCrop: the box is the drawn crop, Hv = H, Wv = W, oy = ox = 0.  Resize(S) + crop: the box is the frame (its valid
+ * extent inside a padded canvas), (Hv, Wv) the resized size, (oy, ox) the crop offset.
+ * WEIGHTS, in integers, per axis (y shown): S = max(h, Hv); for output row o, u = 2 (o + oy) + 1; for box-relative tap j in [0, h)
+ *   n_j = max(0, 2S - |(2j+1) Hv - u h|),   wy_j = n_j / sum_j n_j
+ * the triangle filter of support max(h / Hv, 1) about (o + oy + 0.5) h / Hv, clipped to the box and renormalised: the weights of
+ * F.interpolate(mode="bilinear", antialias=True, align_corners=False) on the cropped box.  n_j and their sum are exact in fp32.
+ * VALUES: r = sum_j wy_j sum_i wx_i src[index[b], y0+j, x0+i, c] in fp32 (0..255), then
+ *   image = fl(fl(fl(r / 255) - mean[c]) / std[c])       three separately rounded fp32 operations with true division
+ * mean, std fp32 [C] on the device, both or neither (NULL: image = fl(r / 255)).  patches_bf16 is the round-to-nearest-even of image
+ * in vitamd_im2col_bf16's layout.  A record with h = Hv = H and w = Wv = W has one tap of weight 1 per value: the bits of
+ * vitamd_frames_prep with geom (y0 + oy, x0 + ox, flip) and the table of those mean and std.
+ * Down-scaling is limited to 8x per axis (at most 16 taps); up-scaling is not limited.  Either output may be NULL, not both; the fast
+ * form (separable through LDS, a 32 x 32 output tile per workgroup) needs C == 3, W % 4 == 0, p % 4 == 0 and the alignments of
+ * vitamd_frames_prep, anything else takes one lane per output element.  No atomics: the same bits on every call.
+ * CLAMPS, before any address forms: index into [0, Nsrc); y0 into [0, Hs-1] and h into [1, Hs-y0]; Hv into [max(H, ceil(h / 8)), 8192];
+ * oy into [0, Hv-H]; x0, w, Wv, ox alike; any non-zero flip counts as 1.  No device-side value can make the kernel read outside src
+ * or run more than 16 taps per axis.
+ * VITAMD_ERR_SHAPE (answered first): B, Nsrc, Hs, Ws, H, W < 1; C outside 1..4; Hs, Ws, H or W > 8192; NULL index with Nsrc < B; with
+ * patches_bf16 given p < 1, H % p != 0 or W % p != 0; Nsrc*Hs*Ws*C or B*C*H*W beyond 2^40 elements.  VITAMD_ERR_ARG: NULL src, NULL
+ * box, one of mean / std without the other, both outputs NULL.  Nothing is launched in either case.  H > Hs and W > Ws are legal.
+ * The grid is capped at vitamd_frames_prep_resize_grid_cap() workgroups with a stride loop beyond (over tiles, or over elements).
+ * Only enqueues on `stream`; no backward.
+ * replaces the Resize / RandomResizedCrop of the reference's loaders (datasets.py: Resize(image_size) in front of RandomCrop; timm's
+ * RandomResizedCrop in the DeiT recipe) on the CPU workers, and the host-side scaling of raw video frames to the tokenizer's size. */
+int vitamd_frames_prep_resize(const unsigned char* src, const long long* index, const int* box, const float* mean, const float* std,
+                              void* patches_bf16, float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, void* stream);
+int vitamd_frames_prep_resize_grid_cap(void);
 /* Fills geom int32 [B, 3] on the device for vitamd_frames_prep.  Sample b takes the words w0, w1, w2 of Philox4x32-10 with key
  * (seed low, seed high) and counter (b, 1, step low, step high) - c1 = 1 keeps it off vitamd_sample_logits' stream, which uses c1 = 0:
  *   y0 = (w0 * (Hs-H+1)) >> 32     x0 = (w1 * (Ws-W+1)) >> 32     flip = flip_enabled ? w2 >> 31 : 0       (64-bit products)

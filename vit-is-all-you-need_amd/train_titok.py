@@ -185,6 +185,9 @@ def add_common_args(p):
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
     p.add_argument("--u8", action="store_true",
                    help="feed seeded random uint8 frames through vitamd.data.DeviceLoader (the device input pipeline) instead of one fp32 batch")
+    p.add_argument("--resize", type=int, default=None, metavar="S",
+                   help="with --u8: the frames come at 3/2 by 2 times the image size (192 x 256 for 128) and are resized on the device, shorter "
+                        "side to S, then centre-cropped (vitamd.resize.ResizeLoader)")
     p.add_argument("--perceptual_weight", type=float, default=0.0,
                    help="weight of the ConvNeXt-S perceptual term (reference train_titok.py:155-158); 0 = no perceptual term")
     p.add_argument("--perceptual_weights", type=str, default=None,
@@ -229,8 +232,14 @@ def run(model, args, codebook_size):
     feed = None
     if getattr(args, "u8", False):
         from vitamd.data import DeviceLoader
-        u8 = torch.randint(0, 256, (args.bs, args.image_size, args.image_size, 3), generator=g, dtype=torch.uint8)
-        feed = DeviceLoader(((u8, None) for _ in range(args.train_steps)), dev, args.image_size, patch=args.patch_size, train=False)
+        if getattr(args, "resize", None) is not None:
+            from vitamd.resize import ResizeLoader
+            u8 = torch.randint(0, 256, (args.bs, args.image_size * 3 // 2, args.image_size * 2, 3), generator=g, dtype=torch.uint8)
+            feed = ResizeLoader(((u8, None) for _ in range(args.train_steps)), dev, args.image_size, mode="resize_crop", resize_to=args.resize,
+                                patch=args.patch_size, train=False)
+        else:
+            u8 = torch.randint(0, 256, (args.bs, args.image_size, args.image_size, 3), generator=g, dtype=torch.uint8)
+            feed = DeviceLoader(((u8, None) for _ in range(args.train_steps)), dev, args.image_size, patch=args.patch_size, train=False)
     for step in range(args.train_steps):
         t0 = time.time()
         if feed is not None:
@@ -245,6 +254,8 @@ def run(model, args, codebook_size):
 
 def main():
     args = parse_args()
+    if args.resize is not None and not args.u8:
+        raise SystemExit("--resize resizes inside the device input feed (vitamd.resize.ResizeLoader): it needs --u8")
     cfg = TiTokConfig(args.image_size, args.patch_size, args.latent_tokens, args.codebook_size, args.latent_dim, args.transformer)
     run(TiTok(cfg), args, cfg.codebook_size)
 

@@ -195,11 +195,13 @@ class VideoGPT(nn.Module):
 
 
 @torch.no_grad()
-def frames_to_tokens(tokenizer, videos, index=None):
+def frames_to_tokens(tokenizer, videos, index=None, size=None):
     """videos [B, T, 3, H, W] -> code ids int64 [B, T, N] (train_videogpt.py:122-127): every frame through tokenizer.encode, in eval mode
     and without a graph; the tokenizer's training flag is put back.  videos may also be raw uint8 [B, T, H, W, C] on the device (what the
     reference's video sets hold): they go through vitamd.data.Frames, scaled to [0, 1].  index (uint8 videos only): int64 [B, T'] of
-    frame numbers into the flattened [B*T] frames - the window videos[:, offset:offset+T'] without a copy -> ids [B, T', N]"""
+    frame numbers into the flattened [B*T] frames - the window videos[:, offset:offset+T'] without a copy -> ids [B, T', N].  size (uint8
+    videos only; an int or (H, W)): the tokenizer's frame size where the videos have another - the shorter side is resized to the shorter
+    side of `size` (antialiased bilinear) and the centre is cropped, inside the same launch (vitamd.resize.ResizedFrames)"""
     if videos.dim() != 5:
         raise ValueError(f"frames_to_tokens: expected videos [B, T, C, H, W] or uint8 [B, T, H, W, C], got {tuple(videos.shape)}")
     B, T = videos.shape[:2]
@@ -209,9 +211,15 @@ def frames_to_tokens(tokenizer, videos, index=None):
                 raise ValueError(f"frames_to_tokens: index must be int64 [{B}, T'], got {tuple(index.shape)}")
             T = index.shape[1]
             index = index.reshape(-1)
-        frames = data.Frames(videos, tuple(videos.shape[2:4]), index=index)
-    elif index is not None:
-        raise ValueError("frames_to_tokens: index goes with uint8 videos; slice a float tensor instead")
+        if size is not None and data._hw(size) != tuple(videos.shape[2:4]):
+            from vitamd import resize
+            out_hw = data._hw(size)
+            box = resize.resize_center_boxes(B * T, tuple(videos.shape[2:4]), min(out_hw), out_hw)
+            frames = resize.ResizedFrames(videos, out_hw, box, index=index)
+        else:
+            frames = data.Frames(videos, tuple(videos.shape[2:4]), index=index)
+    elif index is not None or size is not None:
+        raise ValueError("frames_to_tokens: index and size go with uint8 videos; slice or resize a float tensor instead")
     else:
         frames = videos.reshape(B * T, *videos.shape[2:])
     was_training = getattr(tokenizer, "training", False)

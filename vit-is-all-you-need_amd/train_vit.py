@@ -89,6 +89,14 @@ def parse_args(argv=None):
     p.add_argument("--train_steps", type=int, default=50)
     p.add_argument("--u8", action="store_true",
                    help="feed seeded random uint8 frames through vitamd.data.DeviceLoader (the device input pipeline: random crop and flip, ImageNet normalisation) instead of one fp32 batch")
+    p.add_argument("--rrc", action="store_true",
+                   help="with --u8: RandomResizedCrop on the device (vitamd.resize.ResizeLoader, mode rrc) from frames of --src_size")
+    p.add_argument("--rrc_scale", type=float, nargs=2, default=(0.08, 1.0), metavar=("LO", "HI"), help="the area range of --rrc")
+    p.add_argument("--resize", type=int, default=None, metavar="S",
+                   help="with --u8 and without --rrc: the reference's transform Resize(S) -> RandomCrop(image_size) -> flip on the device "
+                        "(vitamd.resize.ResizeLoader, mode resize_crop) from frames of --src_size")
+    p.add_argument("--src_size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                   help="the size of the seeded random source frames of --rrc / --resize (default: a non-square 8 : 7 frame, 320 x 280 at 224)")
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
     p.add_argument("--dropout", type=float, default=0.0)
@@ -124,6 +132,13 @@ def main(argv=None):
         raise SystemExit("--mixup / --cutmix mix inside the device input feed (vitamd.mix.MixLoader): they need --u8")
     if args.graph and args.label_smoothing > 0:
         raise SystemExit("--graph with --label_smoothing: the graphed step is built on the hard-label loss - use one or the other")
+    resizing = args.rrc or args.resize is not None
+    if resizing and not args.u8:
+        raise SystemExit("--rrc / --resize resize inside the device input feed (vitamd.resize.ResizeLoader): they need --u8")
+    if resizing and mixing:
+        raise SystemExit("--rrc / --resize with --mixup / --cutmix: mixing resized samples in one launch is not built - use one or the other")
+    if args.src_size is not None and not resizing:
+        raise SystemExit("--src_size goes with --rrc or --resize")
     dev = torch.device("cuda")
     cfg = ViTConfig(args.image_size, 3, args.patch_size, args.transformer, args.extra_tokens, args.dropout)
     model = ViTClassifier(cfg, args.num_classes).to(dev)
@@ -136,10 +151,17 @@ def main(argv=None):
     if args.u8:
         from vitamd.data import IMAGENET_MEAN, IMAGENET_STD, DeviceLoader
         side = args.image_size + args.image_size // 7           # 256 for 224: the frame the random crop is taken from
-        u8 = torch.randint(0, 256, (args.bs, side, side, 3), generator=g, dtype=torch.uint8)
+        src_hw = (side, side)
+        if resizing:                                            # a non-square frame of another size: 320 x 280 for 224
+            src_hw = tuple(args.src_size) if args.src_size is not None else (args.image_size * 10 // 7, args.image_size * 5 // 4)
+        u8 = torch.randint(0, 256, (args.bs, *src_hw, 3), generator=g, dtype=torch.uint8)
         host_labels = labels.cpu()
         host = ((u8, host_labels) for _ in range(args.train_steps))
-        if mixing:
+        if resizing:
+            from vitamd.resize import ResizeLoader
+            feed = ResizeLoader(host, dev, args.image_size, mode="rrc" if args.rrc else "resize_crop", scale=tuple(args.rrc_scale),
+                                resize_to=args.resize, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)
+        elif mixing:
             from vitamd.mix import Mix, MixLoader
             mix = Mix(args.mixup, args.cutmix, args.mix_prob, args.mix_switch_prob, label_smoothing=args.label_smoothing, seed=0)
             feed = MixLoader(host, dev, args.image_size, mix, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)

@@ -7,8 +7,8 @@ image the tokenizers' losses take as their target, in one kernel launch (csrc/in
     for frames, labels in DeviceLoader(host_iter, "cuda", 224, patch=16): ...
 
 Frame gather, crop and flip are an index map and the value arithmetic is a table built on the CPU with torch's own ops, so what comes out
-equals torchvision's ToTensor / Normalize / crop / flip bit for bit.  Resizing is NOT here: the reference resizes per image, from varying
-source sizes, in its CPU workers, and that stays there.  No backward: a uint8 input takes no gradient."""
+equals torchvision's ToTensor / Normalize / crop / flip bit for bit.  Resizing is NOT in this module: frames of another size go through
+vitamd.resize (ResizedFrames, ResizeLoader).  No backward: a uint8 input takes no gradient."""
 from __future__ import annotations
 
 import torch
@@ -265,10 +265,7 @@ class DeviceLoader:
         src = s["dev"][:n]
         src_hw = tuple(src.shape[1:3])
         with torch.cuda.device(self.device):
-            if self.train:
-                geom = random_geom(n, src_hw, self.out_hw, self.seed, self.step, flip=True, device=self.device)
-            else:
-                geom = center_geom(n, src_hw, self.out_hw).to(self.device)
+            geom = self._geom(n, src_hw)
             table = norm_table(self.mean, self.std, channels=src.shape[3], device=self.device)
             frames = self._frames(src, geom, table).materialise(self.patch, self.image).release_source()
             labels = self._labels(labels)
@@ -285,3 +282,10 @@ class DeviceLoader:
     def _labels(self, labels):
         """what is handed out beside the frames: the labels on the device as they came (or None)"""
         return labels
+
+    def _geom(self, n, src_hw):
+        """(y0, x0, flip) of this step's n samples, on the device: random crop + flip under (seed, step) for train=True, centred and
+        unflipped otherwise (vitamd.resize.ResizeLoader, whose record carries the crop, overrides it)"""
+        if self.train:
+            return random_geom(n, src_hw, self.out_hw, self.seed, self.step, flip=True, device=self.device)
+        return center_geom(n, src_hw, self.out_hw).to(self.device)

@@ -157,6 +157,8 @@ class MixLoader(data.DeviceLoader):
     rewritten only behind the event of the copy that last read it (recorded `depth` batches earlier), as the frame slots are."""
 
     def __init__(self, host_iter, device, size, mix, **kwargs):
+        if any(k in kwargs for k in ("mode", "scale", "ratio", "resize_to")):
+            raise ValueError("MixLoader: mixing resized samples in one launch is not built (vitamd.resize.ResizeLoader resizes, without mixing)")
         super().__init__(host_iter, device, size, **kwargs)
         if not isinstance(mix, Mix):
             raise ValueError(f"MixLoader: mix must be a vitamd.mix.Mix, got {type(mix).__name__}")

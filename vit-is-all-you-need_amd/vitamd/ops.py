@@ -1249,8 +1249,17 @@ def frames_prep_grid_cap():
     return int(_L().vitamd_frames_prep_grid_cap())
 
 
-def check_frames(src_shape, out_hw, patch=None, B=None, has_index=False):
+def frames_prep_resize_grid_cap():
+    """workgroups one launch of the resizing frame kernels has at most (asked of the library); more tiles make them loop"""
+    return int(_L().vitamd_frames_prep_resize_grid_cap())
+
+
+FRAMES_MAX_SIZE = 8192      # of Hs, Ws, H, W where the kernel resizes (include/vitamd.h vitamd_frames_prep_resize)
+
+
+def check_frames(src_shape, out_hw, patch=None, B=None, has_index=False, resize=False):
     """The shape rules of vitamd_frames_prep as ValueError, without looking at a device: src [Nsrc, Hs, Ws, C] -> B samples of out_hw.
+    resize=True: those of vitamd_frames_prep_resize (the output may be larger than the source; no size beyond 8192).
     -> (B, Nsrc, Hs, Ws, C, H, W)"""
     if len(src_shape) != 4:
         raise ValueError(f"frames: expected uint8 [N, Hs, Ws, C] (channels last), got shape {tuple(src_shape)}")
@@ -1259,7 +1268,10 @@ def check_frames(src_shape, out_hw, patch=None, B=None, has_index=False):
     B = Nsrc if B is None else int(B)
     if min(B, Nsrc, Hs, Ws, H, W) < 1 or not 1 <= C <= 4:
         raise ValueError(f"frames: every size must be >= 1 and C in 1..4, got src {tuple(src_shape)}, out {(H, W)}, B {B}")
-    if H > Hs or W > Ws:
+    if resize:
+        if max(Hs, Ws, H, W) > FRAMES_MAX_SIZE:
+            raise ValueError(f"frames: the resizing kernel takes sizes up to {FRAMES_MAX_SIZE}, got src {(Hs, Ws)}, out {(H, W)}")
+    elif H > Hs or W > Ws:
         raise ValueError(f"frames: the output {(H, W)} does not fit the source {(Hs, Ws)} (resizing stays with the host loader)")
     if not has_index and Nsrc < B:
         raise ValueError(f"frames: {B} samples need {B} source frames or an index, got {Nsrc}")
@@ -1268,21 +1280,44 @@ def check_frames(src_shape, out_hw, patch=None, B=None, has_index=False):
     return B, Nsrc, Hs, Ws, C, H, W
 
 
-def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=None, mix=None):
+def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=None, mix=None, resize=None):
     """uint8 frames [Nsrc, Hs, Ws, C] -> (patch rows bf16 [B*gh*gw, C*p*p] or None, image fp32 [B, C, H, W] or None) in one launch
     (semantics, clamps and refusals: include/vitamd.h vitamd_frames_prep).  index int64 [B] or None, geom int32 [B, 3] or None,
     table fp32 [C, 256], all on the device of src.  mix = (rec int32 [B, 6], lam fp32 [B] or None) on that device: Mixup / CutMix on the
-    way (vitamd_frames_prep_mix; lam None promises that no row of rec has mode 1)."""
+    way (vitamd_frames_prep_mix; lam None promises that no row of rec has mode 1).  resize = (box int32 [B, 10], mean fp32 [C] or None,
+    std fp32 [C] or None) on that device: the antialiased bilinear resize of vitamd_frames_prep_resize in front of the crop; the record
+    carries the crop and the flip and mean / std stand where the table stood, so table and geom must be None, and mix is refused."""
+    if resize is not None and mix is not None:
+        raise ValueError("frames_prep: give mix or resize, not both (mixing resized samples in one launch is not built)")
     if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
         raise ValueError(f"frames_prep: src must be a uint8 tensor, got {getattr(src, 'dtype', type(src).__name__)}")
     if patch is None and not image:
         raise ValueError("frames_prep: nothing to write (give a patch size, image=True, or both)")
     if index is not None and (not isinstance(index, torch.Tensor) or index.dim() != 1 or index.numel() < 1):
         raise ValueError("frames_prep: index must be a 1-d int64 tensor with one entry per output sample")
-    B, Nsrc, Hs, Ws, C, H, W = check_frames(src.shape, out_hw, patch, None if index is None else index.numel(), index is not None)
-    _need(src, torch.uint8, "src", 4); _need(table, F32, "table", 2)
-    if tuple(table.shape) != (C, 256):
-        raise _lib.VitamdError(f"table: expected [{C}, 256], got {tuple(table.shape)}")
+    if resize is not None:
+        if not (isinstance(resize, (tuple, list)) and len(resize) == 3):
+            raise ValueError("frames_prep: resize must be (box int32 [B, 10], mean fp32 [C] or None, std fp32 [C] or None)")
+        if (resize[1] is None) != (resize[2] is None):
+            raise ValueError("frames_prep: give mean and std together, or neither")
+        if table is not None or geom is not None:
+            raise ValueError("frames_prep: with resize= the record carries crop and flip and (mean, std) the normalisation: table and geom must be None")
+    B, Nsrc, Hs, Ws, C, H, W = check_frames(src.shape, out_hw, patch, None if index is None else index.numel(), index is not None,
+                                            resize=resize is not None)
+    _need(src, torch.uint8, "src", 4)
+    if resize is None:
+        _need(table, F32, "table", 2)
+        if tuple(table.shape) != (C, 256):
+            raise _lib.VitamdError(f"table: expected [{C}, 256], got {tuple(table.shape)}")
+    else:
+        _need(resize[0], torch.int32, "box", 2)
+        if tuple(resize[0].shape) != (B, 10):
+            raise _lib.VitamdError(f"box: expected [{B}, 10], got {tuple(resize[0].shape)}")
+        for name, v in (("mean", resize[1]), ("std", resize[2])):
+            if v is not None:
+                _need(v, F32, name, 1)
+                if v.numel() != C:
+                    raise _lib.VitamdError(f"{name}: expected [{C}], got {tuple(v.shape)}")
     if index is not None:
         _need(index, torch.int64, "index", 1)
     if geom is not None:
@@ -1302,6 +1337,11 @@ def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=Non
                 raise _lib.VitamdError(f"lam: expected [{B}], got {tuple(lam.shape)}")
     patches = torch.empty((B * (H // patch) * (W // patch), C * patch * patch), dtype=BF16, device=src.device) if patch is not None else None
     img = torch.empty((B, C, H, W), dtype=F32, device=src.device) if image else None
+    if resize is not None:
+        _lib.check(_L().vitamd_frames_prep_resize(_p(src), _p(index), _p(resize[0]), _p(resize[1]), _p(resize[2]), _p(patches), _p(img), B, Nsrc,
+                                                  Hs, Ws, C, H, W, patch if patch is not None else 0, _stream()),
+                   f"frames_prep_resize[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
+        return patches, img
     if mix is not None:
         _lib.check(_L().vitamd_frames_prep_mix(_p(src), _p(index), _p(geom), _p(table), _p(patches), _p(img), B, Nsrc, Hs, Ws, C, H, W,
                                                patch if patch is not None else 0, _p(mix[0]), _p(mix[1]), _stream()),
