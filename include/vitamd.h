@@ -460,6 +460,28 @@ int vitamd_frames_prep_mix(const unsigned char* src, const long long* index, con
 int vitamd_frames_prep_resize(const unsigned char* src, const long long* index, const int* box, const float* mean, const float* std,
                               void* patches_bf16, float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, void* stream);
 int vitamd_frames_prep_resize_grid_cap(void);
+/* vitamd_frames_prep_resize with Mixup / CutMix applied on the way: every argument of vitamd_frames_prep_resize,
+ * then rec int32 [B, 6] = (partner, mode, yl, yh, xl, xh) per output sample and lam fp32 [B] as vitamd_frames_prep_mix takes them.
+ * With R_j the fp32 image vitamd_frames_prep_resize gives for sample j - cut with ITS OWN index[j] and box[j] (crop, scale, flip) and
+ * already normalised - output sample b with q = partner[b] is
+ *   mode 0, q == b, or a mode outside {1, 2}:  R_b                          (the bits of vitamd_frames_prep_resize)
+ *   mode 1 (Mixup):     fl(fl(R_b * l) + fl(R_q * m)),  l = lam[b], m = fl(1 - l)       three separately rounded fp32 operations,
+ *                       never a fused multiply-add: bit-equal to torch's CPU a.mul(l).add(p.mul(1 - l)) of the two stand-alone images
+ *   mode 2 (CutMix):    R_q where yl <= y < yh and xl <= x < xh, else R_b; lam is not read
+ * image holds that fp32 value, patches_bf16 its round-to-nearest-even in vitamd_im2col_bf16's layout.  Either output may be NULL, not both.
+ * Fast form (the conditions of vitamd_frames_prep_resize's): the workgroup of a 32 x 32 tile of sample b runs the separable pass for b
+ * and, where the tile takes pixels of q (every tile under mode 1; the tiles that meet the box under mode 2), a second pass with q's
+ * record on the same LDS; a mode-2 tile wholly inside the box runs q's pass alone.  Each pass adds in the order of the plain kernel, so
+ * R_b and R_q carry the bits of a stand-alone launch.  Generic form: one lane per element, the partner's taps only where the pixel
+ * takes them.  No atomics: the same bits on every call.
+ * CLAMPS, before any address forms: those of vitamd_frames_prep_resize on both samples' records; partner into [0, B); yl, yh into
+ * [0, H] and xl, xh into [0, W].  lam may be NULL only if the caller promises that no row has mode 1: a NULL lam is taken as l = 1.
+ * Refusals as vitamd_frames_prep_resize; NULL rec: VITAMD_ERR_ARG.  Nothing is launched on a refusal.  Grid cap:
+ * vitamd_frames_prep_resize_grid_cap().  Only enqueues on `stream`; no backward.
+ * replaces timm's RandomResizedCrop on the CPU workers followed by its Mixup on the fp32 batch and the im2col behind it (the DeiT recipe). */
+int vitamd_frames_prep_resize_mix(const unsigned char* src, const long long* index, const int* box, const float* mean, const float* std,
+                                  void* patches_bf16, float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p,
+                                  const int* rec, const float* lam, void* stream);
 /* Fills geom int32 [B, 3] on the device for vitamd_frames_prep.  Sample b takes the words w0, w1, w2 of Philox4x32-10 with key
  * (seed low, seed high) and counter (b, 1, step low, step high) - c1 = 1 keeps it off vitamd_sample_logits' stream, which uses c1 = 0:
  *   y0 = (w0 * (Hs-H+1)) >> 32     x0 = (w1 * (Ws-W+1)) >> 32     flip = flip_enabled ? w2 >> 31 : 0       (64-bit products)

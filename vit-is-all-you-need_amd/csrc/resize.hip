@@ -14,9 +14,15 @@
 // LDS: strip 80 x 3 x 32 x 4 = 30 720 B + taps 4 608 B: four workgroups per CU.  At the 8x cap a 32-row tile needs (32 + 1) x 8 = 264
 // source rows = four chunks; at the 1.1 - 2.3x of a training crop one.
 // Generic form (any other C, W, p or alignment): one lane per output element, both tap loops in the lane.
+// Mixing (vitamd_frames_prep_resize_mix): the same kernels with MIX = true.  In the fast form the workgroup that
+// owns a tile of sample b runs the separable pass for b and, where the tile takes pixels of the partner q (Mixup: always; CutMix: where
+// the tile meets the box), a second time with q's record - its own taps and strip chunks on the SAME LDS, behind the barrier at the head
+// of tile_pass - then normalises both accumulators and blends or selects per pixel.  A pass keeps its order of additions, so both
+// images carry the bits of a stand-alone launch.  The generic form evaluates the partner's taps only where the pixel takes them.
 // No atomics and a fixed order of additions: the same bits on every call.
 // Every device-side value is clamped before it forms an address (box_of), and no tap loop runs past MAX_TAPS.
 #include "common.h"
+#include "mix_row.h"
 #include "../../include/vitamd.h"
 
 namespace {
@@ -168,11 +174,73 @@ __device__ __forceinline__ void hpass_bytes(const unsigned char* col, int Ws, in
   }
 }
 
+// One separable pass: tile (ty, tx) of the sample cut with record bx -> acc, the lane's 4 neighbouring pixels x 3 channels on the
+// 0..255 scale.  Called by every lane of the workgroup (it holds barriers).  The FIRST barrier is the one that lets a pass follow
+// another on the same LDS: the taps and the strip are rewritten only once every lane has left the previous pass's last vertical
+// accumulation (the previous tile's, or - in the mixing kernel - the receiver's pass of this tile).  After it, taps -> barrier ->
+// per chunk (barrier between chunks) horizontal pass -> barrier -> vertical accumulation, in ascending tap order across the chunks.
+__device__ __forceinline__ void tile_pass(const unsigned char* __restrict__ src, const Box bx, size_t src_bytes, bool dwords, int Ws, int H, int W,
+                                          int ty, int tx, float (&strip)[STRIP_ROWS][3][TW], float (&wx)[MAX_TAPS][TW], float (&wy)[MAX_TAPS][TH],
+                                          int (&xj0)[TW], int (&xnt)[TW], int (&yj0)[TH], int (&ynt)[TH], f32x4 (&acc)[3]) {
+  const int tid = threadIdx.x;
+  const int hx = tid % TW, hr = tid / TW;            // horizontal pass: tile column, first row of the walk
+  const int vo = tid / (TW / 4), vg = tid % (TW / 4);   // vertical pass: tile row, group of 4 columns
+  __syncthreads();                                   // the previous pass's readers of the taps and the strip are done
+  if (tid < TW) {                                    // wave 0: the x-taps of tile column tid
+    const int x = tx * TW + tid;
+    Taps tp = {0, 0, 0, 0, 1};
+    if (x < W) tp = taps_of((bx.flip ? W - 1 - x : x) + bx.ox, bx.w, bx.Wv);
+    const float sum = numer_sum(tp);
+    for (int k = 0; k < MAX_TAPS; ++k) wx[k][tid] = k < tp.nt ? __fdiv_rn(numer(tp, k), sum) : 0.f;
+    xj0[tid] = tp.j0;
+    xnt[tid] = tp.nt;
+  } else if (tid >= 64 && tid < 64 + TH) {           // wave 1: the y-taps of tile row tid - 64
+    const int r = tid - 64, y = ty * TH + r;
+    Taps tp = {0, 0, 0, 0, 1};
+    if (y < H) tp = taps_of(y + bx.oy, bx.h, bx.Hv);
+    const float sum = numer_sum(tp);
+    for (int k = 0; k < MAX_TAPS; ++k) wy[k][r] = k < tp.nt ? __fdiv_rn(numer(tp, k), sum) : 0.f;
+    yj0[r] = tp.j0;
+    ynt[r] = tp.nt;
+  }
+  __syncthreads();
+  const int rows = min(TH, H - ty * TH);             // first and last tap are monotone in the output row
+  const int ylo = yj0[0], yhi = yj0[rows - 1] + ynt[rows - 1];
+  const int nx = xnt[hx], my_j0 = yj0[vo], my_nt = ynt[vo];
+  const int nt_max = (2 * max(bx.w, bx.Wv) + bx.Wv - 1) / bx.Wv;       // ceil(2S / Wv): no column of this sample has more taps
+  const unsigned char* col = bx.frame + ((size_t)bx.y0 * Ws + bx.x0 + xj0[hx]) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int cs = ylo; cs < yhi; cs += STRIP_ROWS) {
+    const int ce = min(cs + STRIP_ROWS, yhi);
+    if (cs != ylo) __syncthreads();                  // the previous chunk's vertical pass is done with the strip
+    if (nt_max <= 4) hpass<4>(src, col, src_bytes, dwords, Ws, cs, ce, hr, hx, nx, wx, strip);
+    else if (nt_max <= 8) hpass<8>(src, col, src_bytes, dwords, Ws, cs, ce, hr, hx, nx, wx, strip);
+    else hpass_bytes(col, Ws, cs, ce, hr, hx, nx, wx, strip);
+    __syncthreads();
+    const int k0 = max(cs - my_j0, 0), k1 = min(ce - my_j0, my_nt);
+    for (int k = k0; k < k1; ++k) {
+      const float wgt = wy[k][vo];
+      const int r = my_j0 + k - cs;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += wgt * *(const f32x4*)&strip[r][c][4 * vg];
+    }
+  }
+}
+
+// MIX: vitamd_frames_prep_resize_mix.  The workgroup runs the pass for the receiver b and, where the tile takes any of the partner's
+// pixels (every tile of a mode-1 sample, the tiles of a mode-2 sample that meet its box), a second pass with q's record on the SAME
+// LDS - its own taps, nt_max and strip chunks; tile_pass's first barrier keeps it off the first pass's readers.  A mode-2 tile that
+// lies wholly inside the box takes nothing of b and skips the receiver's pass.  Which passes run depends on the sample's record and
+// the tile alone, so every lane of the workgroup reaches the same barriers.  Both accumulators are finished (normalised) before they
+// are blended or selected per pixel.  The plain kernel is the MIX = false instantiation: one pass, nothing else compiled in.
+template <bool MIX>
 __global__ __launch_bounds__(256) void frames_prep_resize_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ index,
                                                                  const int* __restrict__ box, const float* __restrict__ mean,
                                                                  const float* __restrict__ stdv, __bf16* __restrict__ patches,
                                                                  float* __restrict__ image, int B, int Nsrc, int Hs, int Ws, int H, int W,
-                                                                 int p, size_t src_bytes, bool dwords) {
+                                                                 int p, size_t src_bytes, bool dwords, const int* __restrict__ rec,
+                                                                 const float* __restrict__ lam) {
   __shared__ __attribute__((aligned(16))) float strip[STRIP_ROWS][3][TW];
   __shared__ float wx[MAX_TAPS][TW], wy[MAX_TAPS][TH];
   __shared__ int xj0[TW], xnt[TW], yj0[TH], ynt[TH];
@@ -182,61 +250,45 @@ __global__ __launch_bounds__(256) void frames_prep_resize_kernel(const unsigned 
   const size_t total = (size_t)B * per_sample;
   const int gh = patches ? H / p : 0, gw = patches ? W / p : 0, pd = 3 * p * p;
   const bool norm = mean != nullptr;
-  const int hx = tid % TW, hr = tid / TW;            // horizontal pass: tile column, first row of the walk
-  const int vo = tid / (TW / 4), vg = tid % (TW / 4);   // vertical pass: tile row, group of 4 columns
+  const int vo = tid / (TW / 4), vg = tid % (TW / 4);   // the lane's tile row and group of 4 columns (tile_pass's vertical pass)
   for (size_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
     const int b = (int)(tile / per_sample);
     const unsigned t = (unsigned)(tile - (size_t)b * per_sample);
     const int ty = (int)(t / (unsigned)tiles_x), tx = (int)(t - (unsigned)ty * tiles_x);
-    const Box bx = box_of(src, index, box, b, Nsrc, Hs, Ws, 3, H, W);
-    __syncthreads();                                 // the previous tile's readers of the taps and the strip are done
-    if (tid < TW) {                                  // wave 0: the x-taps of tile column tid
-      const int x = tx * TW + tid;
-      Taps tp = {0, 0, 0, 0, 1};
-      if (x < W) tp = taps_of((bx.flip ? W - 1 - x : x) + bx.ox, bx.w, bx.Wv);
-      const float sum = numer_sum(tp);
-      for (int k = 0; k < MAX_TAPS; ++k) wx[k][tid] = k < tp.nt ? __fdiv_rn(numer(tp, k), sum) : 0.f;
-      xj0[tid] = tp.j0;
-      xnt[tid] = tp.nt;
-    } else if (tid >= 64 && tid < 64 + TH) {         // wave 1: the y-taps of tile row tid - 64
-      const int r = tid - 64, y = ty * TH + r;
-      Taps tp = {0, 0, 0, 0, 1};
-      if (y < H) tp = taps_of(y + bx.oy, bx.h, bx.Hv);
-      const float sum = numer_sum(tp);
-      for (int k = 0; k < MAX_TAPS; ++k) wy[k][r] = k < tp.nt ? __fdiv_rn(numer(tp, k), sum) : 0.f;
-      yj0[r] = tp.j0;
-      ynt[r] = tp.nt;
-    }
-    __syncthreads();
-    const int rows = min(TH, H - ty * TH);           // first and last tap are monotone in the output row
-    const int ylo = yj0[0], yhi = yj0[rows - 1] + ynt[rows - 1];
-    const int nx = xnt[hx], my_j0 = yj0[vo], my_nt = ynt[vo];
-    const int nt_max = (2 * max(bx.w, bx.Wv) + bx.Wv - 1) / bx.Wv;       // ceil(2S / Wv): no column of this sample has more taps
-    const unsigned char* col = bx.frame + ((size_t)bx.y0 * Ws + bx.x0 + xj0[hx]) * 3;
-    f32x4 acc[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    for (int cs = ylo; cs < yhi; cs += STRIP_ROWS) {
-      const int ce = min(cs + STRIP_ROWS, yhi);
-      if (cs != ylo) __syncthreads();                // the previous chunk's vertical pass is done with the strip
-      if (nt_max <= 4) hpass<4>(src, col, src_bytes, dwords, Ws, cs, ce, hr, hx, nx, wx, strip);
-      else if (nt_max <= 8) hpass<8>(src, col, src_bytes, dwords, Ws, cs, ce, hr, hx, nx, wx, strip);
-      else hpass_bytes(col, Ws, cs, ce, hr, hx, nx, wx, strip);
-      __syncthreads();
-      const int k0 = max(cs - my_j0, 0), k1 = min(ce - my_j0, my_nt);
-      for (int k = k0; k < k1; ++k) {
-        const float wgt = wy[k][vo];
-        const int r = my_j0 + k - cs;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += wgt * *(const f32x4*)&strip[r][c][4 * vg];
+    f32x4 acc[3] = {}, accq[3] = {};                 // a pass that is skipped leaves zeros, which no pixel then takes
+    MixRow mr = {};
+    bool pass_b = true, pass_q = false;
+    if constexpr (MIX) {
+      mr = mix_row(rec, lam, b, B, H, W);
+      const int y0 = ty * TH, y1 = min(y0 + TH, H), x0 = tx * TW, x1 = min(x0 + TW, W);      // the tile's pixels: [y0, y1) x [x0, x1)
+      if (mr.mode == 1) {
+        pass_q = true;
+      } else if (mr.mode == 2) {
+        pass_q = mr.yl < mr.yh && mr.xl < mr.xh && mr.yl < y1 && mr.yh > y0 && mr.xl < x1 && mr.xh > x0;      // the box meets the tile
+        pass_b = !(mr.yl <= y0 && mr.yh >= y1 && mr.xl <= x0 && mr.xh >= x1);                                 // and does not cover it
       }
+    }
+    if (pass_b) tile_pass(src, box_of(src, index, box, b, Nsrc, Hs, Ws, 3, H, W), src_bytes, dwords, Ws, H, W, ty, tx, strip, wx, wy, xj0, xnt, yj0, ynt, acc);
+    if constexpr (MIX) {
+      if (pass_q) tile_pass(src, box_of(src, index, box, mr.q, Nsrc, Hs, Ws, 3, H, W), src_bytes, dwords, Ws, H, W, ty, tx, strip, wx, wy, xj0, xnt, yj0, ynt, accq);
     }
     const int y = ty * TH + vo, x = tx * TW + 4 * vg;
     if (y < H && x < W) {                            // W % 4 == 0: a group of 4 columns is inside or outside as a whole
+      const bool in_rows = MIX && mr.mode == 2 && y >= mr.yl && y < mr.yh;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float m = norm ? mean[c] : 0.f, sd = norm ? stdv[c] : 1.f;
         f32x4 v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = finish(acc[c][j], norm, m, sd);
+        for (int j = 0; j < 4; ++j) {
+          if constexpr (MIX) {
+            const bool take = in_rows && x + j >= mr.xl && x + j < mr.xh;      // a pixel outside the box never reads accq, one inside never acc
+            if (mr.mode == 1) v[j] = blend(finish(acc[c][j], norm, m, sd), finish(accq[c][j], norm, m, sd), mr.l, mr.m);
+            else v[j] = finish(take ? accq[c][j] : acc[c][j], norm, m, sd);
+          } else {
+            v[j] = finish(acc[c][j], norm, m, sd);
+          }
+        }
         if (image) *(f32x4*)(image + (((size_t)b * 3 + c) * H + y) * W + x) = v;
         if (patches) {
           const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
@@ -247,11 +299,28 @@ __global__ __launch_bounds__(256) void frames_prep_resize_kernel(const unsigned 
   }
 }
 
+// element (c, y, x) of the sample cut with record bx, on the 0..255 scale: both tap loops in the lane
+__device__ __forceinline__ float resize_elem(const Box bx, int c, int y, int x, int Ws, int C, int W) {
+  const Taps tx = taps_of((bx.flip ? W - 1 - x : x) + bx.ox, bx.w, bx.Wv), ty = taps_of(y + bx.oy, bx.h, bx.Hv);
+  const float sx = numer_sum(tx), sy = numer_sum(ty);
+  const unsigned char* s = bx.frame + ((size_t)(bx.y0 + ty.j0) * Ws + bx.x0 + tx.j0) * C + c;
+  float r = 0.f;
+  for (int ky = 0; ky < ty.nt; ++ky) {
+    float row = 0.f;
+    for (int kx = 0; kx < tx.nt; ++kx) row += __fdiv_rn(numer(tx, kx), sx) * (float)s[((size_t)ky * Ws + kx) * C];
+    r += __fdiv_rn(numer(ty, ky), sy) * row;
+  }
+  return r;
+}
+
+// MIX: the partner's taps are evaluated only where the pixel takes them (every pixel of a mode-1 sample, the box of a mode-2 one); a
+// pixel inside the box evaluates the partner's alone
+template <bool MIX>
 __global__ __launch_bounds__(256) void frames_prep_resize_generic_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ index,
                                                                          const int* __restrict__ box, const float* __restrict__ mean,
                                                                          const float* __restrict__ stdv, __bf16* __restrict__ patches,
                                                                          float* __restrict__ image, int B, int Nsrc, int Hs, int Ws, int C, int H,
-                                                                         int W, int p) {
+                                                                         int W, int p, const int* __restrict__ rec, const float* __restrict__ lam) {
   const size_t total = (size_t)B * C * H * W;
   const int gh = patches ? H / p : 0, gw = patches ? W / p : 0, pd = C * p * p;
   const bool norm = mean != nullptr;
@@ -261,23 +330,54 @@ __global__ __launch_bounds__(256) void frames_prep_resize_generic_kernel(const u
     const int y = (int)(t % H); t /= H;
     const int c = (int)(t % C);
     const int b = (int)(t / C);
-    const Box bx = box_of(src, index, box, b, Nsrc, Hs, Ws, C, H, W);
-    const Taps tx = taps_of((bx.flip ? W - 1 - x : x) + bx.ox, bx.w, bx.Wv), ty = taps_of(y + bx.oy, bx.h, bx.Hv);
-    const float sx = numer_sum(tx), sy = numer_sum(ty);
-    const unsigned char* s = bx.frame + ((size_t)(bx.y0 + ty.j0) * Ws + bx.x0 + tx.j0) * C + c;
-    float r = 0.f;
-    for (int ky = 0; ky < ty.nt; ++ky) {
-      float row = 0.f;
-      for (int kx = 0; kx < tx.nt; ++kx) row += __fdiv_rn(numer(tx, kx), sx) * (float)s[((size_t)ky * Ws + kx) * C];
-      r += __fdiv_rn(numer(ty, ky), sy) * row;
+    int from = b;
+    MixRow mr = {};
+    if constexpr (MIX) {
+      mr = mix_row(rec, lam, b, B, H, W);
+      if (mr.mode == 2 && y >= mr.yl && y < mr.yh && x >= mr.xl && x < mr.xh) from = mr.q;
     }
-    const float v = finish(r, norm, norm ? mean[c] : 0.f, norm ? stdv[c] : 1.f);
+    const float r = resize_elem(box_of(src, index, box, from, Nsrc, Hs, Ws, C, H, W), c, y, x, Ws, C, W);
+    float v = finish(r, norm, norm ? mean[c] : 0.f, norm ? stdv[c] : 1.f);
+    if constexpr (MIX) {
+      if (mr.mode == 1) {
+        const float rq = resize_elem(box_of(src, index, box, mr.q, Nsrc, Hs, Ws, C, H, W), c, y, x, Ws, C, W);
+        v = blend(v, finish(rq, norm, norm ? mean[c] : 0.f, norm ? stdv[c] : 1.f), mr.l, mr.m);
+      }
+    }
     if (image) image[i] = v;
     if (patches) {
       const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
       patches[(((size_t)b * gh + ph) * gw + pw) * pd + (c * p + kh) * p + kw] = f2bf(v);
     }
   }
+}
+
+// the two entries: rec == nullptr launches the plain kernels
+template <bool MIX>
+int frames_prep_resize(const unsigned char* src, const long long* index, const int* box, const float* mean, const float* std, void* patches_bf16,
+                       float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, const int* rec, const float* lam,
+                       void* stream) {
+  if (B < 1 || Nsrc < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || C < 1 || C > 4) return VITAMD_ERR_SHAPE;
+  if (Hs > MAX_SIZE || Ws > MAX_SIZE || H > MAX_SIZE || W > MAX_SIZE) return VITAMD_ERR_SHAPE;
+  if (patches_bf16 && (p < 1 || H % p != 0 || W % p != 0)) return VITAMD_ERR_SHAPE;
+  if (!index && Nsrc < B) return VITAMD_ERR_SHAPE;
+  const long long n_src = count(Nsrc, Hs, Ws, C), n_out = count(B, C, H, W);
+  if (n_src < 0 || n_out < 0) return VITAMD_ERR_SHAPE;
+  if (!src || !box || (mean == nullptr) != (std == nullptr) || (!patches_bf16 && !image) || (MIX && !rec)) return VITAMD_ERR_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool aligned = ((uintptr_t)image & 15) == 0 && ((uintptr_t)patches_bf16 & 7) == 0;      // of the 16- and 8-byte stores
+  if (C == 3 && W % 4 == 0 && (!patches_bf16 || p % 4 == 0) && aligned) {
+    const size_t tiles = (size_t)B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
+    const dim3 grid((unsigned)(tiles < (size_t)RESIZE_GRID_CAP ? tiles : (size_t)RESIZE_GRID_CAP));
+    hipLaunchKernelGGL(frames_prep_resize_kernel<MIX>, grid, dim3(256), 0, st, src, index, box, mean, std, (__bf16*)patches_bf16, image, B, Nsrc,
+                       Hs, Ws, H, W, p, (size_t)n_src, ((uintptr_t)src & 3) == 0, rec, lam);
+  } else {
+    const size_t wgs = ((size_t)n_out + 255) / 256;
+    const dim3 grid((unsigned)(wgs < (size_t)RESIZE_GRID_CAP ? wgs : (size_t)RESIZE_GRID_CAP));
+    hipLaunchKernelGGL(frames_prep_resize_generic_kernel<MIX>, grid, dim3(256), 0, st, src, index, box, mean, std, (__bf16*)patches_bf16, image,
+                       B, Nsrc, Hs, Ws, C, H, W, p, rec, lam);
+  }
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
 }  // namespace
@@ -287,25 +387,11 @@ extern "C" int vitamd_frames_prep_resize_grid_cap(void) { return RESIZE_GRID_CAP
 extern "C" int vitamd_frames_prep_resize(const unsigned char* src, const long long* index, const int* box, const float* mean, const float* std,
                                          void* patches_bf16, float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p,
                                          void* stream) {
-  if (B < 1 || Nsrc < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || C < 1 || C > 4) return VITAMD_ERR_SHAPE;
-  if (Hs > MAX_SIZE || Ws > MAX_SIZE || H > MAX_SIZE || W > MAX_SIZE) return VITAMD_ERR_SHAPE;
-  if (patches_bf16 && (p < 1 || H % p != 0 || W % p != 0)) return VITAMD_ERR_SHAPE;
-  if (!index && Nsrc < B) return VITAMD_ERR_SHAPE;
-  const long long n_src = count(Nsrc, Hs, Ws, C), n_out = count(B, C, H, W);
-  if (n_src < 0 || n_out < 0) return VITAMD_ERR_SHAPE;
-  if (!src || !box || (mean == nullptr) != (std == nullptr) || (!patches_bf16 && !image)) return VITAMD_ERR_ARG;
-  const hipStream_t st = (hipStream_t)stream;
-  const bool aligned = ((uintptr_t)image & 15) == 0 && ((uintptr_t)patches_bf16 & 7) == 0;      // of the 16- and 8-byte stores
-  if (C == 3 && W % 4 == 0 && (!patches_bf16 || p % 4 == 0) && aligned) {
-    const size_t tiles = (size_t)B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
-    const dim3 grid((unsigned)(tiles < (size_t)RESIZE_GRID_CAP ? tiles : (size_t)RESIZE_GRID_CAP));
-    hipLaunchKernelGGL(frames_prep_resize_kernel, grid, dim3(256), 0, st, src, index, box, mean, std, (__bf16*)patches_bf16, image, B, Nsrc, Hs,
-                       Ws, H, W, p, (size_t)n_src, ((uintptr_t)src & 3) == 0);
-  } else {
-    const size_t wgs = ((size_t)n_out + 255) / 256;
-    const dim3 grid((unsigned)(wgs < (size_t)RESIZE_GRID_CAP ? wgs : (size_t)RESIZE_GRID_CAP));
-    hipLaunchKernelGGL(frames_prep_resize_generic_kernel, grid, dim3(256), 0, st, src, index, box, mean, std, (__bf16*)patches_bf16, image, B,
-                       Nsrc, Hs, Ws, C, H, W, p);
-  }
-  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+  return frames_prep_resize<false>(src, index, box, mean, std, patches_bf16, image, B, Nsrc, Hs, Ws, C, H, W, p, nullptr, nullptr, stream);
+}
+
+extern "C" int vitamd_frames_prep_resize_mix(const unsigned char* src, const long long* index, const int* box, const float* mean,
+                                             const float* std, void* patches_bf16, float* image, int B, int Nsrc, int Hs, int Ws, int C, int H,
+                                             int W, int p, const int* rec, const float* lam, void* stream) {
+  return frames_prep_resize<true>(src, index, box, mean, std, patches_bf16, image, B, Nsrc, Hs, Ws, C, H, W, p, rec, lam, stream);
 }

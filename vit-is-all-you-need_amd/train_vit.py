@@ -100,7 +100,7 @@ def parse_args(argv=None):
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm on the device (vitamd.optim.AdamW, multi-tensor path); default: no clipping")
     p.add_argument("--dropout", type=float, default=0.0)
-    p.add_argument("--mixup", type=float, default=0.0, help="Mixup: the alpha of its Beta draw (0 = off); needs --u8 (vitamd.mix.MixLoader)")
+    p.add_argument("--mixup", type=float, default=0.0, help="Mixup: the alpha of its Beta draw (0 = off); needs --u8 (vitamd.mix.MixLoader; with --rrc / --resize vitamd.mix.ResizeMixLoader)")
     p.add_argument("--cutmix", type=float, default=0.0, help="CutMix: the alpha of its Beta draw (0 = off); needs --u8")
     p.add_argument("--mix_prob", type=float, default=1.0, help="the chance that a batch is mixed at all")
     p.add_argument("--mix_switch_prob", type=float, default=0.5, help="the chance of CutMix when both --mixup and --cutmix are on")
@@ -135,8 +135,6 @@ def main(argv=None):
     resizing = args.rrc or args.resize is not None
     if resizing and not args.u8:
         raise SystemExit("--rrc / --resize resize inside the device input feed (vitamd.resize.ResizeLoader): they need --u8")
-    if resizing and mixing:
-        raise SystemExit("--rrc / --resize with --mixup / --cutmix: mixing resized samples in one launch is not built - use one or the other")
     if args.src_size is not None and not resizing:
         raise SystemExit("--src_size goes with --rrc or --resize")
     dev = torch.device("cuda")
@@ -157,7 +155,12 @@ def main(argv=None):
         u8 = torch.randint(0, 256, (args.bs, *src_hw, 3), generator=g, dtype=torch.uint8)
         host_labels = labels.cpu()
         host = ((u8, host_labels) for _ in range(args.train_steps))
-        if resizing:
+        if resizing and mixing:                                 # the DeiT recipe: RandomResizedCrop and the mix in one launch
+            from vitamd.mix import Mix, ResizeMixLoader
+            mix = Mix(args.mixup, args.cutmix, args.mix_prob, args.mix_switch_prob, label_smoothing=args.label_smoothing, seed=0)
+            feed = ResizeMixLoader(host, dev, args.image_size, mix, mode="rrc" if args.rrc else "resize_crop", scale=tuple(args.rrc_scale),
+                                   resize_to=args.resize, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)
+        elif resizing:
             from vitamd.resize import ResizeLoader
             feed = ResizeLoader(host, dev, args.image_size, mode="rrc" if args.rrc else "resize_crop", scale=tuple(args.rrc_scale),
                                 resize_to=args.resize, patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0)

@@ -103,6 +103,7 @@ SIGNATURES = {
     "vitamd_frames_prep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "vitamd_frames_prep_mix": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "vitamd_frames_prep_resize": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vitamd_frames_prep_resize_mix": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "vitamd_frames_prep_resize_grid_cap": [],
     "vitamd_frames_prep_grid_cap": [],
     "vitamd_crop_flip_draw": [_P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P],

@@ -6,6 +6,7 @@ device input feed (csrc/input.hip, vitamd_frames_prep_mix) and the loss (csrc/lo
     loss_fn = SoftTargetLoss(mix.label_smoothing)
     for frames, labels in loader:
         loss = train_vit.train_step(model, frames, labels, optim, loss_fn=loss_fn)
+    loader = ResizeMixLoader(host_iter, "cuda", 224, mix, mode="rrc", patch=16, image=False)      # RandomResizedCrop AND the mix, one launch
 
 What is mixed is decided on the HOST, from a counter-based generator keyed by (seed, step): a record of six integers and one float
 per sample, which crosses to the device through a pinned buffer.  The prep kernel then cuts sample b and its partner, each with its
@@ -18,7 +19,7 @@ import math
 import numpy as np
 import torch
 
-from . import data, lm, ops
+from . import data, lm, ops, resize
 from . import lib as _lib
 
 MODE_NONE, MODE_MIXUP, MODE_CUTMIX = 0, 1, 2
@@ -158,7 +159,7 @@ class MixLoader(data.DeviceLoader):
 
     def __init__(self, host_iter, device, size, mix, **kwargs):
         if any(k in kwargs for k in ("mode", "scale", "ratio", "resize_to")):
-            raise ValueError("MixLoader: mixing resized samples in one launch is not built (vitamd.resize.ResizeLoader resizes, without mixing)")
+            raise ValueError("MixLoader: this loader does not resize (ResizeMixLoader mixes resized samples in one launch)")
         super().__init__(host_iter, device, size, **kwargs)
         if not isinstance(mix, Mix):
             raise ValueError(f"MixLoader: mix must be a vitamd.mix.Mix, got {type(mix).__name__}")
@@ -193,5 +194,109 @@ class MixLoader(data.DeviceLoader):
             return super()._labels(labels)
         if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() != 1:
             raise ValueError("MixLoader: a mixed batch needs int64 labels [B] from host_iter")
+        rec, lam = self._pair
+        return MixedLabels(labels, labels[rec[:, 0].long()], lam)
+
+
+def _need_mix(mix, B, who):
+    """the (rec, lam) pair of a mixed batch of B samples, checked as MixedFrames checks it"""
+    if not (isinstance(mix, (tuple, list)) and len(mix) == 2):
+        raise ValueError(f"{who}: mix must be (rec int32 [B, 6], lam fp32 [B])")
+    rec, lam = mix
+    if not isinstance(rec, torch.Tensor) or rec.dtype != torch.int32 or tuple(rec.shape) != (B, 6):
+        raise ValueError(f"{who}: rec must be int32 [{B}, 6]")
+    if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or tuple(lam.shape) != (B,):
+        raise ValueError(f"{who}: lam must be fp32 [{B}]")
+    return rec, lam
+
+
+class MixedResizedFrames(resize.ResizedFrames):
+    """resize.ResizedFrames whose samples are mixed with their partners on the way out of the prep kernel (csrc/resize.hip,
+    vitamd_frames_prep_resize_mix): every sample is resized with its own row of `box` and normalised, then mixed
+    by mix = (rec int32 [B, 6], lam fp32 [B]) as MixedFrames mixes.  What images() and patches(p) return is the mixed batch."""
+
+    def __init__(self, src_u8, size, box, index=None, mean=None, std=None, *, mix):
+        if isinstance(box, torch.Tensor) and box.dim() == 2:
+            _need_mix(mix, box.shape[0], "MixedResizedFrames")       # before the base class looks at a device
+        super().__init__(src_u8, size, box, index=index, mean=mean, std=std)
+        rec, lam = _need_mix(mix, self.shape[0], "MixedResizedFrames")
+        self._mix = (rec.to(self.device).contiguous(), lam.to(self.device).contiguous())
+
+    @property
+    def mix(self):
+        """(rec, lam) on the device, as this batch is mixed"""
+        return self._mix
+
+    def materialise(self, patch=None, image=True):
+        """as Frames.materialise, through the resizing and mixing kernel"""
+        want_p = patch is not None and patch not in self._patches
+        want_i = bool(image) and self._image is None
+        if patch is not None and (not isinstance(patch, int) or isinstance(patch, bool) or patch < 1 or self.shape[2] % patch or self.shape[3] % patch):
+            raise ValueError(f"Frames: patch {patch!r} does not tile the output {tuple(self.shape[2:])}")
+        if want_p or want_i:
+            if self._src is None:
+                raise _lib.VitamdError(f"Frames: this batch was materialised by its loader and its source slot is reused; patch={patch}, "
+                                       f"image={image} was not asked of the loader")
+            patches, img = ops.frames_prep_resize_mix(self._src, self.shape[2:], patch if want_p else None, want_i, self._index, self._box,
+                                                      self._mean, self._std, *self._mix)
+            if want_p:
+                self._patches[patch] = patches
+            if want_i:
+                self._image = img
+        return self
+
+
+class ResizeMixLoader(resize.ResizeLoader):
+    """resize.ResizeLoader that mixes: the DeiT / timm recipe's RandomResizedCrop (or Resize + crop) and its Mixup / CutMix in the one
+    launch of vitamd_frames_prep_resize_mix.  With train=True every batch is cut by self.boxes(...) exactly as ResizeLoader cuts it
+    under the same (seed, step), mixed by `mix.draw(B, size, step)` exactly as MixLoader mixes it, and handed out as
+    (MixedResizedFrames, MixedLabels(a, a[partner], lam)).  With train=False it is ResizeLoader's centre form with plain labels.
+    host_iter must yield int64 labels [B] when train=True.
+
+    Both records cross through pinned staging buffers with non_blocking copies on the current stream: the box through ResizeLoader's,
+    the mix record through `depth` buffers of this class, each rewritten only behind the event of the copy that last read it."""
+
+    def __init__(self, host_iter, device, size, mix, mode="rrc", scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), resize_to=None, **kwargs):
+        if not isinstance(mix, Mix):
+            raise ValueError(f"ResizeMixLoader: mix must be a vitamd.mix.Mix, got {type(mix).__name__}")
+        super().__init__(host_iter, device, size, mode=mode, scale=scale, ratio=ratio, resize_to=resize_to, **kwargs)
+        self.mix = mix
+        self._mix_stage = [None] * self.depth
+        self._pair = None                  # (rec, lam) on the device, of the batch being handed out
+
+    def _check(self, batch):
+        """ResizeLoader._check, and a mixed batch needs its labels: refused before anything touches the device"""
+        if self.train and isinstance(batch, (tuple, list)) and len(batch) in (2, 3):
+            labels = batch[1]
+            if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() != 1:
+                raise ValueError("ResizeMixLoader: a mixed batch needs int64 labels [B] from host_iter")
+        return super()._check(batch)
+
+    def _staged_mix(self, rec, lam):
+        """the host mix record -> the device, through the staging buffer of this step (MixLoader._staged)"""
+        B = rec.shape[0]
+        st = self._mix_stage[self.step % self.depth]
+        if st is None or st["rec"].shape[0] < B:
+            st = {"rec": torch.zeros((B, 6), dtype=torch.int32).pin_memory(), "lam": torch.zeros((B,), dtype=torch.float32).pin_memory(),
+                  "done": torch.cuda.Event()}
+            self._mix_stage[self.step % self.depth] = st
+        st["done"].synchronize()           # host: the copy that last read these buffers is over (no-op when never recorded)
+        st["rec"][:B].copy_(rec)
+        st["lam"][:B].copy_(lam)
+        rec_dev = st["rec"][:B].to(self.device, non_blocking=True)
+        lam_dev = st["lam"][:B].to(self.device, non_blocking=True)
+        st["done"].record(torch.cuda.current_stream(self.device))
+        return rec_dev, lam_dev
+
+    def _frames(self, src, geom, table):
+        if not self.train:
+            return super()._frames(src, geom, table)
+        box = self.boxes(src.shape[0], tuple(src.shape[1:3]), self.step, self._extents.popleft())
+        self._pair = self._staged_mix(*self.mix.draw(src.shape[0], self.out_hw, self.step))
+        return MixedResizedFrames(src, self.out_hw, self._staged(box), mean=self.mean, std=self.std, mix=self._pair)
+
+    def _labels(self, labels):
+        if not self.train:
+            return super()._labels(labels)
         rec, lam = self._pair
         return MixedLabels(labels, labels[rec[:, 0].long()], lam)

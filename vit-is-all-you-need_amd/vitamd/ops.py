@@ -1280,15 +1280,17 @@ def check_frames(src_shape, out_hw, patch=None, B=None, has_index=False, resize=
     return B, Nsrc, Hs, Ws, C, H, W
 
 
-def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=None, mix=None, resize=None):
+def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=None, mix=None, resize=None, _resize_mix=False):
     """uint8 frames [Nsrc, Hs, Ws, C] -> (patch rows bf16 [B*gh*gw, C*p*p] or None, image fp32 [B, C, H, W] or None) in one launch
     (semantics, clamps and refusals: include/vitamd.h vitamd_frames_prep).  index int64 [B] or None, geom int32 [B, 3] or None,
     table fp32 [C, 256], all on the device of src.  mix = (rec int32 [B, 6], lam fp32 [B] or None) on that device: Mixup / CutMix on the
     way (vitamd_frames_prep_mix; lam None promises that no row of rec has mode 1).  resize = (box int32 [B, 10], mean fp32 [C] or None,
     std fp32 [C] or None) on that device: the antialiased bilinear resize of vitamd_frames_prep_resize in front of the crop; the record
-    carries the crop and the flip and mean / std stand where the table stood, so table and geom must be None, and mix is refused."""
-    if resize is not None and mix is not None:
-        raise ValueError("frames_prep: give mix or resize, not both (mixing resized samples in one launch is not built)")
+    carries the crop and the flip and mean / std stand where the table stood, so table and geom must be None, and mix is refused:
+    mixing resized samples is frames_prep_resize_mix's route.  That function alone sets _resize_mix, and then comes through here with
+    both, so that every route of the frame kernels shares these checks and the one pair of output allocations below."""
+    if resize is not None and mix is not None and not _resize_mix:
+        raise ValueError("frames_prep: give mix or resize, not both (frames_prep_resize_mix mixes resized samples in one launch)")
     if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
         raise ValueError(f"frames_prep: src must be a uint8 tensor, got {getattr(src, 'dtype', type(src).__name__)}")
     if patch is None and not image:
@@ -1337,6 +1339,11 @@ def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=Non
                 raise _lib.VitamdError(f"lam: expected [{B}], got {tuple(lam.shape)}")
     patches = torch.empty((B * (H // patch) * (W // patch), C * patch * patch), dtype=BF16, device=src.device) if patch is not None else None
     img = torch.empty((B, C, H, W), dtype=F32, device=src.device) if image else None
+    if resize is not None and mix is not None:
+        _lib.check(_L().vitamd_frames_prep_resize_mix(_p(src), _p(index), _p(resize[0]), _p(resize[1]), _p(resize[2]), _p(patches), _p(img), B,
+                                                      Nsrc, Hs, Ws, C, H, W, patch if patch is not None else 0, _p(mix[0]), _p(mix[1]), _stream()),
+                   f"frames_prep_resize_mix[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
+        return patches, img
     if resize is not None:
         _lib.check(_L().vitamd_frames_prep_resize(_p(src), _p(index), _p(resize[0]), _p(resize[1]), _p(resize[2]), _p(patches), _p(img), B, Nsrc,
                                                   Hs, Ws, C, H, W, patch if patch is not None else 0, _stream()),
@@ -1351,6 +1358,18 @@ def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=Non
                                        patch if patch is not None else 0, _stream()),
                f"frames_prep[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
     return patches, img
+
+
+def frames_prep_resize_mix(src, out_hw, patch, image, index, box, mean, std, rec, lam):
+    """uint8 frames [Nsrc, Hs, Ws, C] of any size -> (patch rows bf16 or None, image fp32 or None): every sample resized with its own
+    row of box int32 [B, 10] and normalised (mean, std fp32 [C], both or neither) as frames_prep(resize=) does, then mixed with its
+    partner by rec int32 [B, 6] and lam fp32 [B] (None promises that no row has mode 1) as frames_prep(mix=) does - in one launch
+    (include/vitamd.h vitamd_frames_prep_resize_mix).  patch None: no rows; image False: no image; index int64 [B] or None.  Everything
+    on the device of src.  The argument checks are those of both routes, and the outputs are frames_prep's."""
+    if box is None or rec is None:
+        raise ValueError("frames_prep_resize_mix: needs box int32 [B, 10] and rec int32 [B, 6] (frames_prep takes a batch that is only "
+                         "resized or only mixed)")
+    return frames_prep(src, out_hw, None, patch, image, index, None, mix=(rec, lam), resize=(box, mean, std), _resize_mix=True)
 
 
 def crop_flip_draw(B, src_hw, out_hw, seed, step, flip=True, device=None, out=None):
