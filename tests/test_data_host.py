@@ -220,3 +220,62 @@ def test_device_loader_refuses_wrong_input_before_any_device_work():
     empty = data.DeviceLoader(iter([]), "cuda", 8)
     with pytest.raises(StopIteration):
         next(empty)
+
+
+# ---------------------------------------------------------------------------------------------- one home for what the four routes share
+def test_one_materialise_and_one_launch_hook_per_frames_class():
+    from vitamd import data, mix, resize
+    classes = (data.Frames, resize.ResizedFrames, mix.MixedFrames, mix.MixedResizedFrames)
+    assert [c for c in classes if "materialise" in vars(c)] == [data.Frames]        # the bookkeeping is stated once
+    assert all("_launch" in vars(c) for c in classes)                               # and every class says only which kernel it takes
+    assert len({c._launch for c in classes}) == 4 and all(c.materialise is data.Frames.materialise for c in classes)
+    pkg = os.path.join(ROOT, "vit-is-all-you-need_amd", "vitamd")
+    src = {n: open(os.path.join(pkg, n)).read() for n in sorted(os.listdir(pkg)) if n.endswith(".py")}
+    assert sum(s.count("self._src is None") for s in src.values()) == 1             # the released-source refusal
+    assert "pin_memory(" not in src["mix.py"] and "pin_memory(" not in src["resize.py"]      # the record staging has one home
+    assert src["data.py"].count("def _stage_over(") == 1 and src["data.py"].count("pin_memory(") == 3     # _feed's two and this one
+    assert all(n not in s for n in ("torch.cuda.Event", "non_blocking=") for s in (src["mix.py"], src["resize.py"]))
+
+
+def test_record_staging_keeps_its_order_of_steps(monkeypatch):
+    """DeviceLoader._stage_over with stand-ins for the pinned allocation and the event: entry step % depth, allocated on first use
+    and again when too short; the host waits for the entry's event BEFORE the buffers are rewritten and records it AFTER the copies
+    to the device were issued; the device tensors come back in the order given."""
+    from vitamd import data
+    log = []
+
+    class Event:
+        def synchronize(self):
+            log.append(("sync", {k: v.clone() for k, v in (stage[slot] or {}).items() if k != "done"}))
+
+        def record(self, stream):
+            log.append(("record", stream, {k: v.clone() for k, v in stage[slot].items() if k != "done"}))
+
+    monkeypatch.setattr(torch.cuda, "Event", Event)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: ("stream of", device))
+    monkeypatch.setattr(torch.Tensor, "pin_memory", lambda self: log.append(("pin", tuple(self.shape), self.dtype, int(self.abs().sum()))) or self)
+    ld = data.DeviceLoader(iter([]), "cuda", 8, depth=3)
+    ld.device = "cpu"                                   # where the stand-in copies go
+    stage = [None] * 3
+    rec1, lam1 = torch.arange(12, dtype=torch.int32).reshape(2, 6) + 1, torch.tensor([0.25, 0.5])
+    ld.step, slot = 4, 1
+    out = ld._stage_over(stage, rec=rec1, lam=lam1)
+    assert [e[0] for e in log] == ["pin", "pin", "sync", "record"] and log[0][1:] == ((2, 6), torch.int32, 0) and log[1][1:] == ((2,), torch.float32, 0)
+    assert stage[0] is None and stage[2] is None and list(stage[1]) == ["rec", "lam", "done"]
+    assert not log[2][1]["rec"].any() and torch.equal(log[3][2]["rec"], rec1) and log[3][1] == ("stream of", "cpu")
+    assert isinstance(out, tuple) and torch.equal(out[0], rec1) and torch.equal(out[1], lam1)
+    del log[:]
+    rec2, lam2 = rec1[:1] * 3, lam1[:1] * 3                # a shorter batch, `depth` steps later: the same entry, no allocation
+    ld.step = 7
+    first = stage[1]
+    out = ld._stage_over(stage, rec=rec2, lam=lam2)
+    assert stage[1] is first and [e[0] for e in log] == ["sync", "record"]
+    assert torch.equal(log[0][1]["rec"], rec1) and torch.equal(log[0][1]["lam"], lam1)          # still the earlier record when the host waits
+    assert torch.equal(log[1][2]["rec"][:1], rec2) and torch.equal(log[1][2]["lam"][:1], lam2)
+    assert tuple(out[0].shape) == (1, 6) and torch.equal(out[0], rec2) and torch.equal(out[1], lam2)
+    del log[:]
+    box = torch.ones((5, 10), dtype=torch.int32)            # a record of its own list, and a longer batch: allocated again
+    ld.step, slot = 10, 1
+    stage[1] = {"box": torch.zeros((2, 10), dtype=torch.int32), "done": Event()}
+    (out,) = ld._stage_over(stage, box=box)
+    assert [e[0] for e in log] == ["pin", "sync", "record"] and tuple(stage[1]["box"].shape) == (5, 10) and torch.equal(out, box)

@@ -119,7 +119,9 @@ def test_the_loader_overrides_the_hooks_it_must_and_the_classes_stand_where_thei
     assert issubclass(ML, RL) and issubclass(mix.MixedResizedFrames, resize.ResizedFrames) and issubclass(mix.MixedResizedFrames, data.Frames)
     assert ML._frames is not RL._frames and ML._labels is not RL._labels and ML._check is not RL._check
     assert ML._staged is RL._staged and ML.boxes is RL.boxes and ML._geom is RL._geom and ML.__next__ is data.DeviceLoader.__next__
-    assert mix.MixedResizedFrames.materialise is not resize.ResizedFrames.materialise
+    # the subclass takes its own route through the kernels, and the bookkeeping around it is the one of Frames
+    assert mix.MixedResizedFrames.materialise is data.Frames.materialise
+    assert mix.MixedResizedFrames._launch is not resize.ResizedFrames._launch and mix.MixedResizedFrames._launch is not mix.MixedFrames._launch
     ld = ML(iter([]), "cuda", 16, mix.Mix(), depth=3)
     assert ld._mix_stage is not ld._stage and len(ld._mix_stage) == len(ld._stage) == 3      # a staging list of its own
     assert isinstance(mix.MixedResizedFrames.mix, property)

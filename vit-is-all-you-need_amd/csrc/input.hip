@@ -13,32 +13,19 @@
 // Generic form: one lane per output element.
 // Every device-side value is clamped before it forms an address: index into [0, Nsrc), y0 into [0, Hs-H], x0 into [0, Ws-W].
 #include "common.h"
+#include "frames_out.h"
 #include "mix_row.h"
-#include "../../include/vitamd.h"
 
 namespace {
 
 constexpr int PREP_GRID_CAP = 2048;                  // workgroups per launch (8 per CU); further work is reached by the stride loop
-constexpr long long MAX_ELEMS = 1ll << 40;           // per tensor: keeps every product of the index arithmetic inside 64 bits
-
-// the element count of a tensor, or -1 beyond MAX_ELEMS (checked factor by factor: four ints can overflow 64 bits)
-inline long long count(int a, int b, int c, int d) {
-  long long n = a;
-  for (const int f : {b, c, d}) {
-    n *= f;
-    if (n > MAX_ELEMS) return -1;
-  }
-  return n;
-}
 
 struct Placement { const unsigned char* frame; int y0, x0, flip; };
 
 // where output sample b reads: its (clamped) source frame and crop origin
 __device__ __forceinline__ Placement place(const unsigned char* src, const long long* index, const int* geom, int b, int Nsrc, int Hs, int Ws,
                                            int C, int H, int W) {
-  long long f = index ? index[b] : b;
-  f = f < 0 ? 0 : (f > Nsrc - 1 ? Nsrc - 1 : f);
-  Placement pl = {src + (size_t)f * Hs * Ws * C, 0, 0, 0};
+  Placement pl = {source_frame(src, index, b, Nsrc, Hs, Ws, C), 0, 0, 0};
   if (geom) {
     const int* g = geom + (size_t)b * 3;
     pl.y0 = min(max(g[0], 0), Hs - H);
@@ -96,7 +83,7 @@ __global__ __launch_bounds__(256) void frames_prep_kernel(const unsigned char* _
   const int w4 = W / 4;
   const unsigned per_sample = (unsigned)H * w4;
   const size_t total = (size_t)B * per_sample;
-  const int gh = patches ? H / p : 0, gw = patches ? W / p : 0, pd = 3 * p * p;
+  const FramesOut out = {patches, image, H, W, 3, p, patches ? H / p : 0, patches ? W / p : 0, 3 * p * p};
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     // one 64-bit division per item (the sample), 32-bit arithmetic inside the sample: the host keeps H * W / 4 below 2^31
     const int b = (int)(i / per_sample);
@@ -109,7 +96,7 @@ __global__ __launch_bounds__(256) void frames_prep_kernel(const unsigned char* _
       const unsigned p4 = p / 4;
       const int kw4 = (int)(t % p4); t /= p4;
       const int r = (int)(t & 3); t >>= 2;
-      const int pw = (int)(t % (unsigned)gw); t /= (unsigned)gw;
+      const int pw = (int)(t % (unsigned)out.gw); t /= (unsigned)out.gw;
       x = pw * p + kw4 * 4;
       y = (int)t * 4 + r;                                           // H % p == 0 and p % 4 == 0: rows come in fours
     } else {
@@ -150,11 +137,7 @@ __global__ __launch_bounds__(256) void frames_prep_kernel(const unsigned char* _
           for (int j = 0; j < 4; ++j) v[j] = mr.mode == 1 ? blend(v[j], u[j], mr.l, mr.m) : (take[j] ? u[j] : v[j]);
         }
       }
-      if (image) *(f32x4*)(image + (((size_t)b * 3 + c) * H + y) * W + x) = v;
-      if (patches) {
-        const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
-        *(u32x2*)(patches + (((size_t)b * gh + ph) * gw + pw) * pd + (c * p + kh) * p + kw) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-      }
+      out.store4(b, c, y, x, v);
     }
   }
 }
@@ -175,7 +158,7 @@ __global__ __launch_bounds__(256) void frames_prep_generic_kernel(const unsigned
   for (int i = threadIdx.x; i < C * 256; i += 256) tab[i] = table[i];
   __syncthreads();
   const size_t total = (size_t)B * C * H * W;
-  const int gh = patches ? H / p : 0, gw = patches ? W / p : 0, pd = C * p * p;
+  const FramesOut out = {patches, image, H, W, C, p, patches ? H / p : 0, patches ? W / p : 0, C * p * p};
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {      // i = the element of image
     size_t t = i;
     const int x = (int)(t % W); t /= W;
@@ -190,11 +173,7 @@ __global__ __launch_bounds__(256) void frames_prep_generic_kernel(const unsigned
         v = mr.mode == 1 ? blend(v, u, mr.l, mr.m) : u;
       }
     }
-    if (image) image[i] = v;
-    if (patches) {
-      const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
-      patches[(((size_t)b * gh + ph) * gw + pw) * pd + (c * p + kh) * p + kw] = f2bf(v);
-    }
+    out.store1(i, b, c, y, x, v);
   }
 }
 
@@ -240,25 +219,17 @@ __global__ __launch_bounds__(256) void frames_to_u8_generic_kernel(const float* 
   }
 }
 
-inline dim3 capped_grid(size_t items) {
-  const size_t wgs = (items + 255) / 256;
-  return dim3((unsigned)(wgs < (size_t)PREP_GRID_CAP ? wgs : (size_t)PREP_GRID_CAP));
-}
-
 // the two entries: rec == nullptr launches the plain kernels
 template <bool MIX>
 int frames_prep(const unsigned char* src, const long long* index, const int* geom, const float* table, void* patches_bf16, float* image, int B,
                 int Nsrc, int Hs, int Ws, int C, int H, int W, int p, const int* rec, const float* lam, void* stream) {
-  if (B < 1 || Nsrc < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || C < 1 || C > 4 || H > Hs || W > Ws) return VITAMD_ERR_SHAPE;
-  if (patches_bf16 && (p < 1 || H % p != 0 || W % p != 0)) return VITAMD_ERR_SHAPE;
-  if (!index && Nsrc < B) return VITAMD_ERR_SHAPE;
-  const long long n_src = count(Nsrc, Hs, Ws, C), n_out = count(B, C, H, W);
-  if (n_src < 0 || n_out < 0) return VITAMD_ERR_SHAPE;
+  long long n_src, n_out;
+  if (H > Hs || W > Ws || frames_shape(patches_bf16 != nullptr, index != nullptr, B, Nsrc, Hs, Ws, C, H, W, p, &n_src, &n_out)) return VITAMD_ERR_SHAPE;
   if (!src || !table || (!patches_bf16 && !image) || (MIX && !rec)) return VITAMD_ERR_ARG;
   const hipStream_t st = (hipStream_t)stream;
   const bool aligned = ((uintptr_t)image & 15) == 0 && ((uintptr_t)patches_bf16 & 7) == 0;      // of the 16- and 8-byte stores
   if (C == 3 && W % 4 == 0 && (!patches_bf16 || p % 4 == 0) && aligned && (long long)H * W / 4 < 0x7fffffffll) {
-    const dim3 grid = capped_grid((size_t)n_out / 12);
+    const dim3 grid = capped_grid((size_t)n_out / 12, 256, PREP_GRID_CAP);
     if (((uintptr_t)src & 3) == 0)
       hipLaunchKernelGGL((frames_prep_kernel<true, MIX>), grid, dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16, image, B, Nsrc,
                          Hs, Ws, H, W, p, (size_t)n_src, rec, lam);
@@ -266,7 +237,7 @@ int frames_prep(const unsigned char* src, const long long* index, const int* geo
       hipLaunchKernelGGL((frames_prep_kernel<false, MIX>), grid, dim3(256), 0, st, src, index, geom, table, (__bf16*)patches_bf16, image, B, Nsrc,
                          Hs, Ws, H, W, p, (size_t)n_src, rec, lam);
   } else {
-    hipLaunchKernelGGL(frames_prep_generic_kernel<MIX>, capped_grid((size_t)n_out), dim3(256), 0, st, src, index, geom, table,
+    hipLaunchKernelGGL(frames_prep_generic_kernel<MIX>, capped_grid((size_t)n_out, 256, PREP_GRID_CAP), dim3(256), 0, st, src, index, geom, table,
                        (__bf16*)patches_bf16, image, B, Nsrc, Hs, Ws, C, H, W, p, rec, lam);
   }
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
@@ -305,14 +276,14 @@ extern "C" int vitamd_frames_to_u8(const float* img, unsigned char* out, int B, 
   const size_t hw = (size_t)H * W;
   if (hw % 4 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 3) == 0) {
     const size_t groups = (size_t)B * (hw / 4);
-    const dim3 grid = capped_grid(groups);
+    const dim3 grid = capped_grid(groups, 256, PREP_GRID_CAP);
     unsigned* o = (unsigned*)out;
     if (C == 1) hipLaunchKernelGGL(frames_to_u8_kernel<1>, grid, dim3(256), 0, st, img, o, groups, hw / 4);
     else if (C == 2) hipLaunchKernelGGL(frames_to_u8_kernel<2>, grid, dim3(256), 0, st, img, o, groups, hw / 4);
     else if (C == 3) hipLaunchKernelGGL(frames_to_u8_kernel<3>, grid, dim3(256), 0, st, img, o, groups, hw / 4);
     else hipLaunchKernelGGL(frames_to_u8_kernel<4>, grid, dim3(256), 0, st, img, o, groups, hw / 4);
   } else {
-    hipLaunchKernelGGL(frames_to_u8_generic_kernel, capped_grid((size_t)n), dim3(256), 0, st, img, out, (size_t)n, C, hw);
+    hipLaunchKernelGGL(frames_to_u8_generic_kernel, capped_grid((size_t)n, 256, PREP_GRID_CAP), dim3(256), 0, st, img, out, (size_t)n, C, hw);
   }
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }

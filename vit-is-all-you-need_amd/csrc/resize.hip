@@ -22,26 +22,16 @@
 // No atomics and a fixed order of additions: the same bits on every call.
 // Every device-side value is clamped before it forms an address (box_of), and no tap loop runs past MAX_TAPS.
 #include "common.h"
+#include "frames_out.h"
 #include "mix_row.h"
-#include "../../include/vitamd.h"
 
 namespace {
 
 constexpr int RESIZE_GRID_CAP = 1024;                // workgroups per launch (4 per CU: what the LDS admits); a stride loop beyond
-constexpr long long MAX_ELEMS = 1ll << 40;           // per tensor, as input.hip
 constexpr int MAX_SIZE = 8192;                       // of Hs, Ws, H, W and the virtual sizes: u * h and (2j+1) * Hv stay below 2^31
 constexpr int MAX_TAPS = 16;                         // per axis: 2 * max(h / Hv, 1) at the 8x down-scaling cap
 constexpr int TH = 32, TW = 32;                      // the output tile of a workgroup
 constexpr int STRIP_ROWS = 80;                       // source rows of one horizontal pass
-
-inline long long count(int a, int b, int c, int d) {
-  long long n = a;
-  for (const int f : {b, c, d}) {
-    n *= f;
-    if (n > MAX_ELEMS) return -1;
-  }
-  return n;
-}
 
 struct Box { const unsigned char* frame; int y0, h, Hv, oy, x0, w, Wv, ox, flip; };
 
@@ -52,11 +42,9 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v,
 // MAX_TAPS taps.
 __device__ __forceinline__ Box box_of(const unsigned char* src, const long long* index, const int* box, int b, int Nsrc, int Hs, int Ws, int C,
                                       int H, int W) {
-  long long f = index ? index[b] : b;
-  f = f < 0 ? 0 : (f > Nsrc - 1 ? Nsrc - 1 : f);
   const int* r = box + (size_t)b * 10;
   Box bx;
-  bx.frame = src + (size_t)f * Hs * Ws * C;
+  bx.frame = source_frame(src, index, b, Nsrc, Hs, Ws, C);
   bx.y0 = clampi(r[0], 0, Hs - 1);
   bx.h = clampi(r[1], 1, Hs - bx.y0);
   bx.Hv = clampi(r[2], max(H, (bx.h + 7) / 8), MAX_SIZE);
@@ -248,7 +236,7 @@ __global__ __launch_bounds__(256) void frames_prep_resize_kernel(const unsigned 
   const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
   const unsigned per_sample = (unsigned)tiles_x * tiles_y;
   const size_t total = (size_t)B * per_sample;
-  const int gh = patches ? H / p : 0, gw = patches ? W / p : 0, pd = 3 * p * p;
+  const FramesOut out = {patches, image, H, W, 3, p, patches ? H / p : 0, patches ? W / p : 0, 3 * p * p};
   const bool norm = mean != nullptr;
   const int vo = tid / (TW / 4), vg = tid % (TW / 4);   // the lane's tile row and group of 4 columns (tile_pass's vertical pass)
   for (size_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
@@ -289,11 +277,7 @@ __global__ __launch_bounds__(256) void frames_prep_resize_kernel(const unsigned 
             v[j] = finish(acc[c][j], norm, m, sd);
           }
         }
-        if (image) *(f32x4*)(image + (((size_t)b * 3 + c) * H + y) * W + x) = v;
-        if (patches) {
-          const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
-          *(u32x2*)(patches + (((size_t)b * gh + ph) * gw + pw) * pd + (c * p + kh) * p + kw) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-        }
+        out.store4(b, c, y, x, v);
       }
     }
   }
@@ -322,7 +306,7 @@ __global__ __launch_bounds__(256) void frames_prep_resize_generic_kernel(const u
                                                                          float* __restrict__ image, int B, int Nsrc, int Hs, int Ws, int C, int H,
                                                                          int W, int p, const int* __restrict__ rec, const float* __restrict__ lam) {
   const size_t total = (size_t)B * C * H * W;
-  const int gh = patches ? H / p : 0, gw = patches ? W / p : 0, pd = C * p * p;
+  const FramesOut out = {patches, image, H, W, C, p, patches ? H / p : 0, patches ? W / p : 0, C * p * p};
   const bool norm = mean != nullptr;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {      // i = the element of image
     size_t t = i;
@@ -344,11 +328,7 @@ __global__ __launch_bounds__(256) void frames_prep_resize_generic_kernel(const u
         v = blend(v, finish(rq, norm, norm ? mean[c] : 0.f, norm ? stdv[c] : 1.f), mr.l, mr.m);
       }
     }
-    if (image) image[i] = v;
-    if (patches) {
-      const int ph = y / p, kh = y - ph * p, pw = x / p, kw = x - pw * p;
-      patches[(((size_t)b * gh + ph) * gw + pw) * pd + (c * p + kh) * p + kw] = f2bf(v);
-    }
+    out.store1(i, b, c, y, x, v);
   }
 }
 
@@ -357,24 +337,17 @@ template <bool MIX>
 int frames_prep_resize(const unsigned char* src, const long long* index, const int* box, const float* mean, const float* std, void* patches_bf16,
                        float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, const int* rec, const float* lam,
                        void* stream) {
-  if (B < 1 || Nsrc < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || C < 1 || C > 4) return VITAMD_ERR_SHAPE;
-  if (Hs > MAX_SIZE || Ws > MAX_SIZE || H > MAX_SIZE || W > MAX_SIZE) return VITAMD_ERR_SHAPE;
-  if (patches_bf16 && (p < 1 || H % p != 0 || W % p != 0)) return VITAMD_ERR_SHAPE;
-  if (!index && Nsrc < B) return VITAMD_ERR_SHAPE;
-  const long long n_src = count(Nsrc, Hs, Ws, C), n_out = count(B, C, H, W);
-  if (n_src < 0 || n_out < 0) return VITAMD_ERR_SHAPE;
+  long long n_src, n_out;
+  if (std::max({Hs, Ws, H, W}) > MAX_SIZE || frames_shape(patches_bf16 != nullptr, index != nullptr, B, Nsrc, Hs, Ws, C, H, W, p, &n_src, &n_out)) return VITAMD_ERR_SHAPE;
   if (!src || !box || (mean == nullptr) != (std == nullptr) || (!patches_bf16 && !image) || (MIX && !rec)) return VITAMD_ERR_ARG;
   const hipStream_t st = (hipStream_t)stream;
   const bool aligned = ((uintptr_t)image & 15) == 0 && ((uintptr_t)patches_bf16 & 7) == 0;      // of the 16- and 8-byte stores
   if (C == 3 && W % 4 == 0 && (!patches_bf16 || p % 4 == 0) && aligned) {
     const size_t tiles = (size_t)B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
-    const dim3 grid((unsigned)(tiles < (size_t)RESIZE_GRID_CAP ? tiles : (size_t)RESIZE_GRID_CAP));
-    hipLaunchKernelGGL(frames_prep_resize_kernel<MIX>, grid, dim3(256), 0, st, src, index, box, mean, std, (__bf16*)patches_bf16, image, B, Nsrc,
+    hipLaunchKernelGGL(frames_prep_resize_kernel<MIX>, capped_grid(tiles, 1, RESIZE_GRID_CAP), dim3(256), 0, st, src, index, box, mean, std, (__bf16*)patches_bf16, image, B, Nsrc,
                        Hs, Ws, H, W, p, (size_t)n_src, ((uintptr_t)src & 3) == 0, rec, lam);
   } else {
-    const size_t wgs = ((size_t)n_out + 255) / 256;
-    const dim3 grid((unsigned)(wgs < (size_t)RESIZE_GRID_CAP ? wgs : (size_t)RESIZE_GRID_CAP));
-    hipLaunchKernelGGL(frames_prep_resize_generic_kernel<MIX>, grid, dim3(256), 0, st, src, index, box, mean, std, (__bf16*)patches_bf16, image,
+    hipLaunchKernelGGL(frames_prep_resize_generic_kernel<MIX>, capped_grid((size_t)n_out, 256, RESIZE_GRID_CAP), dim3(256), 0, st, src, index, box, mean, std, (__bf16*)patches_bf16, image,
                        B, Nsrc, Hs, Ws, C, H, W, p, rec, lam);
   }
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;

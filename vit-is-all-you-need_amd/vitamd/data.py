@@ -84,27 +84,35 @@ class Frames:
     .device, and PatchEmbedFn, the tokenizer losses and frames_to_tokens know what to ask of it."""
 
     def __init__(self, src_u8, size, index=None, geom=None, table=None):
+        def own(B, C):
+            if geom is not None and (not isinstance(geom, torch.Tensor) or geom.dtype != torch.int32 or tuple(geom.shape) != (B, 3)):
+                raise ValueError(f"Frames: geom must be int32 [{B}, 3]")
+            if table is not None and (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (C, 256)):
+                raise ValueError(f"Frames: table must be fp32 [{C}, 256]")
+        self._take("Frames", "DeviceLoader", src_u8, size, index, False, own)
+        self._geom = None if geom is None else geom.to(self.device).contiguous()
+        self._table = norm_table(channels=self.shape[1], device=self.device) if table is None else table.to(self.device).contiguous()
+
+    def _take(self, who, loader, src_u8, size, index, resize, own):
+        """What every frames class does with its source: the refusals of src_u8, size and index under the prefix `who` (resize: with
+        the resizing kernel's shape rules), then own(B, C) - the refusals of the class's further arguments, which need no device -
+        and only then the look at the device; sets _src, _index, shape, device and the empty cache of materialise."""
         if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
-            raise ValueError(f"Frames: expected a uint8 tensor, got {getattr(src_u8, 'dtype', type(src_u8).__name__)}")
+            raise ValueError(f"{who}: expected a uint8 tensor, got {getattr(src_u8, 'dtype', type(src_u8).__name__)}")
         if src_u8.dim() == 5:
             src_u8 = src_u8.reshape(-1, *src_u8.shape[2:])
         if index is not None and (not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1):
-            raise ValueError("Frames: index must be a 1-d int64 tensor")
+            raise ValueError(f"{who}: index must be a 1-d int64 tensor")
         H, W = _hw(size)
-        B, _, Hs, Ws, C, _, _ = ops.check_frames(src_u8.shape, (H, W), None, None if index is None else index.numel(), index is not None)
-        if geom is not None and (not isinstance(geom, torch.Tensor) or geom.dtype != torch.int32 or tuple(geom.shape) != (B, 3)):
-            raise ValueError(f"Frames: geom must be int32 [{B}, 3]")
-        if table is not None and (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (C, 256)):
-            raise ValueError(f"Frames: table must be fp32 [{C}, 256]")
+        B, _, _, _, C, _, _ = ops.check_frames(src_u8.shape, (H, W), None, None if index is None else index.numel(), index is not None,
+                                               resize=resize)
+        own(B, C)
         if not src_u8.is_cuda:
-            raise _lib.VitamdError("Frames: src_u8 must be on a ROCm device (DeviceLoader brings host batches over)")
-        dev = src_u8.device
+            raise _lib.VitamdError(f"{who}: src_u8 must be on a ROCm device ({loader} brings host batches over)")
         self._src = src_u8.contiguous()
-        self._index = None if index is None else index.to(dev).contiguous()
-        self._geom = None if geom is None else geom.to(dev).contiguous()
-        self._table = norm_table(channels=C, device=dev) if table is None else table.to(dev).contiguous()
+        self._index = None if index is None else index.to(src_u8.device).contiguous()
         self.shape = torch.Size((B, C, H, W))
-        self.device = dev
+        self.device = src_u8.device
         self._patches = {}
         self._image = None
 
@@ -113,8 +121,13 @@ class Frames:
         """the (y0, x0, flip) rows this batch was cut with, int32 [B, 3] on the device, or None"""
         return self._geom
 
+    def _launch(self, patch, image):
+        """the route of this class through the frame kernels: -> (patch rows or None, image or None), as ops.frames_prep hands them back"""
+        return ops.frames_prep(self._src, self.shape[2:], self._table, patch, image, self._index, self._geom)
+
     def materialise(self, patch=None, image=True):
-        """ONE launch for whatever of (patch rows at this patch size, fp32 image) is not there yet; both are kept.  -> self"""
+        """ONE launch (self._launch, the one thing a subclass changes) for whatever of (patch rows at this patch size, fp32 image) is not
+        there yet; both are kept.  -> self"""
         want_p = patch is not None and patch not in self._patches
         want_i = bool(image) and self._image is None
         if patch is not None and (not isinstance(patch, int) or isinstance(patch, bool) or patch < 1 or self.shape[2] % patch or self.shape[3] % patch):
@@ -123,7 +136,7 @@ class Frames:
             if self._src is None:
                 raise _lib.VitamdError(f"Frames: this batch was materialised by its loader and its source slot is reused; patch={patch}, "
                                        f"image={image} was not asked of the loader")
-            patches, img = ops.frames_prep(self._src, self.shape[2:], self._table, patch if want_p else None, want_i, self._index, self._geom)
+            patches, img = self._launch(patch if want_p else None, want_i)
             if want_p:
                 self._patches[patch] = patches
             if want_i:
@@ -202,20 +215,7 @@ class DeviceLoader:
         """a host batch, refused before anything touches the device"""
         if not (isinstance(batch, (tuple, list)) and len(batch) == 2):
             raise ValueError("DeviceLoader: host_iter must yield (uint8 frames, labels or None)")
-        u8, labels = batch
-        if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.is_cuda:
-            raise ValueError(f"DeviceLoader: frames must be a uint8 CPU tensor, got {getattr(u8, 'dtype', type(u8).__name__)}"
-                             f"{' on ' + str(u8.device) if isinstance(u8, torch.Tensor) else ''}")
-        if u8.dim() != 4:
-            raise ValueError(f"DeviceLoader: frames must be [B, Hs, Ws, C], got shape {tuple(u8.shape)}")
-        ops.check_frames(u8.shape, self.out_hw, self.patch)
-        if labels is not None and (not isinstance(labels, torch.Tensor) or labels.is_cuda or labels.dim() < 1 or labels.shape[0] != u8.shape[0]):
-            raise ValueError(f"DeviceLoader: labels must be a CPU tensor with one row per frame ({u8.shape[0]}) or None")
-        if self._slots is not None:
-            first = self._slots[0]["pinned"]
-            if tuple(u8.shape[1:]) != tuple(first.shape[1:]) or u8.shape[0] > first.shape[0]:
-                raise ValueError(f"DeviceLoader: a batch of shape {tuple(u8.shape)} does not fit the slots of the first one {tuple(first.shape)}")
-        return u8, labels
+        return self._check_frames("DeviceLoader", *batch)
 
     def _feed(self):
         """take the next host batch and start its copy into the next slot; False at the end of host_iter"""
@@ -289,3 +289,35 @@ class DeviceLoader:
         if self.train:
             return random_geom(n, src_hw, self.out_hw, self.seed, self.step, flip=True, device=self.device)
         return center_geom(n, src_hw, self.out_hw).to(self.device)
+
+    def _stage_over(self, stage, **host):
+        """One record of this step - host tensors of one row per sample, by name - to the device, in the order given: through entry
+        step % depth of `stage` (a list of `depth` entries the subclass keeps), pinned buffers that are rewritten only behind the
+        event of the copy that last read them (recorded `depth` batches earlier), with non_blocking copies on the current stream."""
+        st = stage[self.step % self.depth]
+        if st is None or any(st[k].shape[0] < t.shape[0] for k, t in host.items()):
+            st = {k: torch.zeros(t.shape, dtype=t.dtype).pin_memory() for k, t in host.items()}
+            st["done"] = torch.cuda.Event()
+            stage[self.step % self.depth] = st
+        st["done"].synchronize()           # host: the copy that last read these buffers is over (no-op when never recorded)
+        for k, t in host.items():
+            st[k][:t.shape[0]].copy_(t)
+        dev = tuple(st[k][:t.shape[0]].to(self.device, non_blocking=True) for k, t in host.items())
+        st["done"].record(torch.cuda.current_stream(self.device))
+        return dev
+
+    def _check_frames(self, who, u8, labels, resize=False):
+        """the frames and labels of a host batch and their fit into the slots (resize: under the resizing kernel's shape rules)"""
+        if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.is_cuda:
+            raise ValueError(f"{who}: frames must be a uint8 CPU tensor, got {getattr(u8, 'dtype', type(u8).__name__)}"
+                             f"{' on ' + str(u8.device) if isinstance(u8, torch.Tensor) else ''}")
+        if u8.dim() != 4:
+            raise ValueError(f"{who}: frames must be [B, Hs, Ws, C], got shape {tuple(u8.shape)}")
+        ops.check_frames(u8.shape, self.out_hw, self.patch, resize=resize)
+        if labels is not None and (not isinstance(labels, torch.Tensor) or labels.is_cuda or labels.dim() < 1 or labels.shape[0] != u8.shape[0]):
+            raise ValueError(f"{who}: labels must be a CPU tensor with one row per frame ({u8.shape[0]}) or None")
+        if self._slots is not None:
+            first = self._slots[0]["pinned"]
+            if tuple(u8.shape[1:]) != tuple(first.shape[1:]) or u8.shape[0] > first.shape[0]:
+                raise ValueError(f"{who}: a batch of shape {tuple(u8.shape)} does not fit the slots of the first one {tuple(first.shape)}")
+        return u8, labels

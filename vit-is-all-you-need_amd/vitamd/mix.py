@@ -20,7 +20,6 @@ import numpy as np
 import torch
 
 from . import data, lm, ops, resize
-from . import lib as _lib
 
 MODE_NONE, MODE_MIXUP, MODE_CUTMIX = 0, 1, 2
 
@@ -91,6 +90,12 @@ class MixedLabels:
     def __init__(self, a, b, lam):
         self.a, self.b, self.lam = a, b, lam
 
+    @classmethod
+    def of(cls, labels, pair):
+        """the labels of a batch mixed by pair = (rec, lam) on the device: b = labels[partner]"""
+        rec, lam = pair
+        return cls(labels, labels[rec[:, 0].long()], lam)
+
     def __iter__(self):
         return iter((self.a, self.b, self.lam))
 
@@ -109,20 +114,23 @@ class SoftTargetLoss:
         return lm.soft_cross_entropy(logits, labels, smoothing=self.smoothing)
 
 
-class MixedFrames(data.Frames):
-    """data.Frames whose samples are mixed with their partners on the way out of the prep kernel.  mix = (rec int32 [B, 6], lam fp32
-    [B]) on the device (Mix.draw brought over): what images() and patches(p) return is the mixed batch."""
+def _need_mix(mix, B, who):
+    """the (rec, lam) pair of a mixed batch of B samples, checked"""
+    if not (isinstance(mix, (tuple, list)) and len(mix) == 2):
+        raise ValueError(f"{who}: mix must be (rec int32 [B, 6], lam fp32 [B])")
+    rec, lam = mix
+    if not isinstance(rec, torch.Tensor) or rec.dtype != torch.int32 or tuple(rec.shape) != (B, 6):
+        raise ValueError(f"{who}: rec must be int32 [{B}, 6]")
+    if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or tuple(lam.shape) != (B,):
+        raise ValueError(f"{who}: lam must be fp32 [{B}]")
+    return rec, lam
 
-    def __init__(self, src_u8, size, index=None, geom=None, table=None, *, mix):
-        super().__init__(src_u8, size, index=index, geom=geom, table=table)
-        if not (isinstance(mix, (tuple, list)) and len(mix) == 2):
-            raise ValueError("MixedFrames: mix must be (rec int32 [B, 6], lam fp32 [B])")
-        rec, lam = mix
-        B = self.shape[0]
-        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.int32 or tuple(rec.shape) != (B, 6):
-            raise ValueError(f"MixedFrames: rec must be int32 [{B}, 6]")
-        if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or tuple(lam.shape) != (B,):
-            raise ValueError(f"MixedFrames: lam must be fp32 [{B}]")
+
+class _Mixed:
+    """what the two mixed frames classes share: the checked pair on the device, held once their base constructor has run"""
+
+    def _hold_mix(self, mix, who):
+        rec, lam = _need_mix(mix, self.shape[0], who)
         self._mix = (rec.to(self.device).contiguous(), lam.to(self.device).contiguous())
 
     @property
@@ -130,23 +138,17 @@ class MixedFrames(data.Frames):
         """(rec, lam) on the device, as this batch is mixed"""
         return self._mix
 
-    def materialise(self, patch=None, image=True):
-        """as Frames.materialise, through the mixing form of the kernel"""
-        want_p = patch is not None and patch not in self._patches
-        want_i = bool(image) and self._image is None
-        if patch is not None and (not isinstance(patch, int) or isinstance(patch, bool) or patch < 1 or self.shape[2] % patch or self.shape[3] % patch):
-            raise ValueError(f"Frames: patch {patch!r} does not tile the output {tuple(self.shape[2:])}")
-        if want_p or want_i:
-            if self._src is None:
-                raise _lib.VitamdError(f"Frames: this batch was materialised by its loader and its source slot is reused; patch={patch}, "
-                                       f"image={image} was not asked of the loader")
-            patches, img = ops.frames_prep(self._src, self.shape[2:], self._table, patch if want_p else None, want_i, self._index, self._geom,
-                                           mix=self._mix)
-            if want_p:
-                self._patches[patch] = patches
-            if want_i:
-                self._image = img
-        return self
+
+class MixedFrames(_Mixed, data.Frames):
+    """data.Frames whose samples are mixed with their partners on the way out of the prep kernel.  mix = (rec int32 [B, 6], lam fp32
+    [B]) on the device (Mix.draw brought over): what images() and patches(p) return is the mixed batch."""
+
+    def __init__(self, src_u8, size, index=None, geom=None, table=None, *, mix):
+        super().__init__(src_u8, size, index=index, geom=geom, table=table)
+        self._hold_mix(mix, "MixedFrames")
+
+    def _launch(self, patch, image):
+        return ops.frames_prep(self._src, self.shape[2:], self._table, patch, image, self._index, self._geom, mix=self._mix)
 
 
 class MixLoader(data.DeviceLoader):
@@ -155,7 +157,7 @@ class MixLoader(data.DeviceLoader):
     b = labels[partner].  With train=False it is DeviceLoader.  host_iter must yield int64 labels [B].
 
     The record crosses through `depth` pinned staging buffers with non_blocking copies on the current stream; a staging buffer is
-    rewritten only behind the event of the copy that last read it (recorded `depth` batches earlier), as the frame slots are."""
+    rewritten only behind the event of the copy that last read it (recorded `depth` batches earlier): DeviceLoader._stage_over."""
 
     def __init__(self, host_iter, device, size, mix, **kwargs):
         if any(k in kwargs for k in ("mode", "scale", "ratio", "resize_to")):
@@ -169,19 +171,7 @@ class MixLoader(data.DeviceLoader):
 
     def _staged(self, rec, lam):
         """the host record -> the device, through the staging buffer of this step"""
-        B = rec.shape[0]
-        st = self._stage[self.step % self.depth]
-        if st is None or st["rec"].shape[0] < B:
-            st = {"rec": torch.zeros((B, 6), dtype=torch.int32).pin_memory(), "lam": torch.zeros((B,), dtype=torch.float32).pin_memory(),
-                  "done": torch.cuda.Event()}
-            self._stage[self.step % self.depth] = st
-        st["done"].synchronize()           # host: the copy that last read these buffers is over (no-op when never recorded)
-        st["rec"][:B].copy_(rec)
-        st["lam"][:B].copy_(lam)
-        rec_dev = st["rec"][:B].to(self.device, non_blocking=True)
-        lam_dev = st["lam"][:B].to(self.device, non_blocking=True)
-        st["done"].record(torch.cuda.current_stream(self.device))
-        return rec_dev, lam_dev
+        return self._stage_over(self._stage, rec=rec, lam=lam)
 
     def _frames(self, src, geom, table):
         if not self.train:
@@ -194,23 +184,10 @@ class MixLoader(data.DeviceLoader):
             return super()._labels(labels)
         if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() != 1:
             raise ValueError("MixLoader: a mixed batch needs int64 labels [B] from host_iter")
-        rec, lam = self._pair
-        return MixedLabels(labels, labels[rec[:, 0].long()], lam)
+        return MixedLabels.of(labels, self._pair)
 
 
-def _need_mix(mix, B, who):
-    """the (rec, lam) pair of a mixed batch of B samples, checked as MixedFrames checks it"""
-    if not (isinstance(mix, (tuple, list)) and len(mix) == 2):
-        raise ValueError(f"{who}: mix must be (rec int32 [B, 6], lam fp32 [B])")
-    rec, lam = mix
-    if not isinstance(rec, torch.Tensor) or rec.dtype != torch.int32 or tuple(rec.shape) != (B, 6):
-        raise ValueError(f"{who}: rec must be int32 [{B}, 6]")
-    if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or tuple(lam.shape) != (B,):
-        raise ValueError(f"{who}: lam must be fp32 [{B}]")
-    return rec, lam
-
-
-class MixedResizedFrames(resize.ResizedFrames):
+class MixedResizedFrames(_Mixed, resize.ResizedFrames):
     """resize.ResizedFrames whose samples are mixed with their partners on the way out of the prep kernel (csrc/resize.hip,
     vitamd_frames_prep_resize_mix): every sample is resized with its own row of `box` and normalised, then mixed
     by mix = (rec int32 [B, 6], lam fp32 [B]) as MixedFrames mixes.  What images() and patches(p) return is the mixed batch."""
@@ -219,31 +196,10 @@ class MixedResizedFrames(resize.ResizedFrames):
         if isinstance(box, torch.Tensor) and box.dim() == 2:
             _need_mix(mix, box.shape[0], "MixedResizedFrames")       # before the base class looks at a device
         super().__init__(src_u8, size, box, index=index, mean=mean, std=std)
-        rec, lam = _need_mix(mix, self.shape[0], "MixedResizedFrames")
-        self._mix = (rec.to(self.device).contiguous(), lam.to(self.device).contiguous())
+        self._hold_mix(mix, "MixedResizedFrames")
 
-    @property
-    def mix(self):
-        """(rec, lam) on the device, as this batch is mixed"""
-        return self._mix
-
-    def materialise(self, patch=None, image=True):
-        """as Frames.materialise, through the resizing and mixing kernel"""
-        want_p = patch is not None and patch not in self._patches
-        want_i = bool(image) and self._image is None
-        if patch is not None and (not isinstance(patch, int) or isinstance(patch, bool) or patch < 1 or self.shape[2] % patch or self.shape[3] % patch):
-            raise ValueError(f"Frames: patch {patch!r} does not tile the output {tuple(self.shape[2:])}")
-        if want_p or want_i:
-            if self._src is None:
-                raise _lib.VitamdError(f"Frames: this batch was materialised by its loader and its source slot is reused; patch={patch}, "
-                                       f"image={image} was not asked of the loader")
-            patches, img = ops.frames_prep_resize_mix(self._src, self.shape[2:], patch if want_p else None, want_i, self._index, self._box,
-                                                      self._mean, self._std, *self._mix)
-            if want_p:
-                self._patches[patch] = patches
-            if want_i:
-                self._image = img
-        return self
+    def _launch(self, patch, image):
+        return ops.frames_prep_resize_mix(self._src, self.shape[2:], patch, image, self._index, self._box, self._mean, self._std, *self._mix)
 
 
 class ResizeMixLoader(resize.ResizeLoader):
@@ -273,20 +229,8 @@ class ResizeMixLoader(resize.ResizeLoader):
         return super()._check(batch)
 
     def _staged_mix(self, rec, lam):
-        """the host mix record -> the device, through the staging buffer of this step (MixLoader._staged)"""
-        B = rec.shape[0]
-        st = self._mix_stage[self.step % self.depth]
-        if st is None or st["rec"].shape[0] < B:
-            st = {"rec": torch.zeros((B, 6), dtype=torch.int32).pin_memory(), "lam": torch.zeros((B,), dtype=torch.float32).pin_memory(),
-                  "done": torch.cuda.Event()}
-            self._mix_stage[self.step % self.depth] = st
-        st["done"].synchronize()           # host: the copy that last read these buffers is over (no-op when never recorded)
-        st["rec"][:B].copy_(rec)
-        st["lam"][:B].copy_(lam)
-        rec_dev = st["rec"][:B].to(self.device, non_blocking=True)
-        lam_dev = st["lam"][:B].to(self.device, non_blocking=True)
-        st["done"].record(torch.cuda.current_stream(self.device))
-        return rec_dev, lam_dev
+        """the host mix record -> the device, through the staging buffer of this step (as MixLoader._staged)"""
+        return self._stage_over(self._mix_stage, rec=rec, lam=lam)
 
     def _frames(self, src, geom, table):
         if not self.train:
@@ -298,5 +242,4 @@ class ResizeMixLoader(resize.ResizeLoader):
     def _labels(self, labels):
         if not self.train:
             return super()._labels(labels)
-        rec, lam = self._pair
-        return MixedLabels(labels, labels[rec[:, 0].long()], lam)
+        return MixedLabels.of(labels, self._pair)

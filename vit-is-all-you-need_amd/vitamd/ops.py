@@ -1339,24 +1339,11 @@ def frames_prep(src, out_hw, table, patch=None, image=True, index=None, geom=Non
                 raise _lib.VitamdError(f"lam: expected [{B}], got {tuple(lam.shape)}")
     patches = torch.empty((B * (H // patch) * (W // patch), C * patch * patch), dtype=BF16, device=src.device) if patch is not None else None
     img = torch.empty((B, C, H, W), dtype=F32, device=src.device) if image else None
-    if resize is not None and mix is not None:
-        _lib.check(_L().vitamd_frames_prep_resize_mix(_p(src), _p(index), _p(resize[0]), _p(resize[1]), _p(resize[2]), _p(patches), _p(img), B,
-                                                      Nsrc, Hs, Ws, C, H, W, patch if patch is not None else 0, _p(mix[0]), _p(mix[1]), _stream()),
-                   f"frames_prep_resize_mix[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
-        return patches, img
-    if resize is not None:
-        _lib.check(_L().vitamd_frames_prep_resize(_p(src), _p(index), _p(resize[0]), _p(resize[1]), _p(resize[2]), _p(patches), _p(img), B, Nsrc,
-                                                  Hs, Ws, C, H, W, patch if patch is not None else 0, _stream()),
-                   f"frames_prep_resize[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
-        return patches, img
-    if mix is not None:
-        _lib.check(_L().vitamd_frames_prep_mix(_p(src), _p(index), _p(geom), _p(table), _p(patches), _p(img), B, Nsrc, Hs, Ws, C, H, W,
-                                               patch if patch is not None else 0, _p(mix[0]), _p(mix[1]), _stream()),
-                   f"frames_prep_mix[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
-        return patches, img
-    _lib.check(_L().vitamd_frames_prep(_p(src), _p(index), _p(geom), _p(table), _p(patches), _p(img), B, Nsrc, Hs, Ws, C, H, W,
-                                       patch if patch is not None else 0, _stream()),
-               f"frames_prep[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
+    # the four entries take the same arguments but for what cuts a sample (geom and table, or the resize record) and the mix record at the end
+    name = "frames_prep" + ("_resize" if resize is not None else "") + ("_mix" if mix is not None else "")
+    args = [_p(src), _p(index), *((_p(geom), _p(table)) if resize is None else (_p(v) for v in resize)), _p(patches), _p(img), B, Nsrc, Hs, Ws, C,
+            H, W, patch if patch is not None else 0, *(() if mix is None else (_p(mix[0]), _p(mix[1]))), _stream()]
+    _lib.check(getattr(_L(), "vitamd_" + name)(*args), f"{name}[B={B},src={Nsrc}x{Hs}x{Ws}x{C},out={H}x{W},p={patch}]")
     return patches, img
 
 

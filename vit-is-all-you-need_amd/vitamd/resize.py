@@ -20,7 +20,6 @@ import numpy as np
 import torch
 
 from . import data, ops
-from . import lib as _lib
 
 MAX_DOWN = 8                 # the kernel's down-scaling cap per axis (16 taps)
 _NORMS = {}                  # (device, mean, std) -> (mean, std) fp32 [C] on the device
@@ -179,58 +178,26 @@ class ResizedFrames(data.Frames):
     """A data.Frames whose samples are resized on the way out of the prep kernel.  src_u8 as Frames takes it, of any frame size; box
     int32 [B, 10] (rrc_boxes / resize_crop_boxes / resize_center_boxes, or any record of include/vitamd.h vitamd_frames_prep_resize);
     index int64 [B] or None; mean / std: C numbers each, or neither (v / 255).  The record carries crop and flip, so there is no geom
-    and no table.  Frames.__init__ refuses an output larger than the source, so this class has a constructor of its own."""
+    and no table.  The source goes through Frames._take with the resizing kernel's shape rules (an output larger than the source)."""
 
     def __init__(self, src_u8, size, box, index=None, mean=None, std=None):
-        if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
-            raise ValueError(f"ResizedFrames: expected a uint8 tensor, got {getattr(src_u8, 'dtype', type(src_u8).__name__)}")
-        if src_u8.dim() == 5:
-            src_u8 = src_u8.reshape(-1, *src_u8.shape[2:])
-        if index is not None and (not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1):
-            raise ValueError("ResizedFrames: index must be a 1-d int64 tensor")
-        H, W = data._hw(size)
-        B, _, Hs, Ws, C, _, _ = ops.check_frames(src_u8.shape, (H, W), None, None if index is None else index.numel(), index is not None,
-                                                 resize=True)
-        if not isinstance(box, torch.Tensor) or box.dtype != torch.int32 or tuple(box.shape) != (B, 10):
-            raise ValueError(f"ResizedFrames: box must be int32 [{B}, 10]")
-        if (mean is None) != (std is None):
-            raise ValueError("ResizedFrames: give mean and std together, or neither")
-        if not src_u8.is_cuda:
-            raise _lib.VitamdError("ResizedFrames: src_u8 must be on a ROCm device (ResizeLoader brings host batches over)")
-        dev = src_u8.device
-        self._src = src_u8.contiguous()
-        self._index = None if index is None else index.to(dev).contiguous()
-        self._geom = None
-        self._table = None
-        self._box = box.to(dev).contiguous()
-        self._mean, self._std = _norm(mean, std, C, dev, "ResizedFrames")
-        self.shape = torch.Size((B, C, H, W))
-        self.device = dev
-        self._patches = {}
-        self._image = None
+        def own(B, C):
+            if not isinstance(box, torch.Tensor) or box.dtype != torch.int32 or tuple(box.shape) != (B, 10):
+                raise ValueError(f"ResizedFrames: box must be int32 [{B}, 10]")
+            if (mean is None) != (std is None):
+                raise ValueError("ResizedFrames: give mean and std together, or neither")
+        self._take("ResizedFrames", "ResizeLoader", src_u8, size, index, True, own)
+        self._geom = self._table = None
+        self._box = box.to(self.device).contiguous()
+        self._mean, self._std = _norm(mean, std, self.shape[1], self.device, "ResizedFrames")
 
     @property
     def box(self):
         """the records this batch is cut with, int32 [B, 10] on the device"""
         return self._box
 
-    def materialise(self, patch=None, image=True):
-        """as Frames.materialise, through the resizing kernel"""
-        want_p = patch is not None and patch not in self._patches
-        want_i = bool(image) and self._image is None
-        if patch is not None and (not isinstance(patch, int) or isinstance(patch, bool) or patch < 1 or self.shape[2] % patch or self.shape[3] % patch):
-            raise ValueError(f"Frames: patch {patch!r} does not tile the output {tuple(self.shape[2:])}")
-        if want_p or want_i:
-            if self._src is None:
-                raise _lib.VitamdError(f"Frames: this batch was materialised by its loader and its source slot is reused; patch={patch}, "
-                                       f"image={image} was not asked of the loader")
-            patches, img = ops.frames_prep(self._src, self.shape[2:], None, patch if want_p else None, want_i, self._index,
-                                           resize=(self._box, self._mean, self._std))
-            if want_p:
-                self._patches[patch] = patches
-            if want_i:
-                self._image = img
-        return self
+    def _launch(self, patch, image):
+        return ops.frames_prep(self._src, self.shape[2:], None, patch, image, self._index, resize=(self._box, self._mean, self._std))
 
 
 class ResizeLoader(data.DeviceLoader):
@@ -242,7 +209,7 @@ class ResizeLoader(data.DeviceLoader):
     Yields (ResizedFrames already materialised, labels on the device).
 
     The record crosses through `depth` pinned staging buffers with non_blocking copies on the current stream; a staging buffer is
-    rewritten only behind the event of the copy that last read it (recorded `depth` batches earlier), as MixLoader stages its record.
+    rewritten only behind the event of the copy that last read it (recorded `depth` batches earlier): DeviceLoader._stage_over.
     Slots, copy stream and labels are DeviceLoader's."""
 
     def __init__(self, host_iter, device, size, mode="rrc", scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), resize_to=None, **kwargs):
@@ -255,25 +222,13 @@ class ResizeLoader(data.DeviceLoader):
         self._extents = collections.deque()          # of the batches fed and not yet handed out, in order
 
     def _check(self, batch):
-        """a host batch, refused before anything touches the device (DeviceLoader._check with the resizing kernel's shape rules)"""
+        """a host batch, refused before anything touches the device (DeviceLoader's checks with the resizing kernel's shape rules)"""
         if not (isinstance(batch, (tuple, list)) and len(batch) in (2, 3)):
             raise ValueError("ResizeLoader: host_iter must yield (uint8 frames, labels or None[, extents])")
-        u8, labels = batch[:2]
+        u8, labels = self._check_frames("ResizeLoader", *batch[:2], resize=True)
         extents = batch[2] if len(batch) == 3 else None
-        if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.is_cuda:
-            raise ValueError(f"ResizeLoader: frames must be a uint8 CPU tensor, got {getattr(u8, 'dtype', type(u8).__name__)}"
-                             f"{' on ' + str(u8.device) if isinstance(u8, torch.Tensor) else ''}")
-        if u8.dim() != 4:
-            raise ValueError(f"ResizeLoader: frames must be [B, Hs, Ws, C], got shape {tuple(u8.shape)}")
-        ops.check_frames(u8.shape, self.out_hw, self.patch, resize=True)
-        if labels is not None and (not isinstance(labels, torch.Tensor) or labels.is_cuda or labels.dim() < 1 or labels.shape[0] != u8.shape[0]):
-            raise ValueError(f"ResizeLoader: labels must be a CPU tensor with one row per frame ({u8.shape[0]}) or None")
         if extents is not None:
             _extents(u8.shape[0], tuple(u8.shape[1:3]), extents, "ResizeLoader")
-        if self._slots is not None:
-            first = self._slots[0]["pinned"]
-            if tuple(u8.shape[1:]) != tuple(first.shape[1:]) or u8.shape[0] > first.shape[0]:
-                raise ValueError(f"ResizeLoader: a batch of shape {tuple(u8.shape)} does not fit the slots of the first one {tuple(first.shape)}")
         self._extents.append(None if extents is None else extents.clone())
         return u8, labels
 
@@ -287,16 +242,7 @@ class ResizeLoader(data.DeviceLoader):
 
     def _staged(self, box):
         """the host record -> the device, through the staging buffer of this step"""
-        B = box.shape[0]
-        st = self._stage[self.step % self.depth]
-        if st is None or st["box"].shape[0] < B:
-            st = {"box": torch.zeros((B, 10), dtype=torch.int32).pin_memory(), "done": torch.cuda.Event()}
-            self._stage[self.step % self.depth] = st
-        st["done"].synchronize()           # host: the copy that last read this buffer is over (no-op when never recorded)
-        st["box"][:B].copy_(box)
-        box_dev = st["box"][:B].to(self.device, non_blocking=True)
-        st["done"].record(torch.cuda.current_stream(self.device))
-        return box_dev
+        return self._stage_over(self._stage, box=box)[0]
 
     def _geom(self, n, src_hw):
         return None                        # crop and flip are in the record
