@@ -493,6 +493,37 @@ int vitamd_crop_flip_draw(int* geom, int B, int Hs, int Ws, int H, int W, int fl
  * (ties to even), NaN -> 0: bit-equal to (x.clamp(0, 1) * 255).round().to(uint8) for finite input.  C in 1..4, all sizes >= 1,
  * at most 2^40 elements, else VITAMD_ERR_SHAPE; a NULL pointer: VITAMD_ERR_ARG.  Grid cap as vitamd_frames_prep. */
 int vitamd_frames_to_u8(const float* img, unsigned char* out, int B, int C, int H, int W, void* stream);
+/* Random Erasing on the finished batch: rewrites boxes of the two outputs of a vitamd_frames_prep* launch IN
+ * PLACE - image fp32 [B, C, H, W] and patches_bf16 [B*gh*gw, C*p*p], either of which may be NULL, not both - and touches nothing else.
+ * rec int32 [B, K, 5] on the device holds (mode, yl, yh, xl, xh) for box k of sample b, 1 <= K <= 8; fill fp32 [B, K, 4] on the
+ * device (NULL: zeros).  For yl <= y < yh and xl <= x < xh and every channel c:
+ *   mode 1:  image[b, c, y, x] = fill[b, k, c]
+ *   mode 2:  image[b, c, y, x] = z(seed, step, b, c, y, x), an N(0, 1) value (below)
+ * mode 0, any other mode and an empty box write nothing.  patches_bf16 gets the round-to-nearest-even of exactly the fp32 value image
+ * gets, in vitamd_im2col_bf16's layout: erasing both outputs keeps patches_bf16 the bits vitamd_im2col_bf16 makes of image.
+ * OVERLAP: a pixel covered by several boxes of its sample takes the value of the box with the largest k, decided per pixel, so every
+ * element has at most one writer: no read-modify-write, no atomics, the same bits on every call.  A pixel outside every box is
+ * neither read nor written.
+ * NOISE: z depends on (seed, step, b, c, y, x) alone - not on the box, k, p, B, K or which output is present.  One Philox4x32-10 call
+ * per four neighbouring pixels of a row: key (seed low, seed high), counter
+ *   ((c*H + y) * ceil(W/4) + (x >> 2),  (b << 2) | 2,  step low,  step high)
+ * (the low two bits of the second word keep it off vitamd_sample_logits' stream, 0, and vitamd_crop_flip_draw's, 1).  From its words
+ * w0..w3, in fp32 with the full-precision math functions:
+ *   u1 = ((w0 >> 8) + 1) * 2^-24   u2 = (w1 >> 8) * 2^-24   r = sqrtf(-2 logf(u1))   z0 = r cospif(2 u2)   z1 = r sinpif(2 u2)
+ * z2, z3 alike from (w2, w3); pixel x takes z[x & 3].  |z| <= sqrt(48 ln 2).
+ * CLAMPS, before any address forms: yl, yh into [0, H]; xl, xh into [0, W].
+ * Work is proportional to the erased area: workgroups are given (sample, box, one of 32 strips of the box), and one without a box ends
+ * after its record read.  Aligned groups of 4 pixels that are wholly their box's go out as one 16-byte fp32 and one 8-byte bf16 store where
+ * W % 4 == 0, p % 4 == 0 (with patches_bf16), image is 16-byte and patches_bf16 8-byte aligned; box edges and everything else one
+ * element at a time.  The grid is capped at vitamd_frames_erase_grid_cap() workgroups of 256 lanes with a stride loop beyond.
+ * VITAMD_ERR_SHAPE (answered first): B, H, W < 1; C outside 1..4; K outside 1..8; with patches_bf16 given p < 1, H % p != 0 or
+ * W % p != 0; B*C*H*W beyond 2^40 elements; B >= 2^30; C*H*ceil(W/4) beyond 2^32.  VITAMD_ERR_ARG: NULL rec, both outputs NULL.
+ * Nothing is launched in either case.  Only enqueues on `stream`; no backward.
+ * replaces timm's RandomErasing (--reprob, --remode const / rand / pixel) on the normalised fp32 device batch, and the im2col a
+ * caller of the fused feed would have to run again behind it. */
+int vitamd_frames_erase(void* patches_bf16, float* image, int B, int C, int H, int W, int p, const int* rec, const float* fill, int K,
+                        unsigned long long seed, unsigned long long step, void* stream);
+int vitamd_frames_erase_grid_cap(void);
 
 /* ---- helpers around the GEMMs ---------------------------------------------------------------- */
 /* fp32 -> bf16 (autocast's per-step weight / activation cast, train_vit.py:100). */

@@ -106,6 +106,12 @@ def parse_args(argv=None):
     p.add_argument("--mix_switch_prob", type=float, default=0.5, help="the chance of CutMix when both --mixup and --cutmix are on")
     p.add_argument("--label_smoothing", type=float, default=0.0,
                    help="label smoothing of the soft-target loss (vitamd.lm.soft_cross_entropy); also works on the fp32 batch")
+    p.add_argument("--reprob", type=float, default=0.0,
+                   help="Random Erasing: the chance that a sample is erased (0 = off; the DeiT / timm recipe takes 0.25); needs --u8 "
+                        "(vitamd.erase: the batch is erased after the mix, behind the prep launch)")
+    p.add_argument("--remode", type=str, default="pixel", choices=("const", "rand", "pixel"),
+                   help="what an erased box is filled with: zeros, one N(0, 1) value per channel, or one per pixel and channel")
+    p.add_argument("--recount", type=int, default=1, help="the most boxes an erased sample gets (their number is drawn from 1 .. this)")
     p.add_argument("--graph", action="store_true",
                    help="one graph launch per iteration (vitamd.graph.GraphedTrainStep): forward, loss, backward, the clip, the LR schedule "
                         "and the AdamW update, all replayed from the device; needs --dropout 0 (and not --u8)")
@@ -130,6 +136,9 @@ def main(argv=None):
     mixing = args.mixup > 0 or args.cutmix > 0
     if mixing and not args.u8:
         raise SystemExit("--mixup / --cutmix mix inside the device input feed (vitamd.mix.MixLoader): they need --u8")
+    erasing = args.reprob > 0
+    if (erasing or args.remode != "pixel" or args.recount != 1) and not args.u8:
+        raise SystemExit("--reprob / --remode / --recount erase the batch of the device input feed (vitamd.erase): they need --u8")
     if args.graph and args.label_smoothing > 0:
         raise SystemExit("--graph with --label_smoothing: the graphed step is built on the hard-label loss - use one or the other")
     resizing = args.rrc or args.resize is not None
@@ -155,7 +164,22 @@ def main(argv=None):
         u8 = torch.randint(0, 256, (args.bs, *src_hw, 3), generator=g, dtype=torch.uint8)
         host_labels = labels.cpu()
         host = ((u8, host_labels) for _ in range(args.train_steps))
-        if resizing and mixing:                                 # the DeiT recipe: RandomResizedCrop and the mix in one launch
+        if erasing:                                             # the loader chosen below, with the erasing launch behind its prep launch
+            from vitamd import erase as E
+            from vitamd.mix import Mix
+            er = dict(erase=E.Erase(args.reprob, mode=args.remode, max_count=args.recount, seed=0))
+            kw = dict(patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0, **er)
+            rs = dict(mode="rrc" if args.rrc else "resize_crop", scale=tuple(args.rrc_scale), resize_to=args.resize)
+            mix = Mix(args.mixup, args.cutmix, args.mix_prob, args.mix_switch_prob, label_smoothing=args.label_smoothing, seed=0)
+            if resizing and mixing:
+                feed = E.EraseResizeMixLoader(host, dev, args.image_size, mix, **rs, **kw)
+            elif resizing:
+                feed = E.EraseResizeLoader(host, dev, args.image_size, **rs, **kw)
+            elif mixing:
+                feed = E.EraseMixLoader(host, dev, args.image_size, mix, **kw)
+            else:
+                feed = E.EraseLoader(host, dev, args.image_size, **kw)
+        elif resizing and mixing:                                 # the DeiT recipe: RandomResizedCrop and the mix in one launch
             from vitamd.mix import Mix, ResizeMixLoader
             mix = Mix(args.mixup, args.cutmix, args.mix_prob, args.mix_switch_prob, label_smoothing=args.label_smoothing, seed=0)
             feed = ResizeMixLoader(host, dev, args.image_size, mix, mode="rrc" if args.rrc else "resize_crop", scale=tuple(args.rrc_scale),

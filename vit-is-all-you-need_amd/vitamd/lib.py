@@ -108,6 +108,8 @@ SIGNATURES = {
     "vitamd_frames_prep_grid_cap": [],
     "vitamd_crop_flip_draw": [_P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P],
     "vitamd_frames_to_u8": [_P, _P, _I, _I, _I, _I, _P],
+    "vitamd_frames_erase": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _U64, _U64, _P],
+    "vitamd_frames_erase_grid_cap": [],
     "vitamd_tanh_bf16": [_P, _P, _L, _P],
     "vitamd_tanh_bwd_bf16": [_P, _P, _P, _L, _P],
     "vitamd_recon_l1_fwd": [_P, _I, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],

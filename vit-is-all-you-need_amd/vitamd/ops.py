@@ -1453,3 +1453,63 @@ def recon_l1_bwd(tokens, images, grid, patch, g_loss=None, g_recon=None, out=Non
     _lib.check(_L().vitamd_recon_l1_bwd(_p(tokens), is_bf16, _p(images), _p(g_loss), _p(g_recon), _p(out), B, grid, patch, c, ld, out.stride(0),
                                         _stream()), f"recon_l1_bwd[B={B},G={grid},p={patch},c={c},ld={ld}]")
     return out
+
+
+# ------------------------------------------------------------------------------------------ Random Erasing on the finished batch
+ERASE_MAX_BOXES = 8         # include/vitamd.h vitamd_frames_erase: K, the boxes one sample's record holds
+
+
+def frames_erase_grid_cap():
+    """workgroups one launch of the erasing kernel has at most (asked of the library); more (sample, box, strip) units make it loop"""
+    return int(_L().vitamd_frames_erase_grid_cap())
+
+
+def frames_erase(patches, image, patch, rec, fill, seed, step, hw=None):
+    """Random Erasing IN PLACE on the outputs of frames_prep (include/vitamd.h vitamd_frames_erase): patches bf16 [B*gh*gw, C*patch*patch]
+    or None, image fp32 [B, C, H, W] or None (not both None); rec int32 [B, K, 5] = (mode, yl, yh, xl, xh), K <= 8, and fill fp32
+    [B, K, 4] or None (zeros), on the same device.  Mode 1 writes fill[b, k, c], mode 2 the N(0, 1) value of (seed, step, b, c, y, x); a
+    pixel under several boxes takes the one with the largest k; nothing outside the boxes is touched.  hw = (H, W): needed without an
+    image, which otherwise says it.  seed and step are Python integers in [0, 2^64).  Returns nothing."""
+    if patches is None and image is None:
+        raise ValueError("frames_erase: nothing to erase (give patches, image, or both)")
+    if not isinstance(rec, torch.Tensor) or rec.dtype != torch.int32 or rec.dim() != 3 or rec.shape[2] != 5 or not 1 <= rec.shape[1] <= ERASE_MAX_BOXES \
+            or rec.shape[0] < 1:
+        raise ValueError(f"frames_erase: rec must be int32 [B, K <= {ERASE_MAX_BOXES}, 5], got {getattr(rec, 'dtype', type(rec).__name__)} "
+                         f"{tuple(getattr(rec, 'shape', ()))}")
+    B, K = int(rec.shape[0]), int(rec.shape[1])
+    if fill is not None and (not isinstance(fill, torch.Tensor) or fill.dtype != F32 or tuple(fill.shape) != (B, K, 4)):
+        raise ValueError(f"frames_erase: fill must be fp32 [{B}, {K}, 4] or None")
+    for name, v in (("seed", seed), ("step", step)):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < 1 << 64:
+            raise ValueError(f"frames_erase: {name} must be an integer in [0, 2^64), got {v!r}")
+    if image is not None:
+        if not isinstance(image, torch.Tensor) or image.dim() != 4 or image.shape[0] != B or not 1 <= image.shape[1] <= 4 or min(image.shape) < 1:
+            raise ValueError(f"frames_erase: image must be fp32 [{B}, C <= 4, H, W], got shape {tuple(getattr(image, 'shape', ()))}")
+        if hw is not None and tuple(int(v) for v in hw) != tuple(image.shape[2:]):
+            raise ValueError(f"frames_erase: hw {tuple(hw)} is not the image's {tuple(image.shape[2:])}")
+        hw = tuple(image.shape[2:])
+    elif not (isinstance(hw, (tuple, list, torch.Size)) and len(hw) == 2 and all(isinstance(v, int) and v >= 1 for v in hw)):
+        raise ValueError("frames_erase: patch rows alone do not say (H, W): give hw=")
+    H, W = int(hw[0]), int(hw[1])
+    C = None if image is None else int(image.shape[1])
+    if patches is not None:
+        if not isinstance(patch, int) or isinstance(patch, bool) or patch < 1 or H % patch or W % patch:
+            raise ValueError(f"frames_erase: patch {patch!r} does not tile {(H, W)}")
+        rows = B * (H // patch) * (W // patch)
+        if not isinstance(patches, torch.Tensor) or patches.dim() != 2 or patches.shape[0] != rows or patches.shape[1] % (patch * patch) \
+                or not 1 <= patches.shape[1] // (patch * patch) <= 4 or (C is not None and patches.shape[1] != C * patch * patch):
+            raise ValueError(f"frames_erase: patches must be bf16 [{rows}, C * {patch * patch}] with C "
+                             f"{'in 1..4' if C is None else '= ' + str(C)}, got shape {tuple(getattr(patches, 'shape', ()))}")
+        C = int(patches.shape[1]) // (patch * patch)
+        _need(patches, BF16, "patches", 2)
+    if image is not None:
+        _need(image, F32, "image", 4)
+    _need(rec, torch.int32, "rec", 3)
+    if fill is not None:
+        _need(fill, F32, "fill", 3)
+    dev = (patches if patches is not None else image).device
+    if any(t is not None and t.device != dev for t in (image, rec, fill)):
+        raise _lib.VitamdError("frames_erase: patches, image, rec and fill must be on one device")
+    with torch.cuda.device(dev):
+        _lib.check(_L().vitamd_frames_erase(_p(patches), _p(image), B, C, H, W, patch if patches is not None else 0, _p(rec), _p(fill), K, seed, step,
+                                            _stream()), f"frames_erase[B={B},C={C},out={H}x{W},p={patch},K={K}]")
