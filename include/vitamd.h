@@ -95,6 +95,26 @@ int vitamd_gemm_nt_bf16(const void* A, const void* B, void* out, void* out2, con
 #define VITAMD_NT_FORM_TAIL_SPLIT 0x80
 int vitamd_gemm_nt_plan(int M, int N, int K, int ldo, int epi, int tile);
 
+/* vitamd_gemm_nt_bf16 with a caller's workspace (added to ABI 9: no signature changed).  A launch that would take the 128x128 kernel on fewer
+ * tiles than the device has CUs - a few hundred rows against a whole weight: the kept-row layer, the classifier head - leaves most of the chip
+ * idle while each workgroup walks the whole K loop alone.  With `ws` it runs the SPLIT-K form instead: tiles x splits workgroups, each one tile
+ * and one K range, storing fp32 partial tiles to `ws` with plain stores, then a reduce pass that sums them in split order and applies the
+ * epilogue.  No atomics, no waiting between workgroups: the same inputs give the same bits, which differ from the unsplit kernel's by fp32
+ * summation order only.  Split: `tile` one of the automatic codes (0, 512, 1024; explicit codes keep their meaning), one 128x128-kernel launch
+ * (no row panels, no tail split), epilogue not VITAMD_EPI_PATCH_F32 (colsum, where given, is added to by the reduce pass).  splits = 0: the rule - M <= 256 (two tile rows) and
+ * floor(CUs / (2 N/128)) splits, every split at least 2 K-tiles of 64: a function of N, K and the device alone, so that a row's sum does not
+ * depend on how many rows the launch has; splits = n > 0: n splits whatever the shape (capped at K / 128); 1: never split.  Everything else,
+ * and ws == NULL, is vitamd_gemm_nt_bf16 unchanged.  vitamd_gemm_nt_ws_bytes: the bytes of `ws` the call needs (0: it does not split;
+ * negative: -VITAMD_ERR_*; a shorter ws_bytes is VITAMD_ERR_ARG).  vitamd_gemm_nt_ws_plan: vitamd_gemm_nt_plan's
+ * answer for the call, or VITAMD_NT_FORM_SPLITK | 128 << 8 | splits << 16.  (vitamd_gemm_nt_plan keeps describing vitamd_gemm_nt_bf16, which
+ * has no workspace and never splits.) */
+#define VITAMD_NT_FORM_SPLITK 6         /* 128x128 tiles, split-K partials + reduce pass (vitamd_gemm_nt_bf16_ws only) */
+int vitamd_gemm_nt_bf16_ws(const void* A, const void* B, void* out, void* out2, const float* bias, const void* aux,
+                           float* colsum, int M, int N, int K, int ldo, int epi, int n_patches, int seq, int extra,
+                           int tile, int splits, float* ws, long ws_bytes, void* stream);
+long vitamd_gemm_nt_ws_bytes(int M, int N, int K, int ldo, int epi, int tile, int splits);
+int vitamd_gemm_nt_ws_plan(int M, int N, int K, int ldo, int epi, int tile, int splits);
+
 /* fc2 with dropout: out f32 = resid + dropout_p(bf16(A.B^T + bias)), mask = hash(seed, row*N+col).
  * replaces transformer.py:39-40,44 (Linear + nn.Dropout(p) + residual add) in training mode.  `tile` as for vitamd_gemm_nt_bf16 (0, 128,
  * 256, 320, 512, 1024), and so are the size rules: out and resid (M x N x 4 bytes) of 2^31 bytes or more are served in row panels whose
@@ -162,6 +182,16 @@ int vitamd_layernorm_fwd_keep(const float* x_in, const void* addend_bf16, float*
 int vitamd_layernorm_bwd_keep(const void* dy_bf16, const void* x_or_y, const float* mean, const float* rstd, const float* g_res,
                               float* g_out, void* g_bf16, float* colsum, int B, int seq, int keep, int D, int use_xhat,
                               float dropout_p, unsigned long long seed, void* stream);
+/* Forward with up to two bf16 addends and an optional stream store (added to ABI 9: no signature changed): s = fl(x_in + addend1), then
+ * s = fl(s + addend2) when addend2_bf16 is given; y, mean, rstd = LN(s); x_out = s when x_out is given (NULL: no stream store).  The bits of
+ * vitamd_layernorm_fwd(x_in, addend1) followed by vitamd_layernorm_fwd(its x_out, addend2), in one pass over x_in: a caller that needs the
+ * intermediate sum only as the second LayerNorm's input does not store it.  addend1_bf16 is required; any D % 4 == 0. */
+int vitamd_layernorm_fwd_add2(const float* x_in, const void* addend1_bf16, const void* addend2_bf16, float* x_out, void* y_bf16, float* mean,
+                              float* rstd, int M, int D, float eps, void* stream);
+/* Its kept-row form: output row b*keep + t = LN(fl(fl(x_in[b*seq + t] + addend1[b*seq + t]) + addend2[b*keep + t])).  x_in and addend1 are
+ * full size [B*seq, D]; addend2 (required), x_out (optional), y, mean and rstd are compact [B*keep, ...]. */
+int vitamd_layernorm_fwd_keep_add2(const float* x_in, const void* addend1_bf16, const void* addend2_bf16, float* x_out, void* y_bf16,
+                                   float* mean, float* rstd, int B, int seq, int keep, int D, float eps, void* stream);
 
 /* Affine LayerNorm (nn.LayerNorm weight/bias) for the `blocks.py` surface (blocks.py:43,48,179,184).
  * forward: y = bf16(LN(x) * gamma + beta).  backward: g_out = (g_res or 0) + dLN/dx; dgamma, dbeta are

@@ -31,6 +31,39 @@ extern "C" int vitamd_gemm_nt_plan(int M, int N, int K, int ldo, int epi, int ti
   return vitamd_gemm_nt_plan_impl(p);
 }
 
+// vitamd_gemm_nt_bf16 with a caller's workspace: launches that take the 128 x 128 kernel on fewer tiles than CUs run its split-K form + reduce pass.
+extern "C" int vitamd_gemm_nt_bf16_ws(const void* A, const void* B, void* out, void* out2, const float* bias, const void* aux,
+                                      float* colsum, int M, int N, int K, int ldo, int epi, int n_patches, int seq, int extra,
+                                      int tile, int splits, float* ws, long ws_bytes, void* stream) {
+  const int dg = (epi == 6 || epi == 7) ? 1 : 0;
+  if (epi == 6) epi = EPI_GELU;
+  if (epi == 7) epi = EPI_DGELU;
+  GemmNtArgs p{A, B, out, out2, bias, aux, colsum, M, N, K, ldo, epi, n_patches, seq, extra, tile, 0u, 1.0f, 0u, 0u, 0, dg};
+  if (!is_auto(tile) && tile != NT_TILE_128 && tile != NT_TILE_256 && tile != NT_TILE_320 && tile != NT_TILE_LOADER && tile != NT_TILE_SEAM) return VITAMD_ERR_ARG;
+  return vitamd_gemm_nt_ws_impl(p, splits, ws, (size_t)(ws_bytes < 0 ? 0 : ws_bytes), (hipStream_t)stream);
+}
+
+static GemmNtArgs nt_query_args(int M, int N, int K, int ldo, int epi, int tile) {
+  const int dg = (epi == 6 || epi == 7) ? 1 : 0;
+  if (epi == 6) epi = EPI_GELU;
+  if (epi == 7) epi = EPI_DGELU;
+  static char dummy[16];                   // the launch rules only ask whether the optional pointers are present
+  return GemmNtArgs{dummy, dummy, dummy, dummy, nullptr, dummy, nullptr, M, N, K, ldo, epi, 1, 1, 0, tile, 0u, 1.0f, 0u, 0u, 0, dg};
+}
+static bool nt_tile_code_ok(int tile) {
+  return is_auto(tile) || tile == NT_TILE_128 || tile == NT_TILE_256 || tile == NT_TILE_320 || tile == NT_TILE_LOADER || tile == NT_TILE_SEAM;
+}
+
+extern "C" long vitamd_gemm_nt_ws_bytes(int M, int N, int K, int ldo, int epi, int tile, int splits) {
+  if (!nt_tile_code_ok(tile) || splits < 0) return -VITAMD_ERR_ARG;
+  return vitamd_gemm_nt_ws_bytes_impl(nt_query_args(M, N, K, ldo, epi, tile), splits);
+}
+
+extern "C" int vitamd_gemm_nt_ws_plan(int M, int N, int K, int ldo, int epi, int tile, int splits) {
+  if (!nt_tile_code_ok(tile) || splits < 0) return -VITAMD_ERR_ARG;
+  return vitamd_gemm_nt_ws_plan_impl(nt_query_args(M, N, K, ldo, epi, tile), splits);
+}
+
 extern "C" int vitamd_gemm_tn_bf16(const void* L, const void* Rm, float* out, int R, int P, int Q, int ldl, int ldr, int ldo,
                                    int splits, void* stream) {
   GemmTnArgs a{L, Rm, out, R, P, Q, ldl, ldr, ldo, splits, nullptr, 0, 1, 0};

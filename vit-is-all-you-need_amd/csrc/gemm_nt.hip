@@ -22,8 +22,11 @@
 
 namespace {
 
-template <int BM, int BN, int WM, int WN, int EPI>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNtArgs p) {
+// SPLIT (split-K form, for launches with fewer tiles than CUs: launch_splitk below): the grid is tiles x splits; a workgroup takes one tile and the
+// K-tiles [split * nkt / splits, (split + 1) * nkt / splits) and stores its fp32 accumulators to `ws` with plain stores, in the accumulator
+// layout ([split][tile][i * NT + j][thread] f32x4: 1 KiB per wave-instruction); gemm_nt_splitk_reduce sums them and runs the epilogue.  EPI is unused.
+template <int BM, int BN, int WM, int WN, int EPI, bool SPLIT = false>
+__global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNtArgs p, float* __restrict__ ws = nullptr, int splits = 1) {
   constexpr int NW = WM * WN;
   constexpr int WTM = BM / WM, WTN = BN / WN;   // wave tile
   constexpr int MT = WTM / 16, NT = WTN / 16;   // 16x16 accumulator tiles per wave
@@ -41,7 +44,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNtArgs 
 
   const int tiles_n = (p.N + BN - 1) / BN;
   const int tiles_m = (p.M + BM - 1) / BM;
-  const int tile = xcd_remap(blockIdx.x, tiles_m * tiles_n);
+  int bid = blockIdx.x, split = 0;
+  if constexpr (SPLIT) {
+    split = bid / (tiles_m * tiles_n);
+    bid -= split * (tiles_m * tiles_n);
+  }
+  const int tile = xcd_remap(bid, tiles_m * tiles_n);
   const int m0 = (tile / tiles_n) * BM;
   const int n0 = (tile % tiles_n) * BN;
 
@@ -84,12 +92,17 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNtArgs 
   const int b_off = BM * 128 + wn * WTN * 128 + frag_off;
 
   const int nkt = K / BK;
-  stage(0, 0);
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int cur = kt & 1;
+  int kt0 = 0, kt1 = nkt;
+  if constexpr (SPLIT) {
+    kt0 = (int)((long)split * nkt / splits);
+    kt1 = (int)((long)(split + 1) * nkt / splits);
+  }
+  stage(kt0, 0);
+  for (int kt = kt0; kt < kt1; ++kt) {
+    const int cur = (kt - kt0) & 1;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // tile kt landed for everyone; everyone finished reading buffer cur^1
-    if (kt + 1 < nkt) stage(kt + 1, cur ^ 1);
+    if (kt + 1 < kt1) stage(kt + 1, cur ^ 1);
     const char* buf = smem + cur * BUF_BYTES;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -105,6 +118,14 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNtArgs 
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
     }
   }
+  if constexpr (SPLIT) {
+    float* w = ws + ((size_t)split * (tiles_m * tiles_n) + tile) * (BM * BN) + tid * 4;
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) *(f32x4*)(w + (i * NT + j) * (NW * 64 * 4)) = acc[i][j];
+    return;
+  }
   if constexpr (BM == 256 && BN == 256 && WM == 2 && WN == 4 && EPI != EPI_F32) {
     if (p.N % 8 == 0 && p.ldo % 8 == 0) {
       gemm_epilogue_rows<EPI>(p, acc, m0, n0, wm, wn, lane, tid, wave, smem);
@@ -112,6 +133,42 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNtArgs 
     }
   }
   gemm_epilogue<BN, WM, WN, WTM, WTN, MT, NT, EPI>(p, acc, m0, n0, wm, wn, lane, tid, smem);
+}
+
+// The reduce pass of the split-K form of gemm_nt_kernel<128, 128, 2, 2>: one workgroup per 16 x 16-per-wave unit (i, j) of a tile - 16 per tile, so
+// the pass has 16 times the GEMM's tile count in workgroups - sums that unit's partials in split order (the same bits in every run, no atomics)
+// and runs gemm_epilogue on it as a 1 x 1 accumulator tile whose origin is moved by (16 i, 16 j).  A thread reads one f32x4 per split, 4 KiB
+// contiguous per workgroup.
+template <int EPI>
+__global__ __launch_bounds__(256) void gemm_nt_splitk_reduce(const GemmNtArgs p, const float* __restrict__ ws, int splits) {
+  constexpr int BM = 128, BN = 128, WM = 2, WN = 2, WTM = BM / WM, WTN = BN / WN, MT = WTM / 16, NT = WTN / 16;
+  __shared__ float red[WM * BN];              // gemm_epilogue's column-sum scratch (EPI_DGELU with colsum)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
+  const int tile = blockIdx.x / (MT * NT), unit = blockIdx.x % (MT * NT);
+  const int m0 = (tile / tiles_n) * BM + (unit / NT) * 16;
+  const int n0 = (tile % tiles_n) * BN + (unit % NT) * 16;
+  const float* w = ws + ((size_t)tile * (MT * NT) + unit) * (256 * 4) + tid * 4;
+  const size_t stride = (size_t)tiles_m * tiles_n * (BM * BN);
+  f32x4 acc[1][1];
+  acc[0][0] = *(const f32x4*)w;
+  int s = 1;
+  for (; s + 4 <= splits; s += 4) {           // four loads in flight; added in split order
+    const f32x4 a = *(const f32x4*)(w + s * stride), b = *(const f32x4*)(w + (s + 1) * stride);
+    const f32x4 c = *(const f32x4*)(w + (s + 2) * stride), d = *(const f32x4*)(w + (s + 3) * stride);
+    acc[0][0] += a; acc[0][0] += b; acc[0][0] += c; acc[0][0] += d;
+  }
+  for (; s < splits; ++s) acc[0][0] += *(const f32x4*)(w + s * stride);
+  if constexpr (EPI == EPI_DGELU) {
+    // column sums (the path with BIAS_FROM_WGRAD off): gemm_epilogue fills the 2 x 16 columns of this unit in `red` and adds all 128 to colsum
+    // with atomics - the others must be zeros (an atomic add of 0.0 to a column another unit sums)
+    if (p.colsum) {
+      for (int c = tid; c < WM * BN; c += 256) red[c] = 0.f;
+      __syncthreads();
+    }
+  }
+  gemm_epilogue<BN, WM, WN, WTM, WTN, 1, 1, EPI>(p, acc, m0, n0, wm, wn, lane, tid, (char*)red);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -230,7 +287,20 @@ int launch(const GemmNtArgs& p, hipStream_t stream) {
   auto kern = gemm_nt_kernel<BM, BN, WM, WN, EPI>;
   if (int e = set_lds(kern, lds)) return e;
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(WM * WN * 64), lds, stream, p);
+  hipLaunchKernelGGL(kern, dim3(tiles), dim3(WM * WN * 64), lds, stream, p, (float*)nullptr, 1);
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+// Split-K form of the 128 x 128 kernel + its reduce pass: splits * tiles * 64 KiB of `ws`.
+constexpr size_t NT_SPLITK_TILE_BYTES = 128 * 128 * 4;
+template <int EPI>
+int launch_splitk(const GemmNtArgs& p, float* ws, int splits, hipStream_t stream) {
+  constexpr int lds = 2 * (128 + 128) * 128;
+  auto kern = gemm_nt_kernel<128, 128, 2, 2, EPI_F32, true>;
+  if (int e = set_lds(kern, lds)) return e;
+  const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
+  hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(256), lds, stream, p, ws, splits);
+  hipLaunchKernelGGL(gemm_nt_splitk_reduce<EPI>, dim3(tiles * 16), dim3(256), 0, stream, p, (const float*)ws, splits);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 
@@ -321,7 +391,7 @@ namespace {
 
 // ---- which kernel a launch takes (one place: the dispatcher below executes the plan, vitamd_gemm_nt_plan reports it) -------------------------
 // the tile selector of the C ABI: NtTileCode (vitamd_internal.h)
-enum NtForm { NT_FORM_SMALL = 1, NT_FORM_PP = 2, NT_FORM_PP_PERSISTENT = 3, NT_FORM_SEAM = 4, NT_FORM_LOADER = 5 };
+enum NtForm { NT_FORM_SMALL = 1, NT_FORM_PP = 2, NT_FORM_PP_PERSISTENT = 3, NT_FORM_SEAM = 4, NT_FORM_LOADER = 5, NT_FORM_SPLITK = 6 };
 struct NtPlan { int form, rows, err; };
 
 static NtPlan plan_single(const GemmNtArgs& p) {
@@ -503,6 +573,71 @@ static int plan_rows(const GemmNtArgs& p) {
   const NtPlan pl = plan_single(head_of(p, rows_a, tall));
   if (pl.err) return -pl.err;
   return pl.form | (pl.rows << 8) | (rows_a ? 0x80 : 0);
+}
+
+// ---- split-K for launches that leave most of the chip idle (the kept-row layer and the classifier head: M = 256 rows are 2 x N/128 tiles, each
+// walking up to 48 K-tiles alone).  Only the automatic tile codes, only launches plan_single sends to the 128 x 128 kernel as ONE launch (no row
+// panels, no tail split), only the epilogues the reduce pass serves (all but the patch embedding).  Whether the caller asks for column sums does not
+// enter: the launch with and the launch without them must give the same `out` (tests/test_gpu_tn_colsum.py holds BIAS_FROM_WGRAD on against off).
+// The rule (want = 0): launches of at most 256 rows - two tile rows - and the split count a function of N, K and the device ALONE: as many as
+// keep 2 x N/128 tiles x splits within the CU count, every split at least 2 K-tiles (its double buffer fills once).  The K ranges, and with them
+// the order in which a row's products are summed, then do not depend on how many rows the launch has: a sample's result is the same bits in a
+// batch of 32 and in a batch of 256 (tests/test_gpu_parity.py::test_full_size_properties holds the step to that), at the price of half the
+// chip for M <= 128.  `want` > 0 asks for that many splits (still at least 2 K-tiles each) whatever the shape.  1 = the launch stays what it is.
+static int splitk_count(const GemmNtArgs& p, int want) {
+  if (want < 0 || !is_auto(p.tile) || p.epi == EPI_PATCH_F32) return 1;
+  if (panel_rows(p) < p.M) return 1;
+  bool tall = false;
+  if (tail_split_rows(p, tall)) return 1;
+  const NtPlan pl = plan_single(p);
+  if (pl.err || pl.form != NT_FORM_SMALL) return 1;
+  const int cap = p.K / BK / 2;
+  long s = want;
+  if (want == 0) {
+    const long tiles = 2L * ((p.N + 127) / 128);
+    const int cus = device_cus();
+    if (p.M > 256 || tiles >= cus) return 1;
+    s = cus / tiles;
+  }
+  if (s > cap) s = cap;
+  return s < 1 ? 1 : (int)s;
+}
+
+// bytes of workspace vitamd_gemm_nt_ws_impl needs for this call (0: it does not split), or -VITAMD_ERR_*
+long vitamd_gemm_nt_ws_bytes_impl(const GemmNtArgs& p, int splits) {
+  if (int e = check_args(p)) return -e;
+  const int s = splitk_count(p, splits);
+  return s <= 1 ? 0 : (long)(s * (size_t)((p.M + 127) / 128) * ((p.N + 127) / 128) * NT_SPLITK_TILE_BYTES);
+}
+
+// form | rows << 8 | splits << 16 of what vitamd_gemm_nt_ws_impl would do with a large enough workspace
+int vitamd_gemm_nt_ws_plan_impl(const GemmNtArgs& p, int splits) {
+  const int plain = vitamd_gemm_nt_plan_impl(p);
+  if (plain < 0) return plain;
+  const int s = splitk_count(p, splits);
+  return s <= 1 ? plain : (NT_FORM_SPLITK | (128 << 8) | (s << 16));
+}
+
+// vitamd_gemm_nt_impl with a caller's workspace: the split-K form where splitk_count says so and `ws` is given, the plain launch otherwise
+int vitamd_gemm_nt_ws_impl(const GemmNtArgs& p0, int splits, float* ws, size_t ws_bytes, hipStream_t stream) {
+  if (int e = check_args(p0)) return e;
+  if (splits < 0) return VITAMD_ERR_ARG;
+  const int s = ws ? splitk_count(p0, splits) : 1;
+  if (s <= 1) return vitamd_gemm_nt_impl(p0, stream);
+  if ((size_t)s * ((p0.M + 127) / 128) * ((p0.N + 127) / 128) * NT_SPLITK_TILE_BYTES > ws_bytes) return VITAMD_ERR_ARG;
+  GemmNtArgs p = p0;
+  if (p.epi == EPI_GELU) {
+    p.gelu_tab = gelu_table();
+    if (!p.gelu_tab) return VITAMD_ERR_INIT;
+  }
+  switch (p.epi) {
+    case EPI_BIAS_BF16: return launch_splitk<EPI_BIAS_BF16>(p, ws, s, stream);
+    case EPI_GELU: return launch_splitk<EPI_GELU>(p, ws, s, stream);
+    case EPI_RESID_F32: return launch_splitk<EPI_RESID_F32>(p, ws, s, stream);
+    case EPI_DGELU: return launch_splitk<EPI_DGELU>(p, ws, s, stream);
+    case EPI_F32: return launch_splitk<EPI_F32>(p, ws, s, stream);
+    default: return VITAMD_ERR_ARG;
+  }
 }
 
 int vitamd_gemm_nt_impl(const GemmNtArgs& p0, hipStream_t stream) {

@@ -17,11 +17,15 @@ constexpr int MAXV = 4;            // up to 4 float4 per lane: D <= 1024, D % 25
 
 // KEEP (kept-row form, M = B * keep): output row b*keep + t takes row b*seq + t of x_in and row b*keep + t of the addend (the compact
 // output of the kept-query attention); x_out, y, mean, rstd are compact.  The per-row arithmetic is the same code.
-template <int NV, bool HAS_ADD, bool KEEP = false>
+// ADD2: a second bf16 addend, added AFTER the first: s = fl(x + addend), then s = fl(s + addend2) - the bits a launch with `addend` that
+// stored s followed by a launch on that s with `addend2` gives, without the 4 + 4 B per element of the store and the read back.  With
+// KEEP the first addend is then a full-size tensor like x_in (row b*seq + t) and addend2 the compact one.  NOSTORE: x_out is not written.
+template <int NV, bool HAS_ADD, bool KEEP = false, bool ADD2 = false, bool NOSTORE = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x_in, const __bf16* __restrict__ addend,
                                                      float* __restrict__ x_out, __bf16* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd, int M, float eps,
-                                                     int seq = 0, int keep = 0) {
+                                                     int seq = 0, int keep = 0, const __bf16* __restrict__ addend2 = nullptr) {
+  static_assert(HAS_ADD || (!ADD2 && !NOSTORE), "the second addend and the store-free form go with a first addend");
   constexpr int D = NV * 256;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int row = blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += gridDim.x * ROWS_PER_BLOCK) {
@@ -32,11 +36,16 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 #pragma unroll
     for (int j = 0; j < NV; ++j) v[j] = *(const f32x4*)(x_in + base_in + j * 256 + lane * 4);
     if constexpr (HAS_ADD) {
+      const size_t base_add = ADD2 ? base_in : base;
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
-        const u32x2 a = *(const u32x2*)(addend + base + j * 256 + lane * 4);
+        const u32x2 a = *(const u32x2*)(addend + base_add + j * 256 + lane * 4);
         v[j][0] += bf16lo(a[0]); v[j][1] += bf16hi(a[0]); v[j][2] += bf16lo(a[1]); v[j][3] += bf16hi(a[1]);
-        *(f32x4*)(x_out + base + j * 256 + lane * 4) = v[j];
+        if constexpr (ADD2) {
+          const u32x2 a2 = *(const u32x2*)(addend2 + base + j * 256 + lane * 4);
+          v[j][0] += bf16lo(a2[0]); v[j][1] += bf16hi(a2[0]); v[j][2] += bf16lo(a2[1]); v[j][3] += bf16hi(a2[1]);
+        }
+        if constexpr (!NOSTORE) *(f32x4*)(x_out + base + j * 256 + lane * 4) = v[j];
       }
     }
     float s = 0.f;
@@ -81,6 +90,40 @@ __global__ __launch_bounds__(256) void ln_fwd_generic(const float* __restrict__ 
     for (int c = lane; c < D; c += 64) { const float d = xr[c] - mu; q += d * d; }
     const float rs = rsqrtf(wave_sum(q) / D + eps);
     for (int c = lane; c < D; c += 64) y[base + c] = f2bf((xr[c] - mu) * rs);
+    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+  }
+}
+
+// The generic-width fallback of the ADD2 / NOSTORE forms of ln_fwd_kernel (an addend is always there; with KEEP it is full size and addend2
+// compact).  Every pass forms the sum again - the same two roundings, so the same bits - instead of reading it back: there may be no x_out.
+template <bool KEEP, bool ADD2, bool NOSTORE>
+__global__ __launch_bounds__(256) void ln_fwd_generic_add2(const float* __restrict__ x_in, const __bf16* __restrict__ addend,
+                                                           const __bf16* __restrict__ addend2, float* __restrict__ x_out,
+                                                           __bf16* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd,
+                                                           int M, int D, float eps, int seq, int keep) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int row = blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += gridDim.x * ROWS_PER_BLOCK) {
+    const size_t base = (size_t)row * D;
+    size_t base_in = base;
+    if constexpr (KEEP) base_in = ((size_t)(row / keep) * seq + row % keep) * D;
+    const float* xr = x_in + base_in;
+    const __bf16* ar = addend + (ADD2 ? base_in : base);
+    auto summed = [&](int c) {                  // (x + addend) + addend2, in this order
+      float t = xr[c] + bf2f(ar[c]);
+      if constexpr (ADD2) t += bf2f(addend2[base + c]);
+      return t;
+    };
+    float s = 0.f;
+    for (int c = lane; c < D; c += 64) {
+      const float t = summed(c);
+      if constexpr (!NOSTORE) x_out[base + c] = t;
+      s += t;
+    }
+    const float mu = wave_sum(s) / D;
+    float q = 0.f;
+    for (int c = lane; c < D; c += 64) { const float d = summed(c) - mu; q += d * d; }
+    const float rs = rsqrtf(wave_sum(q) / D + eps);
+    for (int c = lane; c < D; c += 64) y[base + c] = f2bf((summed(c) - mu) * rs);
     if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
   }
 }
@@ -235,23 +278,32 @@ void with_width(int D, F f) {
 }
 
 // Every forward launch.  KEEP: the kept-row form (M = B * keep; the addend is required there, so only HAS_ADD = true exists).
+// add2 / x_out == nullptr with an addend: the forms with a second addend / without the stream store (ln_fwd_kernel); the entry points
+// decide which combinations they let through.
 template <bool KEEP>
-int ln_fwd_launch(const float* x_in, const void* addend_bf16, float* x_out, void* y_bf16, float* mean, float* rstd, int M, int D, float eps, int seq,
-                  int keep, void* stream_) {
+int ln_fwd_launch(const float* x_in, const void* addend_bf16, const void* addend2_bf16, float* x_out, void* y_bf16, float* mean, float* rstd, int M,
+                  int D, float eps, int seq, int keep, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const __bf16* add = (const __bf16*)addend_bf16;
+  const __bf16* add2 = (const __bf16*)addend2_bf16;
   __bf16* y = (__bf16*)y_bf16;
   const dim3 grid(grid_for(M)), block(256);
   with_width(D, [&](auto W) {
     constexpr int NV = decltype(W)::value;
-    auto go = [&](auto ADD) {
-      constexpr bool HAS_ADD = decltype(ADD)::value;
-      if constexpr (NV != 0) hipLaunchKernelGGL((ln_fwd_kernel<NV, HAS_ADD, KEEP>), grid, block, 0, stream, x_in, add, x_out, y, mean, rstd, M, eps, seq, keep);
+    auto go = [&](auto ADD, auto SECOND, auto DROP_STORE) {
+      constexpr bool HAS_ADD = decltype(ADD)::value, ADD2 = decltype(SECOND)::value, NOSTORE = decltype(DROP_STORE)::value;
+      if constexpr (NV != 0) hipLaunchKernelGGL((ln_fwd_kernel<NV, HAS_ADD, KEEP, ADD2, NOSTORE>), grid, block, 0, stream, x_in, add, x_out, y, mean, rstd, M, eps, seq, keep, add2);
+      else if constexpr (ADD2 || NOSTORE) hipLaunchKernelGGL((ln_fwd_generic_add2<KEEP, ADD2, NOSTORE>), grid, block, 0, stream, x_in, add, add2, x_out, y, mean, rstd, M, D, eps, seq, keep);
       else hipLaunchKernelGGL((ln_fwd_generic<HAS_ADD, KEEP>), grid, block, 0, stream, x_in, add, x_out, y, mean, rstd, M, D, eps, seq, keep);
     };
-    if constexpr (KEEP) go(std::true_type{});
-    else if (add) go(std::true_type{});
-    else go(std::false_type{});
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (add2 && !x_out) go(yes, yes, yes);
+    else if (add2) go(yes, yes, no);
+    else if constexpr (KEEP) go(yes, no, no);   // (the kept-row form without a second addend always has its addend and always stores)
+    else if (!add) go(no, no, no);
+    else if (!x_out) go(yes, no, yes);
+    else go(yes, no, no);
   });
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
@@ -285,7 +337,7 @@ extern "C" int vitamd_layernorm_fwd(const float* x_in, const void* addend_bf16, 
                                     float* rstd, int M, int D, float eps, void* stream) {
   if (M <= 0 || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
   if (!x_in || !y_bf16 || !mean || !rstd || (addend_bf16 && !x_out)) return VITAMD_ERR_ARG;
-  return ln_fwd_launch<false>(x_in, addend_bf16, x_out, y_bf16, mean, rstd, M, D, eps, 0, 0, stream);
+  return ln_fwd_launch<false>(x_in, addend_bf16, nullptr, x_out, y_bf16, mean, rstd, M, D, eps, 0, 0, stream);
 }
 
 // the bf16 copy (and its column sums) additionally gets the dropout mask (p, seed) of the
@@ -324,7 +376,7 @@ extern "C" int vitamd_layernorm_fwd_keep(const float* x_in, const void* addend_b
   if (B <= 0 || seq <= 0 || keep <= 0 || keep > seq || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
   if ((long long)B * seq > 2147483647LL) return VITAMD_ERR_SHAPE;
   if (!x_in || !y_bf16 || !mean || !rstd || !addend_bf16 || !x_out) return VITAMD_ERR_ARG;
-  return ln_fwd_launch<true>(x_in, addend_bf16, x_out, y_bf16, mean, rstd, B * keep, D, eps, seq, keep, stream);
+  return ln_fwd_launch<true>(x_in, addend_bf16, nullptr, x_out, y_bf16, mean, rstd, B * keep, D, eps, seq, keep, stream);
 }
 
 // LayerNorm backward over M = B * seq rows with a COMPACT g_res [B*keep, D]: row b*seq + t adds g_res[b*keep + t] when t < keep, nothing
@@ -340,4 +392,24 @@ extern "C" int vitamd_layernorm_bwd_keep(const void* dy_bf16, const void* x_or_y
   const DropoutParams dp = dropout_params(dropout_p, seed);
   if (!dp.ok) return VITAMD_ERR_ARG;
   return ln_bwd_launch<true>(dy_bf16, x_or_y, mean, rstd, g_res, g_out, g_bf16, colsum, B * seq, D, use_xhat != 0, dp, seq, keep, stream);
+}
+
+// Forward with up to two bf16 addends and an optional stream store: s = fl(x_in + addend1), then s = fl(s + addend2) when addend2 is given;
+// y, mean, rstd = LN(s); x_out = s when x_out is given.  The bits of vitamd_layernorm_fwd(x_in, addend1) followed by
+// vitamd_layernorm_fwd(its x_out, addend2), in one pass over x_in.  addend1 is required.
+extern "C" int vitamd_layernorm_fwd_add2(const float* x_in, const void* addend1_bf16, const void* addend2_bf16, float* x_out, void* y_bf16,
+                                         float* mean, float* rstd, int M, int D, float eps, void* stream) {
+  if (M <= 0 || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
+  if (!x_in || !addend1_bf16 || !y_bf16 || !mean || !rstd) return VITAMD_ERR_ARG;
+  return ln_fwd_launch<false>(x_in, addend1_bf16, addend2_bf16, x_out, y_bf16, mean, rstd, M, D, eps, 0, 0, stream);
+}
+
+// Its kept-row form: output row b*keep + t = LN(fl(fl(x_in[b*seq + t] + addend1[b*seq + t]) + addend2[b*keep + t])).  x_in and addend1 are
+// full size [B*seq, D]; addend2 (required), x_out (optional), y, mean and rstd are compact [B*keep, ...].
+extern "C" int vitamd_layernorm_fwd_keep_add2(const float* x_in, const void* addend1_bf16, const void* addend2_bf16, float* x_out, void* y_bf16,
+                                              float* mean, float* rstd, int B, int seq, int keep, int D, float eps, void* stream) {
+  if (B <= 0 || seq <= 0 || keep <= 0 || keep > seq || D <= 0 || D % 4) return VITAMD_ERR_SHAPE;
+  if ((long long)B * seq > 2147483647LL) return VITAMD_ERR_SHAPE;
+  if (!x_in || !addend1_bf16 || !addend2_bf16 || !y_bf16 || !mean || !rstd) return VITAMD_ERR_ARG;
+  return ln_fwd_launch<true>(x_in, addend1_bf16, addend2_bf16, x_out, y_bf16, mean, rstd, B * keep, D, eps, seq, keep, stream);
 }

@@ -81,6 +81,9 @@ inline DropoutParams dropout_params(float p, unsigned long long seed) {
 
 int vitamd_gemm_nt_impl(const GemmNtArgs& p, hipStream_t stream);
 int vitamd_gemm_nt_plan_impl(const GemmNtArgs& p);
+int vitamd_gemm_nt_ws_impl(const GemmNtArgs& p, int splits, float* ws, size_t ws_bytes, hipStream_t stream);   // split-K where the rule says so
+long vitamd_gemm_nt_ws_bytes_impl(const GemmNtArgs& p, int splits);
+int vitamd_gemm_nt_ws_plan_impl(const GemmNtArgs& p, int splits);
 int vitamd_init_impl(int device, hipStream_t stream);
 const unsigned* vitamd_gelu_table();   // the current device's erf-GELU table image (vitamd_init), or null: shared by every GELU epilogue
 int vitamd_gemm_tn_impl(const GemmTnArgs& p, hipStream_t stream);

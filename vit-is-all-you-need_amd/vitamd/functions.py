@@ -220,6 +220,13 @@ def ensure_side_overlap(device, attempts=6):
     return ratio
 
 
+STREAM_ONCE = True        # with DEFER_RESID: a layer that receives `pending` stores the residual stream once, not twice.  LN1 forms x0 = x + pending in registers
+                          # and does not store it; LN2 forms it again (the same fp32 + bf16 rounding) and adds the attention output: x1 = (x + pending) + o,
+                          # bit for bit what LN2 of the stored x0 gave.  Nothing else read x0: the backward takes xhat from the saved bf16 `a`, which is
+                          # why the path exists only for the widths where it does (ops.XHAT_WIDTHS) and without dropout.  24 -> 22 B per element over the
+                          # two HBM-bound kernels, and one fp32 [M, D] tensor per layer less to keep for the backward.  DESIGN.md section 4.11.
+
+
 def _f32c(t):
     return t.detach().to(F32).contiguous()
 
@@ -243,7 +250,9 @@ def layer_forward(x0, wqkv, bqkv, w1, b1, w2, b2, B, N, H, causal, need_grad, p_
     """x0 fp32 [M,D] -> x2 fp32 [M,D], the tensors backward needs, and the dropout record
     (p_attn, seed_attn, p_mlp, seed_mlp).  p_attn: SDPA dropout_p (transformer.py:28); p_mlp: the
     nn.Dropout after fc2 (transformer.py:40).
-    pending: bf16 [M,D] MLP output of the layer below that has not been added to x0 yet (this layer's first LayerNorm adds it).
+    pending: bf16 [M,D] MLP output of the layer below that has not been added to x0 yet (this layer's first LayerNorm adds it).  With
+    STREAM_ONCE (and a width of ops.XHAT_WIDTHS, no dropout) the sum x0 + pending is never stored: the x0 slot of the saved tuple is None,
+    and layer_backward's first LayerNorm takes xhat alone.
     defer: return (x1, y) with y = bf16 fc2 output instead of x2 = x1 + y (the caller hands y to the next layer as `pending`).
     keep (last layer of a stack only; non-causal, no dropout, 0 < keep < N): the caller uses the first `keep` tokens of every sequence.
     LN1 and the QKV GEMM run on all M rows (K and V need every token); attention is computed for the queries < keep, and LN2, fc1+GELU
@@ -253,7 +262,12 @@ def layer_forward(x0, wqkv, bqkv, w1, b1, w2, b2, B, N, H, causal, need_grad, p_
     wqkv_b, _ = WEIGHTS.get(wqkv, need_grad)
     w1_b, _ = WEIGHTS.get(w1, need_grad)
     w2_b, _ = WEIGHTS.get(w2, need_grad)
-    x0, a, mean1, rstd1 = ops.layernorm_fwd(x0, addend=pending)                  # (residual of the layer below +) LN1   transformer.py:43-44
+    once = STREAM_ONCE and pending is not None and x0.shape[1] in ops.XHAT_WIDTHS and p_attn == 0 and p_mlp == 0
+    if once:                                                                     # x0 = x + pending stays in registers: LN2 forms it again
+        x, x0 = x0, None
+        _, a, mean1, rstd1 = ops.layernorm_fwd(x, addend=pending, store=False)
+    else:
+        x0, a, mean1, rstd1 = ops.layernorm_fwd(x0, addend=pending)              # (residual of the layer below +) LN1   transformer.py:43-44
     qkv = ops.gemm_nt(a, wqkv_b, ops.EPI_BIAS_BF16, bias=bqkv)                   # fused QKV      transformer.py:27
     if keep is not None:
         if causal or p_attn > 0 or p_mlp > 0 or defer or not 0 < keep < N:
@@ -264,14 +278,20 @@ def layer_forward(x0, wqkv, bqkv, w1, b1, w2, b2, B, N, H, causal, need_grad, p_
         else:
             o, lse = ops.attention_fwd(qkv, B, N, H)                             # full size; the backward needs the full o for delta
             o_k = o.view(B, N, -1)[:, :keep].reshape(B * keep, -1).contiguous()  # Mk rows copied
-        x1, bln, mean2, rstd2 = ops.layernorm_fwd_keep(x0, o_k, B, N, keep)      # gathers the kept rows of x0: all compact from here on
+        if once:
+            x1, bln, mean2, rstd2 = ops.layernorm_fwd_keep(x, o_k, B, N, keep, pending=pending)
+        else:
+            x1, bln, mean2, rstd2 = ops.layernorm_fwd_keep(x0, o_k, B, N, keep)  # gathers the kept rows of x0: all compact from here on
         pre, h = ops.gemm_nt(bln, w1_b, ops.EPI_GELU_DG, bias=b1)
         x2 = ops.gemm_nt(h, w2_b, ops.EPI_RESID_F32, bias=b2, aux=x1)
         saved = (x0, mean1, rstd1, a, qkv, o, lse, x1, mean2, rstd2, bln, pre, h) if need_grad else None
         return x2, saved, drop
     # (the residual add can also ride in the attention kernel's epilogue - ops.attention_fwd(resid=) - which measured equal: 34.47 vs 34.43 ms)
     o, lse = ops.attention_fwd(qkv, B, N, H, causal, dropout=drop[:2])           # SDPA           transformer.py:28-29
-    x1, bln, mean2, rstd2 = ops.layernorm_fwd(x0, addend=o)                      # residual + LN2 transformer.py:43-44
+    if once:
+        x1, bln, mean2, rstd2 = ops.layernorm_fwd(x, addend=pending, addend2=o)           # (x + pending) + o: the x0 of LN1, formed again
+    else:
+        x1, bln, mean2, rstd2 = ops.layernorm_fwd(x0, addend=o)                  # residual + LN2 transformer.py:43-44
     # fc1 + GELU (transformer.py:37-38); `pre` holds bf16(gelu'(fc1 out)) for the backward - the derivative is evaluated
     # here, where its exp is shared with the erf and the VALU work hides under the output stores (-85 us per layer in dgrad fc2)
     pre, h = ops.gemm_nt(bln, w1_b, ops.EPI_GELU_DG, bias=b1)

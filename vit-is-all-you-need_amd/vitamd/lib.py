@@ -23,6 +23,9 @@ SIGNATURES = {
     "vitamd_init": [_I, _P],
     "vitamd_gemm_nt_plan": [_I, _I, _I, _I, _I, _I],
     "vitamd_gemm_nt_bf16": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vitamd_gemm_nt_bf16_ws": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P],
+    "vitamd_gemm_nt_ws_bytes": [_I, _I, _I, _I, _I, _I, _I],
+    "vitamd_gemm_nt_ws_plan": [_I, _I, _I, _I, _I, _I, _I],
     "vitamd_gemm_tn_bf16": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "vitamd_gemm_tn_bf16_ws": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P],
     "vitamd_gemm_tn_bf16_ws_colsum": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P],
@@ -71,6 +74,8 @@ SIGNATURES = {
     "vitamd_sample_logits": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _U64, _P],
     "vitamd_layernorm_fwd_keep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "vitamd_layernorm_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P],
+    "vitamd_layernorm_fwd_add2": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
+    "vitamd_layernorm_fwd_keep_add2": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "vitamd_attention_keep_forms": [_I, _I],
     "vitamd_attention_fwd_keep": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_attention_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

@@ -96,8 +96,8 @@ def gemm_nt(a, b, epi, *, bias=None, aux=None, out=None, out2=None, colsum=None,
         tile = auto_tile(a.device, M, N, K, epi)
     elif tile == _RAW_AUTO:             # the library's own automatic choice, no host-side policy (the probe's seam arm)
         tile = 0
-    code = _L().vitamd_gemm_nt_bf16(_p(a), _p(b), _p(out), _p(out2), _p(bias), _p(aux), _p(colsum), M, N, K, N, epi,
-                                    n_patches, seq, extra, tile, _stream())
+    code = _nt_launch(a.device, (_p(a), _p(b), _p(out), _p(out2), _p(bias), _p(aux), _p(colsum), M, N, K, N, epi,
+                                 n_patches, seq, extra, tile))
     _lib.check(code, f"gemm_nt[M={M},N={N},K={K},epi={epi}]")
     return (out, out2) if epi in (EPI_GELU, EPI_GELU_DG) else out
 
@@ -167,6 +167,30 @@ def _workspace(device, nbytes):
     return ws
 
 
+NT_SPLITS = 0             # split-K of the NT GEMMs that take the 128x128 kernel on fewer tiles than the device has CUs (the kept-row layer, the classifier
+                          # head: include/vitamd.h vitamd_gemm_nt_bf16_ws): 0 = the library's rule, 1 = never (the unsplit kernel: tests, A/B), n = n splits.
+                          # Read on every call.  Results differ from the unsplit kernel's by fp32 summation order only, and are the same in every run.
+NT_FORM_SPLITK = 6        # include/vitamd.h VITAMD_NT_FORM_SPLITK (vitamd_gemm_nt_ws_plan)
+
+
+def _nt_launch(device, args):
+    """vitamd_gemm_nt_bf16 on `args` (everything but the stream), or its workspace form where the library would split this launch.  The partial
+    tiles go to this stream's split-K scratch (_workspace: launches of one stream run one after the other, so the weight-gradient GEMMs share
+    it).  Inside a stream capture the scratch is not grown: a launch it is too small for stays unsplit (an eager step before the capture, as
+    GraphedStep makes, has sized it)."""
+    L = _L()
+    M, N, K, ldo, epi, tile = args[7], args[8], args[9], args[10], args[11], args[15]
+    need = L.vitamd_gemm_nt_ws_bytes(M, N, K, ldo, epi, tile, NT_SPLITS) if NT_SPLITS != 1 else 0
+    if need > 0 and torch.cuda.is_current_stream_capturing():
+        ws = _WORKSPACES.get((device, torch.cuda.current_stream().cuda_stream))
+        if ws is None or ws.numel() * 4 < need:
+            need = 0
+    if need <= 0:
+        return L.vitamd_gemm_nt_bf16(*args, _stream())
+    ws = _workspace(device, need)
+    return L.vitamd_gemm_nt_bf16_ws(*args, NT_SPLITS, _p(ws), ws.numel() * 4, _stream())
+
+
 TN_FORM_SHARED, TN_FORM_EXCLUSIVE = 0, 1      # include/vitamd.h VITAMD_TN_FORM_*
 
 
@@ -206,8 +230,11 @@ def gemm_tn(l, r, out, splits=0, accumulate=True, atomic=False, form=TN_FORM_SHA
 
 
 # ------------------------------------------------------------------------------------------ LayerNorm
-def layernorm_fwd(x, addend=None):
-    """x fp32 [M,D] (+ addend bf16) -> (x_sum fp32 or x itself, y bf16, mean, rstd)."""
+def layernorm_fwd(x, addend=None, addend2=None, store=True):
+    """x fp32 [M,D] (+ addend bf16) -> (x_sum fp32 or x itself, y bf16, mean, rstd).
+    addend2 (bf16 [M,D], needs addend): added after addend - x_sum = (x + addend) + addend2, the bits of layernorm_fwd(layernorm_fwd(x, addend)[0],
+    addend2) in one pass over x.  store=False (needs addend): x_sum is not written and None is returned in its place, for a caller that only
+    needs the sum as this LayerNorm's input."""
     _need(x, F32, "x", 2)
     M, D = x.shape
     y = torch.empty((M, D), dtype=BF16, device=x.device)
@@ -216,15 +243,23 @@ def layernorm_fwd(x, addend=None):
     x_out = None
     if addend is not None:
         _need(addend, BF16, "addend", 2)
-        x_out = torch.empty_like(x)
+        x_out = torch.empty_like(x) if store else None
+    if addend2 is not None or not store:
+        if addend is None or tuple(addend.shape) != (M, D) or (addend2 is not None and tuple(_need(addend2, BF16, "addend2", 2).shape) != (M, D)):
+            raise _lib.VitamdError("layernorm_fwd: addend2 and store=False need addend; the addends are bf16 [M, D] like x")
+        code = _L().vitamd_layernorm_fwd_add2(_p(x), _p(addend), _p(addend2), _p(x_out), _p(y), _p(mean), _p(rstd), M, D, LN_EPS, _stream())
+        _lib.check(code, f"layernorm_fwd_add2[M={M},D={D}]")
+        return x_out, y, mean, rstd
     code = _L().vitamd_layernorm_fwd(_p(x), _p(addend), _p(x_out), _p(y), _p(mean), _p(rstd), M, D, LN_EPS, _stream())
     _lib.check(code, f"layernorm_fwd[M={M},D={D}]")
     return (x_out if addend is not None else x), y, mean, rstd
 
 
-def layernorm_fwd_keep(x, addend, B, seq, keep):
+def layernorm_fwd_keep(x, addend, B, seq, keep, pending=None):
     """Kept-row form: x fp32 [B*seq, D] (the full stream), addend bf16 [B*keep, D] (compact) -> compact (x_sum fp32 [B*keep, D], y bf16,
-    mean, rstd); output row b*keep + t = LN(x[b*seq + t] + addend[b*keep + t]), the same per-row arithmetic as layernorm_fwd."""
+    mean, rstd); output row b*keep + t = LN(x[b*seq + t] + addend[b*keep + t]), the same per-row arithmetic as layernorm_fwd.
+    pending (bf16 [B*seq, D], full size like x): added to x first - row b*keep + t = LN((x[b*seq + t] + pending[b*seq + t]) + addend[b*keep + t]),
+    the bits of layernorm_fwd_keep(layernorm_fwd(x, pending)[0], addend, ...) without the full-size sum in memory."""
     _need(x, F32, "x", 2); _need(addend, BF16, "addend", 2)
     D = x.shape[1]
     if x.shape[0] != B * seq or tuple(addend.shape) != (B * keep, D) or not 0 < keep <= seq:
@@ -234,9 +269,18 @@ def layernorm_fwd_keep(x, addend, B, seq, keep):
     y = torch.empty((Mk, D), dtype=BF16, device=x.device)
     mean = torch.empty((Mk,), dtype=F32, device=x.device)
     rstd = torch.empty((Mk,), dtype=F32, device=x.device)
+    if pending is not None:
+        if _need(pending, BF16, "pending", 2).shape != x.shape:
+            raise _lib.VitamdError("layernorm_fwd_keep: pending must be bf16 [B*seq, D] like x")
+        _lib.check(_L().vitamd_layernorm_fwd_keep_add2(_p(x), _p(pending), _p(addend), _p(x_out), _p(y), _p(mean), _p(rstd), B, seq, keep, D, LN_EPS,
+                                                       _stream()), f"layernorm_fwd_keep_add2[B={B},seq={seq},keep={keep},D={D}]")
+        return x_out, y, mean, rstd
     _lib.check(_L().vitamd_layernorm_fwd_keep(_p(x), _p(addend), _p(x_out), _p(y), _p(mean), _p(rstd), B, seq, keep, D, LN_EPS, _stream()),
                f"layernorm_fwd_keep[B={B},seq={seq},keep={keep},D={D}]")
     return x_out, y, mean, rstd
+
+
+XHAT_WIDTHS = (256, 512, 768, 1024)       # the widths whose LayerNorm backward reads xhat from the forward's bf16 output (register-resident kernels)
 
 
 def layernorm_bwd(dy, x, mean, rstd, g_res=None, want_bf16=False, colsum=None, dropout=(0.0, 0), xhat=None, keep=None):
@@ -244,25 +288,30 @@ def layernorm_bwd(dy, x, mean, rstd, g_res=None, want_bf16=False, colsum=None, d
     also gets that dropout mask (it is then the gradient of a dropped-out Linear output).
     xhat: the forward's bf16 output (= xhat for this non-affine LayerNorm); given, and D in {256,512,768,1024}, the kernel reads
     it instead of recomputing xhat from the fp32 x (2 B instead of 4 B per element of an HBM-bound kernel).
-    keep=(seq, k): g_res is COMPACT fp32 [M/seq*k, D] - row b*seq + t adds g_res[b*k + t] when t < k, nothing otherwise."""
-    _need(dy, BF16, "dy", 2); _need(x, F32, "x", 2)
-    M, D = x.shape
-    g = torch.empty_like(x)
-    gb = torch.empty((M, D), dtype=BF16, device=x.device) if want_bf16 else None
+    keep=(seq, k): g_res is COMPACT fp32 [M/seq*k, D] - row b*seq + t adds g_res[b*k + t] when t < k, nothing otherwise.
+    x may be None where xhat takes its place (xhat given and D in XHAT_WIDTHS): a forward that did not store the LayerNorm's fp32 input."""
+    _need(dy, BF16, "dy", 2)
+    if x is not None:
+        _need(x, F32, "x", 2)
+    M, D = dy.shape if x is None else x.shape
+    if x is None and (xhat is None or D not in XHAT_WIDTHS):
+        raise _lib.VitamdError(f"layernorm_bwd: without x the backward needs xhat and D in {XHAT_WIDTHS} (D={D})")
+    g = torch.empty((M, D), dtype=F32, device=dy.device)
+    gb = torch.empty((M, D), dtype=BF16, device=dy.device) if want_bf16 else None
     if g_res is not None:
         _need(g_res, F32, "g_res", 2)
     if keep is not None:
         seq, k = keep
         if g_res is None or M % seq or not 0 < k <= seq or tuple(g_res.shape) != (M // seq * k, D):
             raise _lib.VitamdError(f"layernorm_bwd: keep=({seq}, {k}) needs M % seq == 0 and g_res fp32 [M/seq*k, D]")
-        use_xhat = xhat is not None and D in (256, 512, 768, 1024)
+        use_xhat = xhat is not None and D in XHAT_WIDTHS
         if use_xhat:
             _need(xhat, BF16, "xhat", 2)
         code = _L().vitamd_layernorm_bwd_keep(_p(dy), _p(xhat if use_xhat else x), _p(mean), _p(rstd), _p(g_res), _p(g), _p(gb), _p(colsum),
                                               M // seq, seq, k, D, int(use_xhat), float(dropout[0]), int(dropout[1]), _stream())
         _lib.check(code, f"layernorm_bwd_keep[M={M},D={D},seq={seq},keep={k}]")
         return g, gb
-    if xhat is not None and D in (256, 512, 768, 1024):
+    if xhat is not None and D in XHAT_WIDTHS:
         _need(xhat, BF16, "xhat", 2)
         code = _L().vitamd_layernorm_bwd_xhat(_p(dy), _p(xhat), _p(rstd), _p(g_res), _p(g), _p(gb), _p(colsum), M, D,
                                               float(dropout[0]), int(dropout[1]), _stream())
