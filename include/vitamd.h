@@ -34,7 +34,7 @@ extern "C" {
 
 /* ABI version of this header (bumped on any signature change): 9 (the KV-cached decoding entry points; the cross-entropy and token-embedding
  * entry points, the multi-tensor optimiser entry points vitamd_mt_* and the table advance vitamd_sched_*, were added to 9 without changing
- * an existing signature). */
+ * an existing signature; so was the evaluation entry point vitamd_classify_metrics). */
 int vitamd_abi_version(void);
 
 /* Per-device set-up, once per device and process (idempotent; device < 0 = the current device; never inside a stream capture): builds the
@@ -383,6 +383,25 @@ int vitamd_soft_cross_entropy_fwd(const void* logits, int logits_bf16, const lon
 int vitamd_soft_cross_entropy_bwd(const void* logits, int logits_bf16, const long long* target_a, const long long* target_b,
                                   const float* lam, float smoothing, const float* lse, const float* stats, const float* grad_out,
                                   void* dlogits, int dlogits_bf16, int M, int V, int ld, int ldo, void* stream);
+/* Evaluation: per-row loss and rank of the target, added to counters that stay on the device.  logits, ld, the
+ * 16-byte rule and target as vitamd_cross_entropy_fwd (M and ld are long here and must fit an int).  Launch one is the RANK form of that
+ * entry's row walk, one pass over each row:
+ *   loss_row[m] = lse[m] - x[m, t]: the bits vitamd_cross_entropy_fwd writes for the same input;
+ *   rank[m] int32 = the number of columns v != t that rank above the target, where v ranks above t unless x[m, v] < x[m, t], or
+ *                   x[m, v] == x[m, t] and v > t.  Compared as fp32 (exact for bf16); an integer count merged by integer adds.
+ * rank == 0 is logits.argmax(-1) == t (the first maximal index) and rank < k is top-k membership.  A NaN compares false: a NaN in
+ * another column ranks above the target, a NaN at the target ranks below every column (rank V - 1), so a NaN never makes a row top-1.
+ * A row with t == ignore_index is not read: rank -1, loss_row 0.  A target outside [0, V) that is not ignore_index forms no address:
+ * it is a counted row of rank V (wrong for every k) and NaN loss, so the error shows in the result without a synchronise.
+ * Launch two (one workgroup, a fixed order) ADDS to the caller's accumulators, with ordinary loads and stores (no atomics):
+ *   loss_sum[0] (fp64) += the fp64 sum of loss_row over the counted rows (rank >= 0);
+ *   counts[0..2] (int64) += the counted rows, the rows with rank == 0, the rows with rank < topk.
+ * Zero both for a fresh evaluation; the same inputs from the same state give the same bits.  Only enqueues on `stream`.
+ * M < 1, V outside 2 .. 65536, ld < V (or M, ld >= 2^31): VITAMD_ERR_SHAPE; a missing pointer or topk outside 1 .. V: VITAMD_ERR_ARG
+ * (after the shape check); nothing is launched in either case.
+ * replaces train_vit.py:114-128 (the validation loop's F.cross_entropy, argmax == labels and their .item()s). */
+int vitamd_classify_metrics(const void* logits, int logits_bf16, const long long* target, float* loss_row, int* rank, double* loss_sum,
+                            long long* counts, long M, int V, long ld, int topk, long long ignore_index, void* stream);
 /* x fp32 [B*S, D]: x[b*S+s, :] = tok_table[ids[b*S+s], :] + pos_table[s, :] (one fp32 add: bit-equal to the framework's gather-and-add).
  * D % 4 == 0, 1 <= S <= pos_rows, else VITAMD_ERR_SHAPE.  An id outside [0, tok_rows) leaves that row of x untouched; no table is read
  * out of bounds.  replaces train_videogpt.py:49 (tok_embed(x) + pos_embed(arange)). */

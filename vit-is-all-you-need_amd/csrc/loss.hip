@@ -11,6 +11,8 @@
 // it may run in place.  Rows whose target is ignore_index (or outside [0, V)) are written as zeros without being read.
 // The soft-target pair (Mixup / CutMix / label smoothing) is the SOFT form of the same two kernels: the row walk
 // also carries the plain sum of the row, and the one-hot becomes (1-e) (l [ya] + (1-l) [yb]) + e / V.
+// Evaluation (at the end of the file) is the RANK form of the forward kernel - the same walk also counts the
+// columns that rank above the target - and a single-workgroup launch that adds loss, rows, top-1 and top-k hits to device counters.
 #include "common.h"
 #include "../../include/vitamd.h"
 
@@ -69,10 +71,15 @@ __device__ __forceinline__ void store_piece(void* row, int i, const float (&f)[W
 
 __device__ __forceinline__ float ex2(float d) { return __builtin_amdgcn_exp2f(d * LOG2E); }   // exp(d)
 
-// (m, s) <- (m, s) merged with (m2, s2): s counts exp(x - m)
+// (m, s) <- (m, s) merged with (m2, s2): s counts exp(x - m).  FUSED = false leaves the contraction of s * e + s2 * e2 to the compiler,
+// as the training forms always have (their bits stay what they were): in the plain form it fuses the first product and rounds the
+// second everywhere.  FUSED = true spells exactly that out.  The evaluation form needs it: left to the compiler, the vectoriser packed
+// its last lane merge into two rounded products and an add, one rounding away from the plain form's loss.
+template <bool FUSED = false>
 __device__ __forceinline__ void merge(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
-  s = s * ex2(m - mn) + s2 * ex2(m2 - mn);
+  if constexpr (FUSED) s = __builtin_fmaf(s, ex2(m - mn), s2 * ex2(m2 - mn));
+  else s = s * ex2(m - mn) + s2 * ex2(m2 - mn);
   m = mn;
 }
 
@@ -83,15 +90,26 @@ struct Soft { const long long* target_b; const float* lam; float smoothing; };
 
 // VEC: base and row stride allow 16-byte loads; the V % W columns after the last whole piece are read one by one.  WIDE: one row per
 // workgroup (256 lanes) instead of one per wave.  SOFT: the same walk also carries the plain sum of the row (the smoothing term), merged
-// over lanes and waves beside (m, s), and the row's loss is the soft-target one; no row is ignored.
-template <bool BF16, bool VEC, bool WIDE, bool SOFT>
+// over lanes and waves beside (m, s), and the row's loss is the soft-target one; no row is ignored.  RANK (the evaluation form,
+// vitamd_classify_metrics; never with SOFT): every lane first loads the target's logit x_t, the walk also counts the columns that rank
+// above the target (rank_above), the count is merged by integer adds and written to rank_out; a row whose target is ignore_index is
+// not read (rank -1, loss 0) and no lse is written.  Its (m, s) arithmetic rounds as the plain form's does (merge<true>), so the
+// two losses of a row are the same bits.
+__device__ __forceinline__ int rank_above(float x, int c, float xt, int tcol) {
+  return (c != tcol && !(x < xt || (x == xt && c > tcol))) ? 1 : 0;      // a NaN compares false: it ranks above, a NaN target below all
+}
+
+template <bool BF16, bool VEC, bool WIDE, bool SOFT, bool RANK = false>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* logits, const long long* __restrict__ target, float* __restrict__ loss_row,
-                                                    float* __restrict__ lse_out, int M, int V, int ld, long long ignore_index, Soft soft) {
+                                                    float* __restrict__ lse_out, int M, int V, int ld, long long ignore_index, Soft soft,
+                                                    int* __restrict__ rank_out = nullptr) {
+  static_assert(!(SOFT && RANK), "the evaluation form has hard targets");
   constexpr int W = BF16 ? 8 : 4;
   constexpr int TPR = WIDE ? 256 : 64;      // lanes per row
   constexpr int RPW = 256 / TPR;            // rows per workgroup
   typedef typename Elem<BF16>::type T;
   __shared__ float red[3][4];
+  __shared__ int redn[4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int t = WIDE ? (int)threadIdx.x : lane;
   for (long row0 = (long)blockIdx.x * RPW; row0 < M; row0 += (long)gridDim.x * RPW) {
@@ -99,6 +117,18 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* logits, const l
     if (row >= M) continue;                 // wave-uniform (never taken when WIDE: no barrier is skipped)
     const T* xr = (const T*)logits + (size_t)row * ld;
     float m = NEG_BIG, s = 0.f, sx = 0.f;     // sx: the sum of the row's logits (SOFT)
+    float xt = 0.f;                           // RANK: the target's logit (NaN for a target outside [0, V): no address is formed)
+    int tcol = -1, above = 0;
+    if constexpr (RANK) {
+      const long long tg = target[row];       // uniform over the lanes that share the row
+      if (tg == ignore_index) {               // not read; WIDE: the whole workgroup leaves, no barrier is skipped by a part of it
+        if (t == 0) { loss_row[row] = 0.f; rank_out[row] = -1; }
+        continue;
+      }
+      const bool in_range = tg >= 0 && tg < V;
+      tcol = in_range ? (int)tg : -1;
+      xt = in_range ? load_one<BF16>(xr, tcol) : __builtin_nanf("");
+    }
     if constexpr (VEC) {
       const int nvec = V / W;
 #pragma unroll 2
@@ -109,6 +139,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* logits, const l
 #pragma unroll
           for (int j = 0; j < W; ++j) sx += f[j];
         }
+        if constexpr (RANK) {
+#pragma unroll
+          for (int j = 0; j < W; ++j) above += rank_above(f[j], i * W + j, xt, tcol);
+        }
         float vm = f[0];
 #pragma unroll
         for (int j = 1; j < W; ++j) vm = fmaxf(vm, f[j]);
@@ -116,37 +150,50 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* logits, const l
         float a = 0.f;
 #pragma unroll
         for (int j = 0; j < W; ++j) a += ex2(f[j] - mn);
-        s = s * ex2(m - mn) + a;
+        if constexpr (RANK) s = __builtin_fmaf(s, ex2(m - mn), a);      // as merge<true>: what the plain form's contraction gives
+        else s = s * ex2(m - mn) + a;
         m = mn;
       }
       const int c = nvec * W + t;
       if (c < V) {
         const float x = load_one<BF16>(xr, c);
-        merge(m, s, x, 1.f);
+        merge<RANK>(m, s, x, 1.f);
         if constexpr (SOFT) sx += x;
+        if constexpr (RANK) above += rank_above(x, c, xt, tcol);
       }
     } else {
       for (int c = t; c < V; c += TPR) {
         const float x = load_one<BF16>(xr, c);
-        merge(m, s, x, 1.f);
+        merge<RANK>(m, s, x, 1.f);
         if constexpr (SOFT) sx += x;
+        if constexpr (RANK) above += rank_above(x, c, xt, tcol);
       }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-      merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+      merge<RANK>(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
       if constexpr (SOFT) sx += __shfl_xor(sx, o, 64);
+      if constexpr (RANK) above += __shfl_xor(above, o, 64);
     }
     if constexpr (WIDE) {
-      if (lane == 0) { red[0][w] = m; red[1][w] = s; red[2][w] = sx; }
+      if (lane == 0) {
+        red[0][w] = m; red[1][w] = s; red[2][w] = sx;
+        if constexpr (RANK) redn[w] = above;
+      }
       __syncthreads();
       m = red[0][0]; s = red[1][0]; sx = red[2][0];
 #pragma unroll
-      for (int i = 1; i < 4; ++i) { merge(m, s, red[0][i], red[1][i]); sx += red[2][i]; }
+      for (int i = 1; i < 4; ++i) { merge<RANK>(m, s, red[0][i], red[1][i]); sx += red[2][i]; }
+      if constexpr (RANK) above = (redn[0] + redn[1]) + (redn[2] + redn[3]);
       __syncthreads();                      // red is rewritten by the next row
     }
     if (t == 0) {
-      const float lse = m + __builtin_amdgcn_logf(s) * LN2;
+      const float lse = RANK ? __builtin_fmaf(__builtin_amdgcn_logf(s), LN2, m) : m + __builtin_amdgcn_logf(s) * LN2;
+      if constexpr (RANK) {                   // xt is the value the plain form loads below: the same subtraction, the same bits
+        loss_row[row] = tcol >= 0 ? lse - xt : __builtin_nanf("");
+        rank_out[row] = above;
+        continue;
+      }
       const long long tg = target[row];
       float loss = 0.f;
       if constexpr (SOFT) {
@@ -271,15 +318,15 @@ inline int ce_grid(int M, int rows_per_wg) {
   return (int)(g < CE_GRID_CAP ? g : CE_GRID_CAP);
 }
 
-template <bool BF16, bool VEC, bool SOFT>
+template <bool BF16, bool VEC, bool SOFT, bool RANK = false>
 void launch_ce_fwd(const void* logits, const long long* target, float* loss_row, float* lse, int M, int V, int ld, long long ignore_index,
-                   Soft soft, hipStream_t s) {
+                   Soft soft, hipStream_t s, int* rank = nullptr) {
   if (V > CE_WIDE_V)
-    hipLaunchKernelGGL((ce_fwd_kernel<BF16, VEC, true, SOFT>), dim3(ce_grid(M, 1)), dim3(256), 0, s, logits, target, loss_row, lse, M, V, ld,
-                       ignore_index, soft);
+    hipLaunchKernelGGL((ce_fwd_kernel<BF16, VEC, true, SOFT, RANK>), dim3(ce_grid(M, 1)), dim3(256), 0, s, logits, target, loss_row, lse, M, V,
+                       ld, ignore_index, soft, rank);
   else
-    hipLaunchKernelGGL((ce_fwd_kernel<BF16, VEC, false, SOFT>), dim3(ce_grid(M, 4)), dim3(256), 0, s, logits, target, loss_row, lse, M, V, ld,
-                       ignore_index, soft);
+    hipLaunchKernelGGL((ce_fwd_kernel<BF16, VEC, false, SOFT, RANK>), dim3(ce_grid(M, 4)), dim3(256), 0, s, logits, target, loss_row, lse, M, V,
+                       ld, ignore_index, soft, rank);
 }
 
 template <bool IN_BF16, bool OUT_BF16, bool SOFT>
@@ -423,5 +470,66 @@ extern "C" int vitamd_embed_tokens_bwd(const float* g, const long long* ids, flo
   if (!g || !ids || !dtok || !dpos) return VITAMD_ERR_ARG;
   hipLaunchKernelGGL(embed_tokens_bwd_kernel, dim3(S, (D + 255) / 256), dim3(256), 0, (hipStream_t)stream, g, ids, dtok, dpos, B, S, D,
                      tok_rows);
+  return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------ evaluation
+namespace {
+
+// The second launch of vitamd_classify_metrics: one workgroup, a fixed order.  Over the counted rows (rank >= 0) of this call: the fp64
+// sum of loss_row, the rows, the rows of rank 0 and the rows of rank < topk; thread 0 then ADDS the four to the caller's accumulators
+// with ordinary loads and stores (launches on one stream are ordered: no atomics).
+__global__ __launch_bounds__(1024) void metrics_sum_kernel(const float* __restrict__ loss_row, const int* __restrict__ rank,
+                                                          double* __restrict__ loss_sum, long long* __restrict__ counts, int M, int topk) {
+  __shared__ double ssum[16];
+  __shared__ int scnt[3][16];
+  double a = 0.0;
+  int n = 0, n1 = 0, nk = 0;
+  for (int i = threadIdx.x; i < M; i += 1024) {
+    const int r = rank[i];
+    if (r < 0) continue;
+    a += (double)loss_row[i];
+    n += 1;
+    n1 += r == 0 ? 1 : 0;
+    nk += r < topk ? 1 : 0;
+  }
+  a = wave_sum(a);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n += __shfl_xor(n, o, 64);
+    n1 += __shfl_xor(n1, o, 64);
+    nk += __shfl_xor(nk, o, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { ssum[w] = a; scnt[0][w] = n; scnt[1][w] = n1; scnt[2][w] = nk; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  a = 0.0; n = 0; n1 = 0; nk = 0;
+  for (int i = 0; i < 16; ++i) { a += ssum[i]; n += scnt[0][i]; n1 += scnt[1][i]; nk += scnt[2][i]; }
+  loss_sum[0] += a;
+  counts[0] += n;
+  counts[1] += n1;
+  counts[2] += nk;
+}
+
+}  // namespace
+
+extern "C" int vitamd_classify_metrics(const void* logits, int logits_bf16, const long long* target, float* loss_row, int* rank,
+                                       double* loss_sum, long long* counts, long M, int V, long ld, int topk, long long ignore_index,
+                                       void* stream) {
+  if (M < 1 || M > 0x7fffffffL || V < 2 || V > CE_MAX_V || ld < V || ld > 0x7fffffffL) return VITAMD_ERR_SHAPE;
+  if (!logits || !target || !loss_row || !rank || !loss_sum || !counts || topk < 1 || topk > V) return VITAMD_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int m = (int)M, l = (int)ld;
+  const Soft none{nullptr, nullptr, 0.f};
+  const bool vec = aligned16(logits) && l % (logits_bf16 ? 8 : 4) == 0;
+  if (logits_bf16) {
+    if (vec) launch_ce_fwd<true, true, false, true>(logits, target, loss_row, nullptr, m, V, l, ignore_index, none, s, rank);
+    else launch_ce_fwd<true, false, false, true>(logits, target, loss_row, nullptr, m, V, l, ignore_index, none, s, rank);
+  } else {
+    if (vec) launch_ce_fwd<false, true, false, true>(logits, target, loss_row, nullptr, m, V, l, ignore_index, none, s, rank);
+    else launch_ce_fwd<false, false, false, true>(logits, target, loss_row, nullptr, m, V, l, ignore_index, none, s, rank);
+  }
+  hipLaunchKernelGGL(metrics_sum_kernel, dim3(1), dim3(1024), 0, s, (const float*)loss_row, (const int*)rank, loss_sum, counts, m, topk);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }

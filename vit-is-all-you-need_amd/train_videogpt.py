@@ -81,6 +81,17 @@ class VideoGPT(nn.Module):
         h = self.transformer(lm.token_embed(inp, self.tok_embed.weight, self.pos_embed.weight))
         return lm.linear_cross_entropy(h, self.proj.weight, self.proj.bias, y.reshape(B * T * N))
 
+    def eval_logits(self, x):
+        """x [B, T, N] token ids -> (logits [B*T*N, codebook_size], targets int64 [B*T*N]): the validation route, what
+        vitamd.metrics.ClassifyMetrics.update takes.  Where lm.fused_head_applies holds the logits are bf16 straight from the head GEMM
+        (lm.token_embed, the stack, lm.head_logits: the numbers `loss` takes its cross-entropy of, never in fp32); otherwise
+        functions.linear's fp32 logits.  No graph is kept under torch.no_grad()."""
+        B, T, N = x.shape
+        y = x.reshape(B, T * N)
+        inp = torch.cat([self._sos(B, x.device), y[:, :-1]], dim=-1)
+        h = self.transformer(lm.token_embed(inp, self.tok_embed.weight, self.pos_embed.weight))
+        return lm.head_logits(h, self.proj.weight, self.proj.bias), y.reshape(B * T * N)
+
     def _head(self, h_last):
         """fp32 logits [B, codebook_size] of hidden states [B, D]: the skinny-M GEMM (one row per sequence) where its shape rules hold,
         else the padded generic Linear"""
@@ -268,6 +279,27 @@ def train_step(model, tokens, optim, lr_sched=None):
     return loss
 
 
+def evaluate(model, token_batches, topk=5, metrics=None):
+    """Token-level validation of a VideoGPT: the model in eval mode under torch.no_grad() over `token_batches` of ids [B, T, N], every
+    batch's eval_logits added to a vitamd.metrics.ClassifyMetrics on the device (metrics: one to continue; None: a fresh one).  The host
+    reads nothing before the final result() -> {"loss" (mean next-token cross-entropy), "top1", "topk" (token accuracies), "count",
+    "perplexity"}.  model.training is put back, also when a batch raises."""
+    from vitamd.metrics import ClassifyMetrics
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for tokens in token_batches:
+                if metrics is None:
+                    metrics = ClassifyMetrics(topk=topk, device=tokens.device)
+                metrics.update(*model.eval_logits(tokens))
+    finally:
+        model.train(was_training)
+    if metrics is None:
+        raise ValueError("evaluate: no batches")
+    return metrics.result()
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="VideoGPT training on synthetic tokens (MI355X-native path)")
     p.add_argument("--frame_size", type=int, default=64)
@@ -291,6 +323,10 @@ def parse_args(argv=None):
     p.add_argument("--image_size", type=int, default=64, help="frame side for --tokenizer tatitok")
     p.add_argument("--patch_size", type=int, default=16, help="patch side for --tokenizer tatitok")
     p.add_argument("--condition_frames", type=int, default=1, help="frames the final generation is conditioned on (--tokenizer tatitok)")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="evaluate every N training steps on seeded held-out random tokens (evaluate / vitamd.metrics.ClassifyMetrics: loss, "
+                        "perplexity and token accuracy from counters on the device, one host read per evaluation); 0 = never")
+    p.add_argument("--eval_batches", type=int, default=2, help="the batches of one evaluation (--eval_every)")
     return p.parse_args(argv)
 
 
@@ -314,6 +350,9 @@ def make_optim(model, args):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
+        raise SystemExit("--eval_every needs N >= 0 and --eval_batches >= 1")
+    topk = min(5, args.codebook_size)                                 # of the evaluations: top-5, or all the classes of a smaller head
     dev = torch.device("cuda")
     cfg = VideoGPTConfig(args.frame_size, args.codebook_size, args.transformer, args.max_frames, args.dropout)
     model = VideoGPT(cfg).to(dev)
@@ -331,11 +370,20 @@ def main(argv=None):
     if args.graph:
         from vitamd.graph import GraphedTrainStep
         graphed = GraphedTrainStep(model, lambda tok: model.loss(tok), (tokens,), optim)      # refuses dropout > 0
+    val = None
+    if args.eval_every > 0:                                       # held-out ids under their own seed
+        gv = torch.Generator(device="cpu").manual_seed(1)
+        val = [torch.randint(0, args.codebook_size, (args.bs, args.max_frames, args.frame_size), generator=gv).to(dev)
+               for _ in range(args.eval_batches)]
     for step in range(args.train_steps):
         t0 = time.time()
         loss = graphed(tokens) if graphed is not None else train_step(model, tokens, optim, sched)
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} {tokens.numel() / (time.time() - t0):.0f} tokens/s")
+        if val is not None and (step + 1) % args.eval_every == 0:
+            r = evaluate(model, val, topk=topk)
+            print(f"step {step} val loss {r['loss']:.4f} perplexity {r['perplexity']:.2f} top1 {r['top1']:.4f} top{topk} "
+                  f"{r['topk']:.4f} over {r['count']} tokens")
     if titok is not None:
         model.eval()
         cond = min(max(args.condition_frames, 1), args.max_frames - 1)

@@ -75,6 +75,27 @@ def train_step(model, images, labels, optim, lr_sched=None, loss_fn=None):
     return loss
 
 
+def evaluate(model, batches, topk=5, metrics=None):
+    """The validation half of the reference loop (train_vit.py:114-128) without its per-batch .item()s: the model in eval mode under
+    torch.no_grad() over `batches` of (images fp32 [B, C, H, W] or vitamd.data.Frames, int64 labels on the device), every batch added to
+    a vitamd.metrics.ClassifyMetrics on the device (metrics: one to continue; None: a fresh one).  The host reads nothing before the
+    final result() -> {"loss", "top1", "topk", "count", "perplexity"}.  model.training is put back, also when a batch raises."""
+    from vitamd.metrics import ClassifyMetrics
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for images, labels in batches:
+                if metrics is None:
+                    metrics = ClassifyMetrics(topk=topk, device=labels.device)
+                metrics.update(model(images), labels)
+    finally:
+        model.train(was_training)
+    if metrics is None:
+        raise ValueError("evaluate: no batches")
+    return metrics.result()
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="ViT classifier training on synthetic data (MI355X-native path)")
     p.add_argument("--image_size", type=int, default=224)
@@ -115,7 +136,33 @@ def parse_args(argv=None):
     p.add_argument("--graph", action="store_true",
                    help="one graph launch per iteration (vitamd.graph.GraphedTrainStep): forward, loss, backward, the clip, the LR schedule "
                         "and the AdamW update, all replayed from the device; needs --dropout 0 (and not --u8)")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="evaluate every N training steps on seeded held-out random data (evaluate / vitamd.metrics.ClassifyMetrics: loss, "
+                        "top-1 and top-k from counters on the device, one host read per evaluation); 0 = never")
+    p.add_argument("--eval_batches", type=int, default=2, help="the batches of one evaluation (--eval_every)")
     return p.parse_args(argv)
+
+
+def make_val_batches(args, dev):
+    """-> a function whose every call yields the same args.eval_batches held-out batches (their own seed): fp32 images, or with --u8 uint8
+    frames through the training feed's loader with train=False (the centre crop; after --rrc / --resize, Resize + CenterCrop)"""
+    g = torch.Generator(device="cpu").manual_seed(1)
+    n, size = args.eval_batches, args.image_size
+    labels = [torch.randint(0, args.num_classes, (args.bs,), generator=g) for _ in range(n)]
+    if not args.u8:
+        images = [torch.randn(args.bs, 3, size, size, generator=g) for _ in range(n)]
+        return lambda: ((x.to(dev), y.to(dev)) for x, y in zip(images, labels))
+    from vitamd.data import IMAGENET_MEAN, IMAGENET_STD, DeviceLoader
+    resizing = args.rrc or args.resize is not None
+    src_hw = (size + size // 7,) * 2
+    if resizing:
+        src_hw = tuple(args.src_size) if args.src_size is not None else (size * 10 // 7, size * 5 // 4)
+    u8 = [torch.randint(0, 256, (args.bs, *src_hw, 3), generator=g, dtype=torch.uint8) for _ in range(n)]
+    kw = dict(patch=args.patch_size, image=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, train=False)
+    if resizing:
+        from vitamd.resize import ResizeLoader
+        return lambda: ResizeLoader(zip(u8, labels), dev, size, mode="rrc" if args.rrc else "resize_crop", resize_to=args.resize, **kw)
+    return lambda: DeviceLoader(zip(u8, labels), dev, size, **kw)
 
 
 def make_optim(model, args):
@@ -133,6 +180,9 @@ def main(argv=None):
     if args.graph and args.u8:
         raise SystemExit("--graph with --u8: the device loader hands over vitamd.data.Frames (patch rows in buffers of its own), not tensors "
                          "to copy into a graph's static inputs; a graph-fed loader is not built - use one or the other")
+    if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
+        raise SystemExit("--eval_every needs N >= 0 and --eval_batches >= 1")
+    topk = min(5, args.num_classes)                                 # of the evaluations: top-5, or all the classes of a smaller head
     mixing = args.mixup > 0 or args.cutmix > 0
     if mixing and not args.u8:
         raise SystemExit("--mixup / --cutmix mix inside the device input feed (vitamd.mix.MixLoader): they need --u8")
@@ -203,6 +253,7 @@ def main(argv=None):
         from vitamd.graph import GraphedTrainStep
         hard_loss = nn.functional.cross_entropy
         graphed = GraphedTrainStep(model, lambda x, y: hard_loss(model(x), y), (images, labels), optim)      # refuses dropout > 0
+    val = make_val_batches(args, dev) if args.eval_every > 0 else None
     for step in range(args.train_steps):
         t0 = time.time()
         if feed is not None:
@@ -210,6 +261,9 @@ def main(argv=None):
         loss = graphed(images, labels) if graphed is not None else train_step(model, images, labels, optim, sched, loss_fn)
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} {args.bs / (time.time() - t0):.0f} img/s")
+        if val is not None and (step + 1) % args.eval_every == 0:
+            r = evaluate(model, val(), topk=topk)
+            print(f"step {step} val loss {r['loss']:.4f} top1 {r['top1']:.4f} top{topk} {r['topk']:.4f} over {r['count']} samples")
 
 
 if __name__ == "__main__":

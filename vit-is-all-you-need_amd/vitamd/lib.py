@@ -85,6 +85,7 @@ SIGNATURES = {
     "vitamd_cross_entropy_bwd": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _P],
     "vitamd_soft_cross_entropy_fwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
     "vitamd_soft_cross_entropy_bwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vitamd_classify_metrics": [_P, _I, _P, _P, _P, _P, _P, _L, _I, _L, _I, _LL, _P],
     "vitamd_embed_tokens_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vitamd_embed_tokens_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vitamd_assemble_tokens_grid_cap": [],

@@ -258,3 +258,21 @@ def prefixed_rows(body, pos_weight, prefix_weight):
     """cat([prefix_weight expanded over the batch, body + pos_weight[:S]], dim=1) for body fp32 or bf16 [B, S, D] -> fp32 [B, E+S, D] in
     one kernel; the body's gradient (in its dtype) is the tail of the incoming one, those of the two tables come from one pass over it."""
     return PrefixedRowsFn.apply(body, pos_weight, prefix_weight)
+
+
+# ------------------------------------------------------------------------------------------------ the head alone (DESIGN.md section 24)
+def head_logits(h, weight, bias):
+    """nn.Linear(h) for evaluation, h [..., D] -> logits [M, V] with the leading dimensions flattened, no gradient.  Where
+    fused_head_applies(V, D): bf16, written by the head GEMM exactly as LinearCrossEntropyFn.forward writes them (the numbers the
+    training loss is taken of; no fp32 logits exist).  Other shapes: functions.linear's fp32 logits."""
+    if not isinstance(h, torch.Tensor) or not isinstance(weight, torch.Tensor) or h.dim() < 1 or weight.dim() != 2 or h.shape[-1] != weight.shape[1]:
+        raise ops._lib.VitamdError("head_logits: expected h [..., D] and weight [V, D]")
+    V, D = weight.shape
+    if not h.is_cuda or not weight.is_cuda:
+        raise ops._lib.VitamdError("head_logits: expected ROCm device tensors (the HIP kernels are the only implementation)")
+    with torch.no_grad():
+        if not fused_head_applies(V, D):
+            return linear(h.reshape(-1, D), weight, bias)
+        hb = ops.cast_bf16(_f32c(h.reshape(-1, D)))
+        wb, _ = WEIGHTS.get(weight, True)
+        return ops.gemm_nt(hb, wb, ops.EPI_BIAS_BF16, bias=None if bias is None else _f32c(bias))

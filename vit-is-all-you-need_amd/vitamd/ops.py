@@ -1562,3 +1562,36 @@ def frames_erase(patches, image, patch, rec, fill, seed, step, hw=None):
     with torch.cuda.device(dev):
         _lib.check(_L().vitamd_frames_erase(_p(patches), _p(image), B, C, H, W, patch if patches is not None else 0, _p(rec), _p(fill), K, seed, step,
                                             _stream()), f"frames_erase[B={B},C={C},out={H}x{W},p={patch},K={K}]")
+
+
+# ------------------------------------------------------------------------------------------ evaluation
+def classify_metrics(logits, target, loss_sum, counts, topk=5, ignore_index=-100, loss_row=None, rank=None):
+    """One validation batch, added to counters on the device (include/vitamd.h vitamd_classify_metrics): logits fp32 / bf16 [M, V] (unit
+    inner stride, read once as stored) against target int64 [M].  loss_sum fp64 [1] += the sum of the per-row losses, counts int64 [3] +=
+    (rows, rows whose target is the argmax, rows whose target is among the topk largest), over the rows whose target is not
+    ignore_index.  loss_row fp32 [>= M] and rank int32 [>= M]: the per-row scratch (None: zeros of this call's own); their first M
+    elements hold the row losses and the targets' ranks afterwards (-1: ignored).  Nothing synchronises and nothing is read back; a
+    target outside [0, V) counts as a wrong row with a NaN loss.  -> (loss_row[:M], rank[:M])."""
+    V = logits.shape[-1] if isinstance(logits, torch.Tensor) and logits.dim() == 2 else None
+    if not isinstance(topk, int) or isinstance(topk, bool) or topk < 1 or (V is not None and topk > max(V, 2)):
+        raise ValueError(f"classify_metrics: topk must be an integer in 1 .. V{'' if V is None else ' = ' + str(V)}, got {topk!r}")
+    M, V, ld, is_bf16 = _need_logits(logits)          # V outside 2 .. 65536: its own ValueError
+    _need(target, torch.int64, "target", 1)
+    if target.numel() != M:
+        raise _lib.VitamdError(f"target: expected {M} elements, got {target.numel()}")
+    _need(loss_sum, torch.float64, "loss_sum", 1); _need(counts, torch.int64, "counts", 1)
+    if loss_sum.numel() != 1 or counts.numel() != 3:
+        raise _lib.VitamdError("classify_metrics: expected loss_sum fp64 [1] and counts int64 [3]")
+    if loss_row is None:
+        loss_row = torch.zeros((M,), dtype=F32, device=logits.device)
+    if rank is None:
+        rank = torch.zeros((M,), dtype=torch.int32, device=logits.device)
+    _need(loss_row, F32, "loss_row", 1); _need(rank, torch.int32, "rank", 1)
+    if loss_row.numel() < M or rank.numel() < M:
+        raise _lib.VitamdError(f"classify_metrics: loss_row and rank must hold at least {M} elements")
+    if any(t.device != logits.device for t in (target, loss_sum, counts, loss_row, rank)):
+        raise _lib.VitamdError("classify_metrics: logits, target, the accumulators and the scratch must be on one device")
+    with torch.cuda.device(logits.device):
+        _lib.check(_L().vitamd_classify_metrics(_p(logits), is_bf16, _p(target), _p(loss_row), _p(rank), _p(loss_sum), _p(counts), M, V, ld, topk,
+                                                int(ignore_index), _stream()), f"classify_metrics[M={M},V={V},ld={ld},topk={topk}]")
+    return loss_row[:M], rank[:M]
