@@ -219,6 +219,7 @@ int vitamd_attention_fwd(const void* qkv, void* o, float* lse2, int B, int N, in
 /* Forward fused with the residual add that follows it in the layer (transformer.py:44 `x = x + attn(LN(x))`):
  * resid_out fp32 [B*N, H*64] = resid_in + o (o as rounded to bf16), written by the same workgroup that produces o, so the next
  * LayerNorm reads the stream once (6 instead of 12 B per element).  N <= 256 (the register-resident-softmax kernel). */
+#define VITAMD_ATTN_RESID_MAX_N 256
 int vitamd_attention_fwd_resid(const void* qkv, void* o, float* lse2, const float* resid_in, float* resid_out, int B, int N, int H,
                                int head_dim, int causal, float dropout_p, unsigned long long seed, void* stream);
 /* dqkv bf16 [B,N,3,H,64]; delta fp32 [B,H,N] is scratch written by the call; dbias (may be NULL) fp32
@@ -235,6 +236,8 @@ int vitamd_attention_bwd(const void* qkv, const void* o, const float* lse2, cons
  * sign of zeros).  vitamd_attention_keep_forms(N, nq) returns a bit mask of the shapes served: 1 = forward (129 <= N <= 256, the
  * eight-wave kernel), 2 = backward (33 <= N <= 224 and nq <= 128, the pipelined kernels); the calls return VITAMD_ERR_SHAPE elsewhere and the caller
  * runs the full-size forms (vitamd/functions.py does). */
+#define VITAMD_ATTN_KEEP_FWD 1
+#define VITAMD_ATTN_KEEP_BWD 2
 int vitamd_attention_keep_forms(int N, int nq);
 int vitamd_attention_fwd_keep(const void* qkv, void* o, float* lse2, int B, int N, int H, int head_dim, int nq, void* stream);
 int vitamd_attention_bwd_keep(const void* qkv, const void* o, const float* lse2, const void* d_o, void* dqkv, float* delta,
@@ -278,6 +281,7 @@ int vitamd_attention_form(int N, int causal, float dropout_p, int resid, int nq,
  * reads) to cache positions *len .. *len+T-1.  T = 1 decodes, T = prompt length prefills.  T > Lmax: VITAMD_ERR_SHAPE; rows whose
  * position would reach Lmax are not written (the host binding refuses len + T > Lmax against its own copy of the length).
  * replaces the K/V half of transformer.py:27 for the cached path (the reference recomputes it for the whole prefix). */
+#define VITAMD_DECODE_MAX_LEN 16384   /* of Lmax, and of N in the attention entry points above */
 int vitamd_kv_append(const void* qkv, void* k_cache, void* v_cache, const int* len, int B, int T, int H, int head_dim, int Lmax,
                      void* stream);
 /* Single-query attention: for each (b, h) the query row of qkv bf16 [B, 3*H*64] (one new token per sequence, already appended at
@@ -297,6 +301,7 @@ int vitamd_decode_attention(const void* qkv, const void* k_cache, const void* v_
  * every GELU epilogue of vitamd_gemm_nt_bf16), VITAMD_EPI_RESID_F32 (aux fp32 [M,N]) or VITAMD_EPI_F32 (out f32 = acc + bias), with
  * the semantics of vitamd_gemm_nt_bf16; bias (fp32 [N], rounded to bf16 as autocast does) may be NULL.  Rows are dense (ld = K / N).
  * replaces transformer.py:21,27,37-39,44 and train_videogpt.py:43,53 (the Linears) at one row per sequence. */
+#define VITAMD_SKINNY_MAX_M 64
 long vitamd_gemm_skinny_ws_bytes(int M, int N, int K);
 int vitamd_gemm_skinny_bf16(const void* A, const void* W, void* out, void* out2, const float* bias, const float* aux, int M, int N,
                             int K, int epi, float* ws, long ws_bytes, void* stream);
@@ -332,6 +337,7 @@ int vitamd_decode_embed(const float* tok_table, const float* pos_table, const lo
  * fixed-point integers: no result depends on an order of summation, every call gives the same bits.
  * temperature, top_k or top_p out of range, or a missing pointer: VITAMD_ERR_ARG (after the shape check).
  * replaces the `torch.argmax` of train_videogpt.py:63 where a sampled continuation is wanted (the reference has no sampler). */
+#define VITAMD_SAMPLE_MAX_V 65536
 int vitamd_sample_logits(const float* logits, long long* token, float* info, const float* u, const unsigned long long* step, int B, int V,
                          int ld, float temperature, int top_k, float top_p, unsigned long long seed, void* stream);
 
@@ -346,6 +352,7 @@ int vitamd_sample_logits(const float* logits, long long* token, float* info, con
  * in a fixed order and counts with an integer: no float atomics, every result is bit-reproducible.
  * M >= 1, 2 <= V <= 65536, ld >= V, else VITAMD_ERR_SHAPE; a missing pointer VITAMD_ERR_ARG (after the shape check).
  * replaces train_videogpt.py:52-53 and train_vit.py:101-103 (F.cross_entropy under autocast). */
+#define VITAMD_CE_MAX_V 65536
 int vitamd_cross_entropy_fwd(const void* logits, int logits_bf16, const long long* target, float* loss_row, float* lse, float* stats,
                              int M, int V, int ld, long long ignore_index, void* stream);
 /* The rows one sweep of the (capped) cross-entropy grid covers at this V; an M above it makes workgroups loop over further rows.  For
@@ -506,6 +513,7 @@ int vitamd_frames_prep_mix(const unsigned char* src, const long long* index, con
  * Only enqueues on `stream`; no backward.
  * replaces the Resize / RandomResizedCrop of the reference's loaders (datasets.py: Resize(image_size) in front of RandomCrop; timm's
  * RandomResizedCrop in the DeiT recipe) on the CPU workers, and the host-side scaling of raw video frames to the tokenizer's size. */
+#define VITAMD_FRAMES_MAX_SIZE 8192   /* of Hs, Ws, H, W and the virtual sizes Hv, Wv */
 int vitamd_frames_prep_resize(const unsigned char* src, const long long* index, const int* box, const float* mean, const float* std,
                               void* patches_bf16, float* image, int B, int Nsrc, int Hs, int Ws, int C, int H, int W, int p, void* stream);
 int vitamd_frames_prep_resize_grid_cap(void);
@@ -570,6 +578,7 @@ int vitamd_frames_to_u8(const float* img, unsigned char* out, int B, int C, int 
  * Nothing is launched in either case.  Only enqueues on `stream`; no backward.
  * replaces timm's RandomErasing (--reprob, --remode const / rand / pixel) on the normalised fp32 device batch, and the im2col a
  * caller of the fused feed would have to run again behind it. */
+#define VITAMD_ERASE_MAX_BOXES 8
 int vitamd_frames_erase(void* patches_bf16, float* image, int B, int C, int H, int W, int p, const int* rec, const float* fill, int K,
                         unsigned long long seed, unsigned long long step, void* stream);
 int vitamd_frames_erase_grid_cap(void);
@@ -586,9 +595,14 @@ int vitamd_dropout_bf16(const void* in, void* out, long n, long group, float dro
 int vitamd_dropout_f32(const float* in, float* out, long n, long group, float dropout_p, unsigned long long seed, void* stream);
 /* W fp32 [N,K] -> bf16 [N,K] (wb, may be NULL) and transposed bf16 [K,N] (wbt, may be NULL). */
 int vitamd_cast_transpose_weight(const float* w, void* wb, void* wbt, int N, int K, void* stream);
-/* The same for n weights in ONE launch.  desc_dev: device array of n records
- * {const float* w; bf16* wb; bf16* wbt; int N, K, first_tile, tiles_k;} (40 bytes, 8-byte aligned),
+/* The same for n weights in ONE launch.  desc_dev: device array of n vitamd_cast_desc records,
  * first_tile = running sum of ceil(N/64)*ceil(K/64), tiles_k = ceil(K/64); total_tiles = the final sum. */
+typedef struct vitamd_cast_desc {
+  const float* w;          /* fp32 [N,K] */
+  void* wb;                /* bf16 [N,K], may be NULL */
+  void* wbt;               /* bf16 [K,N], may be NULL */
+  int N, K, first_tile, tiles_k;
+} vitamd_cast_desc;        /* 40 bytes, 8-byte aligned */
 int vitamd_cast_transpose_batched(const void* desc_dev, int n, int total_tiles, void* stream);
 /* images fp32 [B,C,H,W] -> patches bf16 [B*(H/p)*(W/p), C*p*p], vector order (c,kh,kw): the
  * contraction order of Conv2d(kernel=stride=p), train_vit.py:34,39. */
@@ -701,6 +715,7 @@ int vitamd_sched_advance(void* rows_dev, void* sched_dev, int n_rows, void* stre
  *   q[m,:]    = u + (p - u) with p = codebook[idx[m],:], the RAW row;  *loss = 1.25 * mean over M*d of (p - u)^2.
  * ws: vitamd_vq_quantize_ws_bytes(M, K, d) bytes of scratch (negative: the shape error).  Its first K*d floats hold e^ after the call.
  * The loss is summed from per-workgroup partials in a fixed order: the same inputs give the same bits. */
+#define VITAMD_VQ_MAX_D 64
 long vitamd_vq_quantize_ws_bytes(int M, int K, int d);
 int vitamd_vq_quantize_fwd(const float* x, const float* codebook, float* unit, float* rnorm, float* q, long long* idx, float* loss, float* ws,
                            int M, int K, int d, void* stream);
@@ -787,6 +802,7 @@ int vitamd_dwconv7_bwd(const void* dy, int dy_bf16, const float* w, const float*
  * normalised to sum 1.  Sums are fp32: along W first, then along H.
  * Outputs (either may be NULL, not both): rows_bf16 [B*(S/4)^2, 64], the operand of the 4x4 stride-4 stem convolution - row
  * b*(S/4)^2 + (oh/4)*(S/4) + ow/4, column c*16 + (oh%4)*4 + ow%4, columns 48..63 written as zeros; nchw fp32 [B,3,S,S]. */
+#define VITAMD_RESIZE_ROW_LD 64   /* columns of a rows_bf16 row: 3 * 4 * 4 = 48 patch values, zero-padded */
 int vitamd_resize_norm_fwd(const float* img, const int* start_h, const float* taps_h, int Th, const int* start_w, const float* taps_w, int Tw,
                            const float* mean, const float* stdv, void* rows_bf16, float* nchw, int B, int C, int Hin, int Win, int S,
                            void* stream);

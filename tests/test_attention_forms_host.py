@@ -4,17 +4,15 @@ it can answer must be the code of a case of _attention_ref.FORM_CASES / MATRIX /
 each tile-templated one at both edges of its tile count.  A dispatch change that creates an unreached instantiation fails here.  Also:
 the query's refusals are the entry points' own."""
 import ctypes
-import os
 import re
 
 import pytest
 
+import _abi
 import _attention_ref as R
 
 SHAPE, ARG = 1, 2            # VITAMD_ERR_SHAPE, VITAMD_ERR_ARG
 NAN = float("nan")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 _buf = (ctypes.c_float * 64)()
 P = ctypes.addressof(_buf)   # a dummy pointer no refused call dereferences
 
@@ -50,8 +48,8 @@ def swept(form):
 # ------------------------------------------------------------------------------------------ the binding
 def test_the_query_is_in_header_and_binding_and_the_numbers_agree():
     from vitamd import lib, ops
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    assert re.search(r"\bint\s+vitamd_attention_form\s*\(", header) and "vitamd_attention_form" in lib.SIGNATURES
+    header = _abi.header()
+    assert _abi.declared()[1]["vitamd_attention_form"] == "int" and "vitamd_attention_form" in lib.SIGNATURES
     assert lib.ABI_VERSION == 9          # additive: the version does not move
     defines = {n: int(v, 0) for n, v in re.findall(r"#define VITAMD_ATTN_(\w+) (0x[0-9a-f]+|\d+)\b", header)}
     for name in ("FWD_SMALL", "FWD_SMALL8", "FWD_LOOP", "FWD_LONG", "BWD_PIPE", "BWD_LOOP", "BWD_LONG"):

@@ -7,6 +7,7 @@ import os
 import pytest
 import torch
 
+import _abi
 import _code_titok_ref as C
 import vit_oracle as O
 from conftest import ROOT, load_golden
@@ -150,7 +151,7 @@ def test_codes_from_refuses_what_is_not_a_batch_of_ids():
 def test_symbols_are_exported_typed_and_in_the_header():
     from vitamd import lib, ops
     L = lib.load()
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
+    header = _abi.header()
     for name in NEW_SYMBOLS:
         assert name in lib.SIGNATURES and f"int {name}(" in header
         fn = getattr(L, name)

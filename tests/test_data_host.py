@@ -3,11 +3,11 @@ pointers that no such call dereferences, as in test_launch_args_host.py), the CP
 against the lookup table, the crop geometry, and the argument checks of vitamd.data."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
+import _abi
 import _data_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,9 +27,7 @@ def L():
 
 def test_new_symbols_are_bound_with_the_headers_argument_counts(L):
     from vitamd import lib, ops
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    declared = {n: (0 if a.strip() in ("", "void") else a.count(",") + 1)
-                for n, a in re.findall(r"\bint\s+(vitamd_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.S)}
+    declared, _ = _abi.declared()
     for name, n in NEW_SYMBOLS.items():
         assert declared[name] == n == len(lib.SIGNATURES[name]), name
         assert hasattr(L, name)

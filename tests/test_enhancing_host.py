@@ -2,15 +2,14 @@
 reference's golden (state-dict keys and shapes, the sincos tables, the initialisation rule, the refusals), and the float64 restatements
 of tests/_enhancing_ref.py against torch - with the checks the GPU tests use shown to fail for the listed mistakes."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import _abi
 import _enhancing_ref as E
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
 NAMES = {"vitamd_tanh_bf16": 4, "vitamd_tanh_bwd_bf16": 5, "vitamd_recon_l1_fwd": 13, "vitamd_recon_l1_bwd": 13}
@@ -26,13 +25,13 @@ def _tiny(g=None):
 # ------------------------------------------------------------------------------------------------ the library surface
 def test_the_four_symbols_are_bound():
     from vitamd import lib
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
+    header = _abi.header()
     dll = lib.load()
     for name, nargs in NAMES.items():
         assert name in lib.SIGNATURES and f"int {name}(" in header
         fn = getattr(dll, name)
         assert len(lib.SIGNATURES[name]) == nargs and fn.argtypes == lib.SIGNATURES[name] and fn.restype is ctypes.c_int
-        params = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", header, flags=re.S).group(1)
+        params = _abi.declaration(name)
         assert params.count(",") + 1 == nargs
     assert dll.vitamd_abi_version() == 9 == lib.ABI_VERSION
 

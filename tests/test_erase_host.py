@@ -4,16 +4,15 @@ checks of test_gpu_erase.py bite (every planted mistake of _erase_ref fails them
 import ctypes
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import _abi
 import _erase_ref as R
 import _poison as P
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE, ARG = 1, 2
 NEW_SYMBOLS = {"vitamd_frames_erase": 13, "vitamd_frames_erase_grid_cap": 0}
 
@@ -35,9 +34,7 @@ def _erase(**kw):
 # ---------------------------------------------------------------------------------------------- the binding and the refusals
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_argument_counts(L):
     from vitamd import lib
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    declared = {n: (0 if a.strip() in ("", "void") else a.count(",") + 1)
-                for n, a in re.findall(r"\bint\s+(vitamd_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.S)}
+    declared, _ = _abi.declared()
     for name, n in NEW_SYMBOLS.items():
         assert declared[name] == n == len(lib.SIGNATURES[name]), name
         fn = getattr(L, name)

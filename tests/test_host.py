@@ -3,18 +3,18 @@ schedule against the reference's trace, the C-ABI library's exported symbols, an
 product path refuses to run without a device instead of falling back."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
+import _abi
 from conftest import ROOT, load_golden
 
 
 def test_library_exports_every_declared_symbol():
     from vitamd import lib
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    declared = set(re.findall(r"\b(?:int|long)\s+(vitamd_\w+)\s*\(", header))
+    counts, _ = _abi.declared()
+    declared = set(counts)
     assert declared == set(lib.SIGNATURES), (declared ^ set(lib.SIGNATURES))
     if not os.path.exists(lib.LIB_PATH):
         lib.build()
@@ -23,8 +23,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(dll, name), name
     assert lib.load().vitamd_abi_version() == lib.ABI_VERSION
     # ... with as many parameters in the binding as in the header (a dropped or added argument would shift every later one silently)
-    for name, params in re.findall(r"\b(?:int|long)\s+(vitamd_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.S):
-        n = 0 if params.strip() in ("", "void") else params.count(",") + 1
+    for name, n in counts.items():
         assert n == len(lib.SIGNATURES[name]), (name, n, len(lib.SIGNATURES[name]))
 
 

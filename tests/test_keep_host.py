@@ -1,20 +1,18 @@
 """Host-side checks of the kept-row path (no GPU): the new C-ABI names, the split rule for a short reduction, argument checking."""
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi
+
 NEW_SYMBOLS = ("vitamd_layernorm_fwd_keep", "vitamd_layernorm_bwd_keep", "vitamd_attention_keep_forms", "vitamd_attention_fwd_keep",
                "vitamd_attention_bwd_keep")
 
 
 def test_new_entry_points_are_in_header_and_binding():
     from vitamd import lib
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
     for name in NEW_SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
+        assert _abi.declared()[1].get(name) == "int", name
         assert name in lib.SIGNATURES, name
     assert lib.ABI_VERSION == 9          # additive: the version does not move
 

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _abi
 import _lm_ref as R
 
 F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
@@ -98,7 +99,7 @@ def test_symbols_are_exported_and_typed():
     from vitamd import ops
     assert ops.cross_entropy_grid_rows(72) == ops.cross_entropy_grid_rows(4096) == 4 * ops.cross_entropy_grid_rows(4097) > 0
     assert L.vitamd_cross_entropy_grid_rows(1) == -ERR_SHAPE == L.vitamd_cross_entropy_grid_rows(65537)
-    header = open(__import__("os").path.join(__import__("conftest").ROOT, "include", "vitamd.h")).read()
+    header = _abi.header()
     for name in NEW_SYMBOLS:
         assert f"int {name}(" in header
 

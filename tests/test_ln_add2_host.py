@@ -2,13 +2,12 @@
 refusals, and what the poison test demands of vitamd/ (no new uninitialised allocation in the wrappers)."""
 import ctypes
 import os
-import re
 
 import pytest
 
+import _abi
 import _poison as P
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE, ARG = 1, 2            # VITAMD_ERR_SHAPE, VITAMD_ERR_ARG
 _buf = (ctypes.c_float * 64)()
 PTR = ctypes.addressof(_buf)
@@ -22,9 +21,7 @@ def L():
 
 def test_new_symbols_are_declared_and_bound_and_the_abi_version_stays(L):
     from vitamd import lib
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    declared = {n: (0 if a.strip() in ("", "void") else a.count(",") + 1)
-                for n, a in re.findall(r"\bint\s+(vitamd_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.S)}
+    declared, _ = _abi.declared()
     for name, n in (("vitamd_layernorm_fwd_add2", 11), ("vitamd_layernorm_fwd_keep_add2", 13)):
         assert declared[name] == n == len(lib.SIGNATURES[name]), name
         fn = getattr(L, name)

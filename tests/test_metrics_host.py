@@ -8,9 +8,9 @@ import os
 import pytest
 import torch
 
+import _abi
 import _metrics_ref as MR
 import _poison as P
-from conftest import ROOT
 
 F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
 ERR_SHAPE, ERR_ARG = 1, 2
@@ -93,10 +93,7 @@ def test_symbol_is_declared_bound_and_the_abi_stays_9():
     fn = getattr(L, name)
     assert fn.argtypes == lib.SIGNATURES[name] and fn.restype is ctypes.c_int
     assert L.vitamd_abi_version() == 9 == lib.ABI_VERSION
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    start = header.index(f"int {name}(")
-    decl = header[start:header.index(";", start)]
-    assert len(decl[decl.index("(") + 1:decl.rindex(")")].split(",")) == len(lib.SIGNATURES[name]) == 13
+    assert _abi.declared()[1][name] == "int" and len(_abi.declaration(name).split(",")) == len(lib.SIGNATURES[name]) == 13
 
 
 def test_entry_point_refuses_before_any_launch():

@@ -3,15 +3,14 @@ refusals, proof that the checks of test_gpu_mix.py bite (every planted mistake o
 uses), and the conditions tests/test_gpu_poison.py puts on new code in vitamd/."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
+import _abi
 import _mix_ref as R
 import _poison as P
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE, ARG = 1, 2
 NEW_SYMBOLS = {"vitamd_frames_prep_mix": 17, "vitamd_soft_cross_entropy_fwd": 13, "vitamd_soft_cross_entropy_bwd": 16}
 PINNED_SITES = {("ops.py", 137), ("functions.py", 182), ("data.py", 229), ("data.py", 230), ("data.py", 243)}
@@ -106,9 +105,7 @@ def test_mix_refuses_bad_arguments():
 # ---------------------------------------------------------------------------------------------- the binding and the refusals
 def test_new_symbols_are_bound_with_the_headers_argument_counts(L):
     from vitamd import lib
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    declared = {n: (0 if a.strip() in ("", "void") else a.count(",") + 1)
-                for n, a in re.findall(r"\bint\s+(vitamd_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.S)}
+    declared, _ = _abi.declared()
     for name, n in NEW_SYMBOLS.items():
         assert declared[name] == n == len(lib.SIGNATURES[name]), name
         fn = getattr(L, name)

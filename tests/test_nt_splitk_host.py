@@ -2,12 +2,11 @@
 vitamd_gemm_nt_ws_bytes report it (256 CUs are assumed where no device answers), what keeps a launch unsplit, and that vitamd_gemm_nt_plan -
 the description of vitamd_gemm_nt_bf16, which has no workspace - answers what it answered."""
 import ctypes
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi
+
 SHAPE, ARG = 1, 2
 FORM_SMALL, FORM_SPLITK, TILE_BYTES = 1, 6, 128 * 128 * 4
 CUS = 256
@@ -21,9 +20,8 @@ def L():
 
 def test_new_symbols_are_declared_and_bound_and_the_abi_version_stays(L):
     from vitamd import lib, ops
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    declared = {n: (0 if a.strip() in ("", "void") else a.count(",") + 1)
-                for n, a in re.findall(r"\b(?:int|long)\s+(vitamd_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.S)}
+    header = _abi.header()
+    declared, _ = _abi.declared()
     for name, n, restype in (("vitamd_gemm_nt_bf16_ws", 20, ctypes.c_int), ("vitamd_gemm_nt_ws_bytes", 7, ctypes.c_long),
                              ("vitamd_gemm_nt_ws_plan", 7, ctypes.c_int)):
         assert declared[name] == n == len(lib.SIGNATURES[name]), name

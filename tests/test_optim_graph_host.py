@@ -2,23 +2,22 @@
 the advance kernel against optim.hyper_row and utils.lr_factor on every step the GPU test runs, the refusals that need no device, and
 what capturable=True adds to (and keeps out of) the param groups."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+import _abi
 import _optim_graph_ref as R
-from conftest import ROOT
 
 
 def test_symbols_are_declared_bound_and_sized():
     from vitamd import lib, optim
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
+    header = _abi.header()
     L = lib.load()
     for name, nargs, restype in (("vitamd_sched_row_bytes", 0, ctypes.c_long), ("vitamd_sched_advance", 4, ctypes.c_int)):
-        assert re.search(r"\b(?:int|long)\s+%s\s*\(" % name, header), name
+        assert name in _abi.declared()[0], name
         fn = getattr(L, name)
         assert len(lib.SIGNATURES[name]) == nargs and fn.argtypes == lib.SIGNATURES[name] and fn.restype is restype
     assert lib.ABI_VERSION == 9 and L.vitamd_abi_version() == 9                     # additive: no existing signature changed

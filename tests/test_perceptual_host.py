@@ -2,17 +2,15 @@
 against torch's own float64 evaluation, the module's state-dict contract and argument handling, the C ABI's new symbols and refusals, and the
 bounds of the GPU tests against planted mistakes.  No GPU is needed."""
 import ctypes
-import os
-import re
 import warnings
 
 import pytest
 import torch
 
+import _abi
 import _perceptual_ref as R
 
 F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_SHAPE, ERR_ARG = 1, 2
 NEW_SYMBOLS = {"vitamd_dwconv7_fwd": 10, "vitamd_dwconv7_bwd": 10, "vitamd_resize_norm_fwd": 17, "vitamd_resize_norm_bwd": 16}
 RESIZES = [(256, 224), (128, 224), (64, 224), (300, 224), (224, 224), (40, 16), (20, 16), (1, 32), (5, 32)]
@@ -128,12 +126,10 @@ def test_new_symbols_are_bound_with_the_headers_arity():
     from vitamd import lib
     L = lib.load()
     assert L.vitamd_abi_version() == 9 == lib.ABI_VERSION
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
     for name, nargs in NEW_SYMBOLS.items():
         fn = getattr(L, name)
         assert len(lib.SIGNATURES[name]) == nargs and fn.argtypes == lib.SIGNATURES[name] and fn.restype is ctypes.c_int
-        decl = re.search(r"\bint %s\s*\(([^;]*)\);" % name, header)
-        assert decl and len(decl.group(1).split(",")) == nargs, name
+        assert _abi.declared()[1][name] == "int" and len(_abi.declaration(name).split(",")) == nargs, name
 
 
 def test_entry_points_refuse_before_any_launch():

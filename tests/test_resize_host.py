@@ -4,15 +4,14 @@ mistake of _resize_ref.standin is reported at that file's shapes), the host-side
 points and their refusals, and the conditions tests/test_gpu_poison.py puts on new code in vitamd/."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
+import _abi
 import _poison as P
 import _resize_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE, ARG = 1, 2
 NEW_SYMBOLS = {"vitamd_frames_prep_resize": 16, "vitamd_frames_prep_resize_grid_cap": 0}
 PINNED_SITES = {("ops.py", 137), ("functions.py", 182), ("data.py", 229), ("data.py", 230), ("data.py", 243)}
@@ -236,9 +235,7 @@ def test_frames_to_tokens_refuses_size_on_a_float_batch():
 # ---------------------------------------------------------------------------------------------- the binding and the refusals
 def test_new_symbols_are_bound_with_the_headers_argument_counts(L):
     from vitamd import lib, ops
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    declared = {n: (0 if a.strip() in ("", "void") else a.count(",") + 1)
-                for n, a in re.findall(r"\bint\s+(vitamd_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.S)}
+    declared, _ = _abi.declared()
     for name, n in NEW_SYMBOLS.items():
         assert declared[name] == n == len(lib.SIGNATURES[name]), name
         fn = getattr(L, name)

@@ -6,17 +6,16 @@ puts on new code in vitamd/."""
 import ctypes
 import functools
 import os
-import re
 
 import pytest
 import torch
 
+import _abi
 import _poison as P
 import _resize_mix_ref as RM
 import _resize_ref as R
 from test_gpu_poison import NOT_REACHED             # imports without a device: only its tests need one
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE, ARG = 1, 2
 PARENT_SITES = 119                                   # len(_poison.site_spans()) on the commit this route was added to
 
@@ -33,9 +32,7 @@ def L():
 # ---------------------------------------------------------------------------------------------- the binding and the C refusals
 def test_the_symbol_is_bound_with_the_headers_argument_count(L):
     from vitamd import lib
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
-    declared = {n: (0 if a.strip() in ("", "void") else a.count(",") + 1)
-                for n, a in re.findall(r"\bint\s+(vitamd_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.S)}
+    declared, _ = _abi.declared()
     name = "vitamd_frames_prep_resize_mix"
     assert declared[name] == 18 == len(lib.SIGNATURES[name]) == declared["vitamd_frames_prep_resize"] + 2
     fn = getattr(L, name)

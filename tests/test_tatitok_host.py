@@ -2,15 +2,14 @@
 own fp32 evaluation at the shapes the GPU test uses; the new entry points are bound; train_tatitok.TiTok has the reference's keys and
 parameter groups; shape and argument errors come before any device is looked at."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+import _abi
 import _tatitok_ref as T
 import _tokenizer_ref as R
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
 NEW_SYMBOLS = {"vitamd_vq_quantize_unit_fwd": 12, "vitamd_vq_quantize_unit_bwd": 12, "vitamd_conv_recon_mse_fwd": 13,
@@ -81,12 +80,11 @@ def test_unit_quantiser_checker_passes_torch_fp32_and_fails_every_planted_mistak
 def test_new_symbols_are_bound_and_the_abi_version_stays():
     from vitamd import lib
     L = lib.load()
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
+    header = _abi.header()
     for name, nargs in NEW_SYMBOLS.items():
         fn = getattr(L, name)
         assert len(lib.SIGNATURES[name]) == nargs and fn.argtypes == lib.SIGNATURES[name] and fn.restype is ctypes.c_int
-        decl = re.search(r"\bint %s\s*\(([^;]*)\);" % name, header)
-        assert decl and len(decl.group(1).split(",")) == nargs, name
+        assert _abi.declared()[1][name] == "int" and len(_abi.declaration(name).split(",")) == nargs, name
     assert L.vitamd_conv_recon_mse_ws_bytes.restype is ctypes.c_long and "long vitamd_conv_recon_mse_ws_bytes(" in header
     assert L.vitamd_abi_version() == 9 == lib.ABI_VERSION
     # one 32 x 32 tile per workgroup: 256 px = 64 tiles an image; one loss partial forward, 84 gradient partials backward

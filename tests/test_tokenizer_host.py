@@ -3,11 +3,11 @@ tests/_tokenizer_ref.py against torch autograd in float64, the bounds of the GPU
 refusals, the new model surface.  No GPU is needed."""
 import ctypes
 import inspect
-import os
 
 import pytest
 import torch
 
+import _abi
 import _tokenizer_ref as R
 
 F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
@@ -102,10 +102,9 @@ NEW_SYMBOLS = {"vitamd_vq_quantize_fwd": 12, "vitamd_vq_quantize_bwd": 12, "vita
 
 
 def test_symbols_are_exported_and_typed():
-    from conftest import ROOT
     from vitamd import lib
     L = lib.load()
-    header = open(os.path.join(ROOT, "include", "vitamd.h")).read()
+    header = _abi.header()
     for name, nargs in NEW_SYMBOLS.items():
         fn = getattr(L, name)
         assert len(lib.SIGNATURES[name]) == nargs and fn.argtypes == lib.SIGNATURES[name] and fn.restype is ctypes.c_int

@@ -29,7 +29,7 @@ namespace {
 
 constexpr int DH = 64;
 constexpr int MAX_N = 512;        // single-chunk kernels; longer sequences (up to MAX_N_LONG) take the *_long_kernel forms
-constexpr int MAX_N_LONG = 16384;
+constexpr int MAX_N_LONG = VITAMD_DECODE_MAX_LEN;
 constexpr float NEG_BIG = -1.0e30f;
 
 typedef LDS_AS bf16x4* lds_bf16x4_ptr;

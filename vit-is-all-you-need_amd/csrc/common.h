@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/vitamd.h"   // the C ABI: VITAMD_OK / VITAMD_ERR_*, the epilogue and form codes, the limits
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;   // one MFMA A/B fragment (4 VGPRs)
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -12,12 +13,6 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
-
-#define VITAMD_OK 0
-#define VITAMD_ERR_SHAPE 1
-#define VITAMD_ERR_ARG 2
-#define VITAMD_ERR_LAUNCH 3
-#define VITAMD_ERR_INIT 4
 
 // fp32 -> bf16 round-to-nearest-even (plain cast: hipcc emits v_cvt_pk_bf16_f32, NaN-safe)
 __device__ __forceinline__ __bf16 f2bf(float x) { return (__bf16)x; }

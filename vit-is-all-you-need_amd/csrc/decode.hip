@@ -11,7 +11,7 @@
 namespace {
 
 constexpr int DH = 64;              // head dim (the library's only one)
-constexpr int MAX_LEN = 16384;      // = attention.hip MAX_N_LONG
+constexpr int MAX_LEN = VITAMD_DECODE_MAX_LEN;
 constexpr float NEG_BIG = -1e30f;   // running max before the first key (finite: exp2 of a difference of two of these is 1, never NaN)
 
 int dec_cus() {

@@ -15,7 +15,7 @@ namespace {
 
 constexpr int ERASE_GRID_CAP = 2048;                 // workgroups per launch (8 per CU); further (sample, box, strip) units by the stride loop
 constexpr int ERASE_STRIPS = 32;                     // workgroups that share one box: a lane of the recipe's largest box (a third of 224 x 224) has 2 groups
-constexpr int ERASE_MAX_K = 8;
+constexpr int ERASE_MAX_K = VITAMD_ERASE_MAX_BOXES;
 
 struct EraseBox { int mode, yl, yh, xl, xh; };
 

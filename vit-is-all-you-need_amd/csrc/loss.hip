@@ -21,7 +21,7 @@ namespace {
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 constexpr float NEG_BIG = -3.0e38f;   // running maximum before the first element: finite, so that exp2 of (NEG_BIG - NEG_BIG) is 1 and never NaN
-constexpr int CE_MAX_V = 65536;
+constexpr int CE_MAX_V = VITAMD_CE_MAX_V;
 constexpr int CE_WIDE_V = 4096;       // longer rows: the four waves of a workgroup share one row
 constexpr int CE_GRID_CAP = 2048;     // workgroups per launch; further rows are reached by the row-stride loop
 constexpr int EMB_GRID_CAP = 8192;

@@ -61,9 +61,8 @@ __global__ __launch_bounds__(256) void cast_transpose_kernel(const float* __rest
 }
 
 // Batched form: one launch casts (and transposes) EVERY weight of the model.  desc[i] =
-// {w, wb, wbt, N, K, first_tile}; blockIdx.x walks the concatenated 64x64 tile lists.
-struct CastDesc { const float* w; __bf16* wb; __bf16* wbt; int N, K, first_tile, tiles_k; };
-__global__ __launch_bounds__(256) void cast_transpose_batched_kernel(const CastDesc* __restrict__ desc, int n) {
+// include/vitamd.h vitamd_cast_desc; blockIdx.x walks the concatenated 64x64 tile lists.
+__global__ __launch_bounds__(256) void cast_transpose_batched_kernel(const vitamd_cast_desc* __restrict__ desc, int n) {
   __shared__ float tile[64][65];
   __shared__ int which;
   if (threadIdx.x == 0) {
@@ -72,7 +71,9 @@ __global__ __launch_bounds__(256) void cast_transpose_batched_kernel(const CastD
     which = lo;
   }
   __syncthreads();
-  const CastDesc d = desc[which];
+  const vitamd_cast_desc d = desc[which];
+  __bf16* const wb = (__bf16*)d.wb;      // the header types the two bf16 outputs void*
+  __bf16* const wbt = (__bf16*)d.wbt;
   const int t = blockIdx.x - d.first_tile;
   const int n0 = (t / d.tiles_k) * 64, k0 = (t % d.tiles_k) * 64;
   if ((d.K & 3) == 0 && (d.N & 3) == 0) {
@@ -84,19 +85,19 @@ __global__ __launch_bounds__(256) void cast_transpose_batched_kernel(const CastD
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (nn < d.N && k < d.K) {        // K % 4 == 0: the four columns are in range together
         v = *(const f32x4*)(d.w + (size_t)nn * d.K + k);
-        if (d.wb) *(u32x2*)(d.wb + (size_t)nn * d.K + k) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+        if (wb) *(u32x2*)(wb + (size_t)nn * d.K + k) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) tile[r][c + j] = v[j];
     }
     __syncthreads();
-    if (d.wbt) {
+    if (wbt) {
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int idx = it * 256 + threadIdx.x, kl = idx >> 4, c = (idx & 15) * 4;
         const int k = k0 + kl, nn = n0 + c;
         if (k < d.K && nn < d.N)
-          *(u32x2*)(d.wbt + (size_t)k * d.N + nn) = u32x2{pack_bf16x2(tile[c][kl], tile[c + 1][kl]), pack_bf16x2(tile[c + 2][kl], tile[c + 3][kl])};
+          *(u32x2*)(wbt + (size_t)k * d.N + nn) = u32x2{pack_bf16x2(tile[c][kl], tile[c + 1][kl]), pack_bf16x2(tile[c + 2][kl], tile[c + 3][kl])};
       }
     }
     return;
@@ -107,15 +108,15 @@ __global__ __launch_bounds__(256) void cast_transpose_batched_kernel(const CastD
     float v = 0.f;
     if (nn < d.N && k < d.K) {
       v = d.w[(size_t)nn * d.K + k];
-      if (d.wb) d.wb[(size_t)nn * d.K + k] = f2bf(v);
+      if (wb) wb[(size_t)nn * d.K + k] = f2bf(v);
     }
     tile[r][tx] = v;
   }
   __syncthreads();
-  if (d.wbt) {
+  if (wbt) {
     for (int r = ty; r < 64; r += 4) {
       const int k = k0 + r, nn = n0 + tx;
-      if (k < d.K && nn < d.N) d.wbt[(size_t)k * d.N + nn] = f2bf(tile[tx][r]);
+      if (k < d.K && nn < d.N) wbt[(size_t)k * d.N + nn] = f2bf(tile[tx][r]);
     }
   }
 }
@@ -432,7 +433,7 @@ extern "C" int vitamd_cast_transpose_weight(const float* w, void* wb, void* wbt,
 extern "C" int vitamd_cast_transpose_batched(const void* desc_dev, int n, int total_tiles, void* stream) {
   if (n <= 0 || total_tiles <= 0) return VITAMD_ERR_SHAPE;
   if (!desc_dev) return VITAMD_ERR_ARG;
-  hipLaunchKernelGGL(cast_transpose_batched_kernel, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc_dev, n);
+  hipLaunchKernelGGL(cast_transpose_batched_kernel, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const vitamd_cast_desc*)desc_dev, n);
   return hipGetLastError() == hipSuccess ? VITAMD_OK : VITAMD_ERR_LAUNCH;
 }
 

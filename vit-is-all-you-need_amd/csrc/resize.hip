@@ -28,7 +28,7 @@
 namespace {
 
 constexpr int RESIZE_GRID_CAP = 1024;                // workgroups per launch (4 per CU: what the LDS admits); a stride loop beyond
-constexpr int MAX_SIZE = 8192;                       // of Hs, Ws, H, W and the virtual sizes: u * h and (2j+1) * Hv stay below 2^31
+constexpr int MAX_SIZE = VITAMD_FRAMES_MAX_SIZE;                       // of Hs, Ws, H, W and the virtual sizes: u * h and (2j+1) * Hv stay below 2^31
 constexpr int MAX_TAPS = 16;                         // per axis: 2 * max(h / Hv, 1) at the 8x down-scaling cap
 constexpr int TH = 32, TW = 32;                      // the output tile of a workgroup
 constexpr int STRIP_ROWS = 80;                       // source rows of one horizontal pass

@@ -17,7 +17,7 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int MAX_V = 65536;
+constexpr int MAX_V = VITAMD_SAMPLE_MAX_V;
 constexpr int LDS_ROW_MAX_V = 32768;       // the row stays in LDS up to here (128 KiB); longer rows are re-read through L2
 constexpr int REP = 8;                     // copies of each histogram bin, picked by lane: logits crowd into few exponent bins on the first pass
 constexpr unsigned KEY_NINF = 0x007fffffu; // key(-inf): everything finite is above it

@@ -21,7 +21,7 @@ namespace {
 
 constexpr float VQ_EPS = 1e-12f;              // F.normalize
 constexpr float VQ_RNORM_CLAMPED = 1.0f / VQ_EPS;   // rnorm of a row whose norm was below eps: the backward's mark for dx = du / eps
-constexpr int VQ_MAX_D = 64;
+constexpr int VQ_MAX_D = VITAMD_VQ_MAX_D;
 
 // ------------------------------------------------------------------------------------------------ quantiser forward
 // thread i: unit row i of the codebook (i < K) and the empty slot of row i of the packed index buffer (i < M)

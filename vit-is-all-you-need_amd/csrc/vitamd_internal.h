@@ -1,15 +1,17 @@
 // Internal (C++) argument blocks shared between the kernel files and capi.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/vitamd.h"
 
-enum GemmEpilogue {
-  EPI_BIAS_BF16 = 0,  // out bf16 = bf16(acc + bias)            (bias may be null)
-  EPI_GELU = 1,       // out bf16 = pre = bf16(acc + bias); out2 bf16 = gelu(pre)
-  EPI_RESID_F32 = 2,  // out f32  = aux_f32 + bf16(acc + bias)   (residual stream stays fp32)
-  EPI_DGELU = 3,      // out bf16 = bf16(bf16(acc) * gelu'(aux_bf16)); colsum[n] += column sums of out
-  EPI_PATCH_F32 = 4,  // out f32[b*seq + extra + p] = bf16(acc + bias) + aux_f32[p]  (patch embed + pos_emb)
-  EPI_F32 = 5,        // out f32 = acc
-  EPI_DGELU_NOCS = 6, // template argument of the seam / loader kernels only (never GemmNtArgs::epi): EPI_DGELU launched with colsum == null - the
+enum GemmEpilogue {              // the first six are the ABI's numbers (include/vitamd.h VITAMD_EPI_*)
+  EPI_BIAS_BF16 = VITAMD_EPI_BIAS_BF16,  // out bf16 = bf16(acc + bias)            (bias may be null)
+  EPI_GELU = VITAMD_EPI_GELU,            // out bf16 = pre = bf16(acc + bias); out2 bf16 = gelu(pre)
+  EPI_RESID_F32 = VITAMD_EPI_RESID_F32,  // out f32  = aux_f32 + bf16(acc + bias)   (residual stream stays fp32)
+  EPI_DGELU = VITAMD_EPI_DGELU,          // out bf16 = bf16(bf16(acc) * gelu'(aux_bf16)); colsum[n] += column sums of out
+  EPI_PATCH_F32 = VITAMD_EPI_PATCH_F32,  // out f32[b*seq + extra + p] = bf16(acc + bias) + aux_f32[p]  (patch embed + pos_emb)
+  EPI_F32 = VITAMD_EPI_F32,              // out f32 = acc
+  EPI_DGELU_NOCS = 6, // NOT an ABI code (6 is VITAMD_EPI_GELU_DG there, which capi.hip maps to EPI_GELU + gelu_dg: the two never meet).  A
+                      // template argument of the seam / loader kernels only (never GemmNtArgs::epi): EPI_DGELU launched with colsum == null - the
                       // column sums, their butterfly and the atomic compiled out (the bias gradient then comes from the weight-gradient GEMM)
 };
 

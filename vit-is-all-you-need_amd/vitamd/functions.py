@@ -92,8 +92,8 @@ class WeightCache:
                 for w in weights:
                     self.get(w, want_t)
                 return
-            dt = np.dtype([("w", "<u8"), ("wb", "<u8"), ("wbt", "<u8"), ("N", "<i4"), ("K", "<i4"), ("first", "<i4"), ("tk", "<i4")])
-            tab = np.zeros(len(weights), dtype=dt)
+            from .optim import CAST_DTYPE          # struct vitamd_cast_desc of include/vitamd.h
+            tab = np.zeros(len(weights), dtype=CAST_DTYPE)
             first = 0
             for i, (w, e) in enumerate(zip(weights, ents)):
                 N, K = e["wb"].shape

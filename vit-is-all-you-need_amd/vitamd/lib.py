@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -14,121 +15,53 @@ LIB_PATH = os.path.join(_HERE, "libvitamd.so")
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 ABI_VERSION = 9
 
-_c = ctypes
-_P, _I, _F, _L, _U64, _D, _LL = _c.c_void_p, _c.c_int, _c.c_float, _c.c_long, _c.c_ulonglong, _c.c_double, _c.c_longlong
-
-# name -> argtypes ; every function returns int (VITAMD_OK == 0)
-SIGNATURES = {
-    "vitamd_abi_version": [],
-    "vitamd_init": [_I, _P],
-    "vitamd_gemm_nt_plan": [_I, _I, _I, _I, _I, _I],
-    "vitamd_gemm_nt_bf16": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "vitamd_gemm_nt_bf16_ws": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P],
-    "vitamd_gemm_nt_ws_bytes": [_I, _I, _I, _I, _I, _I, _I],
-    "vitamd_gemm_nt_ws_plan": [_I, _I, _I, _I, _I, _I, _I],
-    "vitamd_gemm_tn_bf16": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "vitamd_gemm_tn_bf16_ws": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P],
-    "vitamd_gemm_tn_bf16_ws_colsum": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P],
-    "vitamd_gemm_tn_ws_bytes": [_I, _I, _I, _I],
-    "vitamd_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "vitamd_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "vitamd_layernorm_affine_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "vitamd_layernorm_affine_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "vitamd_layernorm_affine_fwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "vitamd_layernorm_affine_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "vitamd_attention_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P],
-    "vitamd_attention_fwd_resid": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P],
-    "vitamd_attention_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P],
-    "vitamd_layernorm_bwd_dropout": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _U64, _P],
-    "vitamd_layernorm_bwd_xhat": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _U64, _P],
-    "vitamd_linear_dropout_resid_bf16": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _I, _P],
-    "vitamd_cast_f32_bf16_dropout": [_P, _P, _L, _F, _U64, _P],
-    "vitamd_cast_f32_bf16": [_P, _P, _L, _P],
-    "vitamd_dropout_bf16": [_P, _P, _L, _L, _F, _U64, _P],
-    "vitamd_dropout_f32": [_P, _P, _L, _L, _F, _U64, _P],
-    "vitamd_cast_transpose_weight": [_P, _P, _P, _I, _I, _P],
-    "vitamd_cast_transpose_batched": [_P, _I, _I, _P],
-    "vitamd_im2col_bf16": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_colsum_bf16": [_P, _P, _I, _I, _I, _P],
-    "vitamd_embed_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vitamd_vq_nearest": [_P, _P, _P, _I, _I, _I, _P],
-    "vitamd_conv3x3_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_conv3x3_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_adamw_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P],
-    "vitamd_adamw_step_d": [_P, _P, _P, _P, _L, _F, _D, _D, _F, _F, _I, _P],
-    "vitamd_mt_row_bytes": [],
-    "vitamd_mt_chunk_elems": [],
-    "vitamd_mt_grid_cap": [],
-    "vitamd_mt_sumsq": [_P, _P, _I, _I, _P, _P, _F, _P],
-    "vitamd_mt_adamw": [_P, _P, _I, _I, _P, _P],
-    "vitamd_mt_scale": [_P, _P, _I, _I, _P, _P],
-    "vitamd_sched_row_bytes": [],
-    "vitamd_sched_advance": [_P, _P, _I, _P],
-    "vitamd_kv_append": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_decode_attention_ws_bytes": [_I, _I, _I],
-    "vitamd_decode_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
-    "vitamd_gemm_skinny_ws_bytes": [_I, _I, _I],
-    "vitamd_gemm_skinny_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
-    "vitamd_gemm_skinny_qkv_append": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
-    "vitamd_decode_embed": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vitamd_sample_logits": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _U64, _P],
-    "vitamd_layernorm_fwd_keep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "vitamd_layernorm_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P],
-    "vitamd_layernorm_fwd_add2": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "vitamd_layernorm_fwd_keep_add2": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "vitamd_attention_keep_forms": [_I, _I],
-    "vitamd_attention_fwd_keep": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_attention_bwd_keep": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_attention_form": [_I, _I, _F, _I, _I, _I],
-    "vitamd_cross_entropy_grid_rows": [_I],
-    "vitamd_cross_entropy_fwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _LL, _P],
-    "vitamd_cross_entropy_bwd": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _P],
-    "vitamd_soft_cross_entropy_fwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
-    "vitamd_soft_cross_entropy_bwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_classify_metrics": [_P, _I, _P, _P, _P, _P, _P, _L, _I, _L, _I, _LL, _P],
-    "vitamd_embed_tokens_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_embed_tokens_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vitamd_assemble_tokens_grid_cap": [],
-    "vitamd_assemble_tokens_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "vitamd_assemble_tokens_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "vitamd_vq_quantize_ws_bytes": [_I, _I, _I],
-    "vitamd_vq_quantize_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "vitamd_vq_quantize_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "vitamd_recon_mse_ws_bytes": [_I, _I, _I, _I, _I],
-    "vitamd_recon_mse_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_recon_mse_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "vitamd_vq_quantize_unit_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "vitamd_vq_quantize_unit_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "vitamd_conv_recon_mse_ws_bytes": [_I, _I, _I, _I, _I],
-    "vitamd_conv_recon_mse_fwd": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vitamd_conv_recon_mse_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_dwconv7_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vitamd_dwconv7_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vitamd_resize_norm_fwd": [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_resize_norm_bwd": [_P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vitamd_frames_prep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "vitamd_frames_prep_mix": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "vitamd_frames_prep_resize": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "vitamd_frames_prep_resize_mix": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "vitamd_frames_prep_resize_grid_cap": [],
-    "vitamd_frames_prep_grid_cap": [],
-    "vitamd_crop_flip_draw": [_P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P],
-    "vitamd_frames_to_u8": [_P, _P, _I, _I, _I, _I, _P],
-    "vitamd_frames_erase": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _U64, _U64, _P],
-    "vitamd_frames_erase_grid_cap": [],
-    "vitamd_tanh_bf16": [_P, _P, _L, _P],
-    "vitamd_tanh_bwd_bf16": [_P, _P, _P, _L, _P],
-    "vitamd_recon_l1_fwd": [_P, _I, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
-    "vitamd_recon_l1_bwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-}
-
-ERRORS = {1: "unsupported shape", 2: "bad argument", 3: "HIP launch failure", 4: "vitamd_init has not run for this device"}
-
-_lib = None
-
 
 class VitamdError(RuntimeError):
     pass
+
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "vitamd.h")
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+_TYPE_WORDS = {"void", "char", "short", "int", "long", "float", "double", "signed", "unsigned", "const", "struct"}
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(VITAMD_\w+)[ \t]+(0[xX][0-9a-fA-F]+|\d+)[ \t]*$", re.M)
+_DECL = re.compile(r"(?:^|(?<=[;{}]))([^;{}()]*?)\b(vitamd_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def parse_header(text):
+    """The C ABI as include/vitamd.h declares it: ({name: (return type, [parameter type, ...])}, {VITAMD_* macro: int}).  Types are canonical C
+    spellings (`const float*`, `unsigned long long`); a pointer to anything, or one of _SCALARS.  Anything else raises, naming the declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {name: int(value, 0) for name, value in _DEFINE.findall(text)}        # object-like macros with an integer body only
+    protos = {}
+    for ret, name, params in _DECL.findall(re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)):
+        ret = " ".join(ret.split())
+        if ret not in ("int", "long"):
+            raise VitamdError(f"{name}: return type `{ret}` is not int or long")
+        types = []
+        for param in ([] if params.strip() in ("", "void") else params.split(",")):
+            words = [w for w in param.replace("*", " * ").split() if w != "__restrict__"]
+            if len(words) < 2 or words[-1] in _TYPE_WORDS or not re.fullmatch(r"[A-Za-z_]\w*", words[-1]):
+                raise VitamdError(f"{name}: parameter `{' '.join(param.split())}` has no name")
+            ctype = " ".join(words[:-1]).replace(" *", "*")
+            if not ctype.endswith("*") and ctype not in _SCALARS:
+                raise VitamdError(f"{name}: no ctypes type for parameter `{' '.join(param.split())}`")
+            types.append(ctype)
+        protos[name] = (ret, types)
+    return protos, constants
+
+
+try:
+    with open(HEADER) as _fh:
+        PROTOTYPES, CONSTANTS = parse_header(_fh.read())
+except OSError as _e:
+    raise VitamdError(f"{HEADER} is missing: the binding is derived from it") from _e
+SIGNATURES = {name: [ctypes.c_void_p if t.endswith("*") else _SCALARS[t] for t in types] for name, (_, types) in PROTOTYPES.items()}      # name -> argtypes
+RESTYPES = {name: _SCALARS[ret] for name, (ret, _) in PROTOTYPES.items()}
+ERRORS = {CONSTANTS["VITAMD_ERR_SHAPE"]: "unsupported shape", CONSTANTS["VITAMD_ERR_ARG"]: "bad argument",
+          CONSTANTS["VITAMD_ERR_LAUNCH"]: "HIP launch failure", CONSTANTS["VITAMD_ERR_INIT"]: "vitamd_init has not run for this device"}
+
+_lib = None
 
 
 def build(verbose: bool = False) -> str:
@@ -181,7 +114,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_long if name.endswith("_bytes") else ctypes.c_int
+        fn.restype = RESTYPES[name]
     if lib.vitamd_abi_version() != ABI_VERSION:
         raise VitamdError("libvitamd.so ABI version mismatch; rebuild")
     _lib = lib

@@ -8,8 +8,8 @@ from __future__ import annotations
 import torch
 
 from . import lib as _lib
-
-EPI_BIAS_BF16, EPI_GELU, EPI_RESID_F32, EPI_DGELU, EPI_PATCH_F32, EPI_F32, EPI_GELU_DG, EPI_DMUL = range(8)
+from .lib import CONSTANTS as _H      # the VITAMD_* macros of include/vitamd.h: every code and limit below is read from there, none is restated
+EPI_BIAS_BF16, EPI_GELU, EPI_RESID_F32, EPI_DGELU, EPI_PATCH_F32, EPI_F32, EPI_GELU_DG, EPI_DMUL = (_H["VITAMD_EPI_" + _n] for _n in "BIAS_BF16 GELU RESID_F32 DGELU PATCH_F32 F32 GELU_DG DMUL".split())
 # Large NT GEMMs are launched persistent by default (one workgroup per CU: -0.3 ms/step inside the training step and the reason the
 # weight-gradient stream can use the whole chip).  A persistent workgroup whose CU is held by another
 # long-running kernel starts late with its whole tile list still to do, so the form is sensitive to resident foreign kernels
@@ -26,7 +26,7 @@ NT_PERSISTENT = _os.environ.get("VITAMD_NT_PERSISTENT", "1") != "0"
 _seam_env = _os.environ.get("VITAMD_NT_SEAM", "auto")
 NT_SEAM = {"1": True, "0": False}.get(_seam_env)      # process-wide override (None = per device, by probe)
 SEAM_PROBE = {}          # device index -> {"seam_us", "plain_us", "enabled"}: the source of truth for the per-device decision
-NT_FORM_SEAM, NT_FORM_LOADER = 4, 5         # include/vitamd.h VITAMD_NT_FORM_* (vitamd_gemm_nt_plan): the two forms whose epilogue is a burst of asm buffer stores
+NT_FORM_SEAM, NT_FORM_LOADER = _H["VITAMD_NT_FORM_SEAM"], _H["VITAMD_NT_FORM_LOADER"]      # (vitamd_gemm_nt_plan): the two forms whose epilogue is a burst of asm buffer stores
 _RAW_AUTO = -1
 LN_EPS = 1e-5
 BF16, F32 = torch.bfloat16, torch.float32
@@ -170,7 +170,7 @@ def _workspace(device, nbytes):
 NT_SPLITS = 0             # split-K of the NT GEMMs that take the 128x128 kernel on fewer tiles than the device has CUs (the kept-row layer, the classifier
                           # head: include/vitamd.h vitamd_gemm_nt_bf16_ws): 0 = the library's rule, 1 = never (the unsplit kernel: tests, A/B), n = n splits.
                           # Read on every call.  Results differ from the unsplit kernel's by fp32 summation order only, and are the same in every run.
-NT_FORM_SPLITK = 6        # include/vitamd.h VITAMD_NT_FORM_SPLITK (vitamd_gemm_nt_ws_plan)
+NT_FORM_SPLITK = _H["VITAMD_NT_FORM_SPLITK"]        # (vitamd_gemm_nt_ws_plan)
 
 
 def _nt_launch(device, args):
@@ -191,7 +191,7 @@ def _nt_launch(device, args):
     return L.vitamd_gemm_nt_bf16_ws(*args, NT_SPLITS, _p(ws), ws.numel() * 4, _stream())
 
 
-TN_FORM_SHARED, TN_FORM_EXCLUSIVE = 0, 1      # include/vitamd.h VITAMD_TN_FORM_*
+TN_FORM_SHARED, TN_FORM_EXCLUSIVE = _H["VITAMD_TN_FORM_SHARED"], _H["VITAMD_TN_FORM_EXCLUSIVE"]
 
 
 def gemm_tn(l, r, out, splits=0, accumulate=True, atomic=False, form=TN_FORM_SHARED, colsum=None):
@@ -280,7 +280,7 @@ def layernorm_fwd_keep(x, addend, B, seq, keep, pending=None):
     return x_out, y, mean, rstd
 
 
-XHAT_WIDTHS = (256, 512, 768, 1024)       # the widths whose LayerNorm backward reads xhat from the forward's bf16 output (register-resident kernels)
+XHAT_WIDTHS = (256, 512, 768, 1024)       # (a set, so no header macro: csrc/layernorm.hip register_width() is its other copy) the widths whose LayerNorm backward reads xhat from the forward's bf16 output (register-resident kernels)
 
 
 def layernorm_bwd(dy, x, mean, rstd, g_res=None, want_bf16=False, colsum=None, dropout=(0.0, 0), xhat=None, keep=None):
@@ -371,7 +371,7 @@ def layernorm_affine_bwd_f32(dy, x, mean, rstd, gamma, dgamma, dbeta):
 
 
 # ------------------------------------------------------------------------------------------ attention
-ATTN_RESID_MAX_N = 256    # the fused residual add lives in the register-resident-softmax forward kernel
+ATTN_RESID_MAX_N = _H["VITAMD_ATTN_RESID_MAX_N"]    # the fused residual add lives in the register-resident-softmax forward kernel
 
 
 def attention_fwd(qkv, B, N, H, causal=False, dropout=(0.0, 0), resid=None):
@@ -412,8 +412,8 @@ def attention_bwd(qkv, o, lse, d_o, B, N, H, causal=False, dbias=None, dropout=(
 
 
 # include/vitamd.h VITAMD_ATTN_* (vitamd_attention_form): family | key tiles << 4 | query tiles << 8 | flags
-ATTN_FWD_SMALL, ATTN_FWD_SMALL8, ATTN_FWD_LOOP, ATTN_FWD_LONG, ATTN_BWD_PIPE, ATTN_BWD_LOOP, ATTN_BWD_LONG = 1, 2, 3, 4, 5, 6, 7
-ATTN_DROP, ATTN_CAUSAL, ATTN_RES, ATTN_KEEP = 0x1000, 0x2000, 0x4000, 0x8000
+ATTN_FWD_SMALL, ATTN_FWD_SMALL8, ATTN_FWD_LOOP, ATTN_FWD_LONG, ATTN_BWD_PIPE, ATTN_BWD_LOOP, ATTN_BWD_LONG = (_H["VITAMD_ATTN_" + _n] for _n in "FWD_SMALL FWD_SMALL8 FWD_LOOP FWD_LONG BWD_PIPE BWD_LOOP BWD_LONG".split())
+ATTN_DROP, ATTN_CAUSAL, ATTN_RES, ATTN_KEEP = (_H["VITAMD_ATTN_" + _n] for _n in "DROP CAUSAL RES KEEP".split())
 
 
 def attention_form(N, causal=False, dropout_p=0.0, resid=False, nq=0, backward=False):
@@ -432,7 +432,7 @@ def attention_form_fields(code):
     return code & 0xf, code >> 4 & 0xf, code >> 8 & 0xf, code & 0xf000
 
 
-KEEP_FWD, KEEP_BWD = 1, 2          # include/vitamd.h vitamd_attention_keep_forms
+KEEP_FWD, KEEP_BWD = _H["VITAMD_ATTN_KEEP_FWD"], _H["VITAMD_ATTN_KEEP_BWD"]          # the mask bits of vitamd_attention_keep_forms
 
 
 def attention_keep_forms(N, nq):
@@ -594,9 +594,9 @@ def conv3x3_bwd(x, w, dy, need_dx=True, need_dw=True, has_bias=True):
 
 
 # ------------------------------------------------------------------------------------------ KV-cached decoding
-SKINNY_MAX_M = 64         # include/vitamd.h vitamd_gemm_skinny_bf16
+SKINNY_MAX_M = _H["VITAMD_SKINNY_MAX_M"]         # vitamd_gemm_skinny_bf16
 SKINNY_EPIS = (EPI_BIAS_BF16, EPI_GELU, EPI_RESID_F32, EPI_F32)
-DECODE_MAX_LEN = 16384    # cache capacity limit (attention.hip MAX_N_LONG)
+DECODE_MAX_LEN = _H["VITAMD_DECODE_MAX_LEN"]    # cache capacity limit
 
 
 def _need_len(length):
@@ -736,7 +736,7 @@ def decode_embed(tok_table, pos_table, tokens, length, out=None):
 
 
 # ------------------------------------------------------------------------------------------ sampled generation
-SAMPLE_MAX_V = 65536      # include/vitamd.h vitamd_sample_logits
+SAMPLE_MAX_V = _H["VITAMD_SAMPLE_MAX_V"]      # vitamd_sample_logits
 
 
 def check_sampling(temperature, top_k, top_p, V=None):
@@ -784,7 +784,7 @@ def sample_logits(logits, temperature=1.0, top_k=0, top_p=1.0, *, u=None, seed=0
 
 
 # ------------------------------------------------------------------------------------------ training the causal stack
-CE_MAX_V = 65536          # include/vitamd.h vitamd_cross_entropy_fwd
+CE_MAX_V = _H["VITAMD_CE_MAX_V"]          # vitamd_cross_entropy_fwd
 
 
 def cross_entropy_grid_rows(V):
@@ -1000,7 +1000,7 @@ def assemble_tokens_bwd(g, dprefix, dpos, *, ids=None, dtok=None):
 
 
 # ------------------------------------------------------------------------------------------ training the image tokenizers
-VQ_MAX_D = 64             # include/vitamd.h vitamd_vq_quantize_fwd: wider codes stay on vq_nearest and the torch expressions
+VQ_MAX_D = _H["VITAMD_VQ_MAX_D"]             # vitamd_vq_quantize_fwd: wider codes stay on vq_nearest and the torch expressions
 
 
 def _need_vq(x, codebook, what):
@@ -1244,7 +1244,7 @@ def dwconv7_bwd(dy, w, add=None):
     return dx
 
 
-RESIZE_ROW_LD = 64        # include/vitamd.h vitamd_resize_norm_fwd: 3 * 4 * 4 = 48 patch values, zero-padded to the GEMM's K % 64 == 0
+RESIZE_ROW_LD = _H["VITAMD_RESIZE_ROW_LD"]        # vitamd_resize_norm_fwd: 3 * 4 * 4 = 48 patch values, zero-padded to the GEMM's K % 64 == 0
 
 
 def _need_band(table, n_index, n_other, name):
@@ -1303,7 +1303,7 @@ def frames_prep_resize_grid_cap():
     return int(_L().vitamd_frames_prep_resize_grid_cap())
 
 
-FRAMES_MAX_SIZE = 8192      # of Hs, Ws, H, W where the kernel resizes (include/vitamd.h vitamd_frames_prep_resize)
+FRAMES_MAX_SIZE = _H["VITAMD_FRAMES_MAX_SIZE"]      # of Hs, Ws, H, W where the kernel resizes (vitamd_frames_prep_resize)
 
 
 def check_frames(src_shape, out_hw, patch=None, B=None, has_index=False, resize=False):
@@ -1505,7 +1505,7 @@ def recon_l1_bwd(tokens, images, grid, patch, g_loss=None, g_recon=None, out=Non
 
 
 # ------------------------------------------------------------------------------------------ Random Erasing on the finished batch
-ERASE_MAX_BOXES = 8         # include/vitamd.h vitamd_frames_erase: K, the boxes one sample's record holds
+ERASE_MAX_BOXES = _H["VITAMD_ERASE_MAX_BOXES"]         # vitamd_frames_erase: K, the boxes one sample's record holds
 
 
 def frames_erase_grid_cap():

@@ -22,13 +22,17 @@ import torch
 
 from . import lib as _lib
 
-# struct vitamd_mt_row of include/vitamd.h
+# The record layouts of include/vitamd.h, hand-written because the code below indexes them by field name; tests/test_abi_parser_host.py has the
+# compiler compare every offset and size with the header's structs.
+# struct vitamd_mt_row
 ROW_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("first_chunk", "<i4"), ("lr", "<f4"),
                       ("weight_decay", "<f4"), ("beta1", "<f4"), ("one_minus_beta1", "<f4"), ("beta2", "<f4"), ("one_minus_beta2", "<f4"),
                       ("eps", "<f4"), ("inv_bc1", "<f4"), ("inv_sqrt_bc2", "<f4")])
-# struct vitamd_sched_row of include/vitamd.h
+# struct vitamd_sched_row
 SCHED_DTYPE = np.dtype([("step", "<i8"), ("sched_t", "<i8"), ("base_lr", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"), ("min_ratio", "<f8"),
                         ("warmup_steps", "<i8"), ("train_steps", "<i8")])
+# struct vitamd_cast_desc (functions.WeightCache.prepare fills it)
+CAST_DTYPE = np.dtype([("w", "<u8"), ("wb", "<u8"), ("wbt", "<u8"), ("N", "<i4"), ("K", "<i4"), ("first_tile", "<i4"), ("tiles_k", "<i4")])
 _HYPER = ("lr", "weight_decay", "beta1", "one_minus_beta1", "beta2", "one_minus_beta2", "eps", "inv_bc1", "inv_sqrt_bc2")
 
 
