@@ -166,6 +166,34 @@ def train_step(model, ids, optim, lr_sched=None):
     return loss.detach()
 
 
+def evaluate(model, batches, topk=5, metrics=None, codes=None):
+    """The validation half of the loop for the model without pixels: eval mode under torch.no_grad() over `batches` of VQ code ids
+    int64 [b, s]; the decoded logits of model(ids) against the ids go to a vitamd.metrics.ClassifyMetrics (loss, top-1, top-k), the
+    latent ids to a vitamd.metrics.CodebookMetrics.  No host read before the two final results, which are merged ("count", "perplexity":
+    the positions scored and exp(loss); "codes", "code_perplexity": the latent ids counted and the perplexity of their histogram).  model.training is put back, also when a batch raises."""
+    from vitamd.metrics import ClassifyMetrics, CodebookMetrics
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for ids in batches:
+                if metrics is None:
+                    metrics = ClassifyMetrics(topk=topk, device=ids.device)
+                if codes is None:
+                    codes = CodebookMetrics(int(model.config.codebook_size), device=ids.device)
+                logits, latent_ids, _ = model(ids)
+                metrics.update(logits, ids)
+                codes.update(latent_ids)
+    finally:
+        model.train(was_training)
+    if metrics is None or codes is None:
+        raise ValueError("evaluate: no batches")
+    out = codes.result()
+    out["codes"], out["code_perplexity"] = out.pop("count"), out.pop("perplexity")      # the classifier's result has both names too
+    out.update(metrics.result())
+    return out
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="TiTok over VQ code ids, cross-entropy training on synthetic ids (MI355X-native path)")
     p.add_argument("--vq_codebook_size", type=int, default=16384)
@@ -185,6 +213,10 @@ def parse_args(argv=None):
     p.add_argument("--vq", type=str, default="none", choices=("none", "vitvqgan"),
                    help="none: seeded random ids; vitvqgan: the ids of seeded random images through a freshly initialised ViT-VQGAN "
                         "of this project (patch 16, vq_latent_tokens patches, vq_codebook_size codes)")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="evaluate every N training steps on seeded held-out random data (evaluate / vitamd.metrics: cross-entropy, top-1 and top-5 of the decoded logits, codebook usage of the latent ids "
+                        "from counters on the device, one host read per evaluation); 0 = never")
+    p.add_argument("--eval_batches", type=int, default=2, help="the batches of one evaluation (--eval_every)")
     return p.parse_args(argv)
 
 
@@ -204,6 +236,8 @@ def make_ids(args, dev):
 
 def main():
     args = parse_args()
+    if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
+        raise SystemExit("--eval_every needs N >= 0 and --eval_batches >= 1")
     dev = torch.device("cuda")
     cfg = TiTokConfig(args.vq_codebook_size, args.vq_latent_tokens, args.latent_tokens, args.codebook_size, args.latent_dim, args.transformer)
     ids = make_ids(args, dev)
@@ -211,6 +245,10 @@ def main():
     optim = make_optim(model, args)
     sched = get_lr_scheduler(optim, args.warmup_steps, args.train_steps, args.lr / 10)
     usage = torch.zeros([cfg.codebook_size], device=dev)
+    val = None
+    if args.eval_every > 0:
+        g = torch.Generator(device="cpu").manual_seed(1)
+        val = [torch.randint(0, args.vq_codebook_size, (args.bs, args.vq_latent_tokens), generator=g).to(dev) for _ in range(args.eval_batches)]
     for step in range(args.steps):
         t0 = time.time()
         loss = train_step(model, ids, optim, sched)
@@ -219,6 +257,10 @@ def main():
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} codebook_usage {usage.sum().item() / cfg.codebook_size:.3f} "
               f"{args.bs / (time.time() - t0):.1f} sequences/s")
+        if val is not None and (step + 1) % args.eval_every == 0:
+            r = evaluate(model, val)
+            print(f"step {step} val loss {r['loss']:.4f} top1 {r['top1']:.4f} top5 {r['topk']:.4f} codebook_usage {r['usage']:.3f} "
+                  f"code perplexity {r['code_perplexity']:.1f} over {r['count']} positions")
     print(f"reconstructed ids equal to the input: {(model.reconstruct(ids) == ids).float().mean().item():.3f}")
 
 

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from blocks import TiTokDecoder, TiTokEncoder, VectorQuantizer
+from train_titok import make_val_batches, report
 from utils import get_lr_scheduler
 from vitamd import ops, tokenizer
 from vitamd.data import Frames
@@ -160,6 +161,13 @@ def train_step(model, images, optim, lr_sched=None, perceptual=None, perceptual_
     return loss.detach()
 
 
+def evaluate(model, batches, recon=None, codes=None):
+    """The validation half of the loop: vitamd.metrics.evaluate_tokenizer on model(x) = (decoded, result_dict), ids = result_dict["min_encoding_indices"] ->
+    {"mse", "mae", "psnr", "ssim", "count", "usage", "used", "dead", "perplexity", "entropy", "codes", "bad"}, one host read at the end"""
+    from vitamd.metrics import evaluate_tokenizer
+    return evaluate_tokenizer(model, batches, recon=recon, codes=codes, patch=model.encoder.patch_size)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="1D TiTok (train_tatitok) training on synthetic images (MI355X-native path)")
     p.add_argument("--image_size", type=int, default=256)
@@ -180,11 +188,17 @@ def parse_args(argv=None):
     p.add_argument("--perceptual_weights", type=str, default=None,
                    help="path of a torchvision convnext_small state dict for the perceptual network; without it the network is untrained "
                         "(a throughput stand-in).  Nothing is ever downloaded")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="evaluate every N training steps on seeded held-out random data (evaluate / vitamd.metrics: MSE, MAE, PSNR, SSIM and codebook usage "
+                        "from counters on the device, one host read per evaluation); 0 = never")
+    p.add_argument("--eval_batches", type=int, default=2, help="the batches of one evaluation (--eval_every)")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
+        raise SystemExit("--eval_every needs N >= 0 and --eval_batches >= 1")
     dev = torch.device("cuda")
     cfg = TiTokConfig(args.image_size, args.patch_size, args.latent_tokens, args.codebook_size, args.latent_dim, args.transformer)
     model = TiTok(cfg).to(dev)
@@ -197,6 +211,7 @@ def main(argv=None):
     g = torch.Generator(device="cpu").manual_seed(0)
     images = torch.rand((args.bs, 3, args.image_size, args.image_size), generator=g).to(dev)
     usage = torch.zeros([cfg.codebook_size], device=dev)
+    val = make_val_batches(args, dev) if args.eval_every > 0 else None
     for step in range(args.train_steps):
         t0 = time.time()
         loss = train_step(model, images, optim, sched, perceptual=perceptual, perceptual_weight=args.perceptual_weight)
@@ -205,6 +220,8 @@ def main(argv=None):
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} codebook_usage {usage.sum().item() / cfg.codebook_size:.3f} "
               f"{args.bs / (time.time() - t0):.1f} images/s")
+        if val is not None and (step + 1) % args.eval_every == 0:
+            report(step, evaluate(model, val))
 
 
 if __name__ == "__main__":

@@ -170,6 +170,24 @@ def train_step(model, images, optim, lr_sched=None, perceptual=None, perceptual_
     return loss.detach()
 
 
+def evaluate(model, batches, recon=None, codes=None):
+    """The validation half of the loop: vitamd.metrics.evaluate_tokenizer on model(x) = (reconstruction, code ids, quantiser loss) ->
+    {"mse", "mae", "psnr", "ssim", "count", "usage", "used", "dead", "perplexity", "entropy", "codes", "bad"}, one host read at the end"""
+    from vitamd.metrics import evaluate_tokenizer
+    return evaluate_tokenizer(model, batches, recon=recon, codes=codes, patch=model.config.patch_size)
+
+
+def make_val_batches(args, dev):
+    """the args.eval_batches held-out batches of one evaluation (their own seed): fp32 images in [0, 1] on the device"""
+    g = torch.Generator(device="cpu").manual_seed(1)
+    return [torch.rand((args.bs, 3, args.image_size, args.image_size), generator=g).to(dev) for _ in range(args.eval_batches)]
+
+
+def report(step, r):
+    print(f"step {step} val mse {r['mse']:.5f} mae {r['mae']:.5f} psnr {r['psnr']:.2f} ssim {r['ssim']:.4f} codebook_usage {r['usage']:.3f} "
+          f"perplexity {r['perplexity']:.1f} over {r['count']} images")
+
+
 def add_common_args(p):
     p.add_argument("--image_size", type=int, default=128)
     p.add_argument("--patch_size", type=int, default=16)
@@ -193,6 +211,10 @@ def add_common_args(p):
     p.add_argument("--perceptual_weights", type=str, default=None,
                    help="path of a torchvision convnext_small state dict for the perceptual network; without it the network is untrained "
                         "(a throughput stand-in).  Nothing is ever downloaded")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="evaluate every N training steps on seeded held-out random data (evaluate / vitamd.metrics: MSE, MAE, PSNR, SSIM and codebook usage "
+                        "from counters on the device, one host read per evaluation); 0 = never")
+    p.add_argument("--eval_batches", type=int, default=2, help="the batches of one evaluation (--eval_every)")
     return p
 
 
@@ -240,6 +262,9 @@ def run(model, args, codebook_size):
         else:
             u8 = torch.randint(0, 256, (args.bs, args.image_size, args.image_size, 3), generator=g, dtype=torch.uint8)
             feed = DeviceLoader(((u8, None) for _ in range(args.train_steps)), dev, args.image_size, patch=args.patch_size, train=False)
+    if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
+        raise SystemExit("--eval_every needs N >= 0 and --eval_batches >= 1")
+    val = make_val_batches(args, dev) if args.eval_every > 0 else None
     for step in range(args.train_steps):
         t0 = time.time()
         if feed is not None:
@@ -250,6 +275,8 @@ def run(model, args, codebook_size):
         torch.cuda.synchronize()
         print(f"step {step} loss {loss.item():.4f} codebook_usage {usage.sum().item() / codebook_size:.3f} "
               f"{args.bs / (time.time() - t0):.1f} images/s")
+        if val is not None and (step + 1) % args.eval_every == 0:
+            report(step, evaluate(model, val))
 
 
 def main():

@@ -8,7 +8,7 @@ from dataclasses import dataclass
 import torch.nn as nn
 
 from train_titok import HipConv1x1, HipLinear, Quantizer, pixel_shuffle_tokens  # noqa: F401  (Quantizer is the same class)
-from train_titok import add_common_args, run, tokenizer_loss, train_step  # noqa: F401  (train_step is the same function)
+from train_titok import add_common_args, evaluate, run, tokenizer_loss, train_step  # noqa: F401  (train_step and evaluate are the same functions)
 from train_vit import ViT, ViTConfig
 
 

@@ -58,6 +58,16 @@ except OSError as _e:
     raise VitamdError(f"{HEADER} is missing: the binding is derived from it") from _e
 SIGNATURES = {name: [ctypes.c_void_p if t.endswith("*") else _SCALARS[t] for t in types] for name, (_, types) in PROTOTYPES.items()}      # name -> argtypes
 RESTYPES = {name: _SCALARS[ret] for name, (ret, _) in PROTOTYPES.items()}
+# include/vitamd_eval.h: the evaluation entry points added beside ABI 9 (the tables above stay those of vitamd.h alone); its limits join CONSTANTS
+EVAL_HEADER = os.path.join(os.path.dirname(HEADER), "vitamd_eval.h")
+try:
+    with open(EVAL_HEADER) as _fh:
+        EVAL_PROTOTYPES, _eval_constants = parse_header(_fh.read())
+except OSError as _e:
+    raise VitamdError(f"{EVAL_HEADER} is missing: the binding is derived from it") from _e
+CONSTANTS.update(_eval_constants)
+EVAL_SIGNATURES = {name: [ctypes.c_void_p if t.endswith("*") else _SCALARS[t] for t in types] for name, (_, types) in EVAL_PROTOTYPES.items()}
+EVAL_RESTYPES = {name: _SCALARS[ret] for name, (ret, _) in EVAL_PROTOTYPES.items()}
 ERRORS = {CONSTANTS["VITAMD_ERR_SHAPE"]: "unsupported shape", CONSTANTS["VITAMD_ERR_ARG"]: "bad argument",
           CONSTANTS["VITAMD_ERR_LAUNCH"]: "HIP launch failure", CONSTANTS["VITAMD_ERR_INIT"]: "vitamd_init has not run for this device"}
 
@@ -111,10 +121,11 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     check_single_hip_runtime()
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError here = header/library mismatch
-        fn.argtypes = argtypes
-        fn.restype = RESTYPES[name]
+    for signatures, restypes in ((SIGNATURES, RESTYPES), (EVAL_SIGNATURES, EVAL_RESTYPES)):
+        for name, argtypes in signatures.items():
+            fn = getattr(lib, name)  # AttributeError here = header/library mismatch
+            fn.argtypes = argtypes
+            fn.restype = restypes[name]
     if lib.vitamd_abi_version() != ABI_VERSION:
         raise VitamdError("libvitamd.so ABI version mismatch; rebuild")
     _lib = lib

@@ -1595,3 +1595,97 @@ def classify_metrics(logits, target, loss_sum, counts, topk=5, ignore_index=-100
         _lib.check(_L().vitamd_classify_metrics(_p(logits), is_bf16, _p(target), _p(loss_row), _p(rank), _p(loss_sum), _p(counts), M, V, ld, topk,
                                                 int(ignore_index), _stream()), f"classify_metrics[M={M},V={V},ld={ld},topk={topk}]")
     return loss_row[:M], rank[:M]
+
+
+# ------------------------------------------------------------------------------------------ tokenizer evaluation
+RECON_METRICS_MAX_DIM = _H["VITAMD_RECON_METRICS_MAX_DIM"]
+CODE_HIST_MAX_K = _H["VITAMD_CODE_HIST_MAX_K"]
+CODE_HIST_MAX_M = _H["VITAMD_CODE_HIST_MAX_M"]
+
+
+def recon_metrics_tile():
+    """the side of the square tiles one workgroup of vitamd_recon_metrics owns (asked of the library)"""
+    return int(_L().vitamd_recon_metrics_tile())
+
+
+def recon_metrics_grid_cap():
+    """workgroups the first launch of vitamd_recon_metrics has at most; more tiles make it loop"""
+    return int(_L().vitamd_recon_metrics_grid_cap())
+
+
+def recon_metrics_ws_bytes(B, C, H, W, ssim=True):
+    """bytes of the workspace one call needs (three fp32 partial sums per tile); a refused shape raises"""
+    n = int(_L().vitamd_recon_metrics_ws_bytes(int(B), int(C), int(H), int(W), int(bool(ssim))))
+    if n < 0:
+        _lib.check(-n, f"recon_metrics_ws_bytes[B={B},C={C},H={H},W={W},ssim={int(bool(ssim))}]")
+    return n
+
+
+def code_hist_lds_max_k():
+    """the largest codebook vitamd_code_hist counts in LDS; above it the kernel uses global atomics directly"""
+    return int(_L().vitamd_code_hist_lds_max_k())
+
+
+def code_hist_grid_cap():
+    return int(_L().vitamd_code_hist_grid_cap())
+
+
+def recon_metrics(recon, target, sums, count, per_image=None, ws=None, data_range=1.0, clamp=False, ssim=True):
+    """One validation batch of image pairs, added to accumulators on the device (include/vitamd_eval.h vitamd_recon_metrics): recon fp32 / bf16
+    [B, C, H, W] against target fp32 [B, C, H, W], both contiguous (a view that starts off 16-byte alignment is read element by
+    element).  sums fp64 [4] += the sums over the batch of the per-image mse, mae, psnr and ssim; count int64 [1] += B.  per_image fp64
+    [>= B, 4] and ws (any dtype, >= recon_metrics_ws_bytes bytes): scratch, None = zeros of this call's own.  clamp limits recon to
+    [0, data_range] first (a NaN stays); ssim=False skips the windows (H, W >= 1 suffice; the ssim fields are NaN).  Nothing
+    synchronises and nothing is read back.  -> per_image[:B] = (mse_b, mae_b, psnr_b, ssim_b)."""
+    if isinstance(data_range, bool) or not isinstance(data_range, (int, float)) or not 0.0 < float(data_range) <= 3.0e38:
+        raise ValueError(f"recon_metrics: data_range must be a finite number above 0, got {data_range!r}")
+    if not isinstance(clamp, (bool, int)) or not isinstance(ssim, (bool, int)) or clamp not in (0, 1) or ssim not in (0, 1):
+        raise ValueError(f"recon_metrics: clamp and ssim are flags (0 / 1), got {clamp!r}, {ssim!r}")
+    if not isinstance(recon, torch.Tensor) or recon.dtype not in (F32, BF16):
+        raise _lib.VitamdError(f"recon: expected an fp32 or bf16 tensor [B, C, H, W], got {getattr(recon, 'dtype', type(recon).__name__)}")
+    _need(recon, recon.dtype, "recon", 4)
+    _need(target, F32, "target", 4)
+    if recon.shape != target.shape:
+        raise _lib.VitamdError(f"recon_metrics: recon {tuple(recon.shape)} and target {tuple(target.shape)} differ in shape")
+    B, C, H, W = (int(v) for v in recon.shape)
+    lo = 11 if ssim else 1
+    if B < 1 or C < 1 or H < lo or W < lo or H > RECON_METRICS_MAX_DIM or W > RECON_METRICS_MAX_DIM:
+        raise _lib.VitamdError(f"recon_metrics: shape {tuple(recon.shape)} needs B, C >= 1 and {lo} <= H, W <= {RECON_METRICS_MAX_DIM}"
+                               f"{' (an 11 x 11 window must fit)' if ssim else ''}")
+    _need(sums, torch.float64, "sums", 1); _need(count, torch.int64, "count", 1)
+    if sums.numel() != 4 or count.numel() != 1:
+        raise _lib.VitamdError("recon_metrics: expected sums fp64 [4] and count int64 [1]")
+    with torch.cuda.device(recon.device):
+        need = recon_metrics_ws_bytes(B, C, H, W, ssim)
+        if per_image is None:
+            per_image = torch.zeros((B, 4), dtype=torch.float64, device=recon.device)
+        if ws is None:
+            ws = torch.zeros((need // 4,), dtype=F32, device=recon.device)
+        _need(per_image, torch.float64, "per_image", 2)
+        if per_image.shape[0] < B or per_image.shape[1] != 4:
+            raise _lib.VitamdError(f"recon_metrics: per_image must be fp64 [>= {B}, 4], got {tuple(per_image.shape)}")
+        if not isinstance(ws, torch.Tensor) or not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
+            raise _lib.VitamdError(f"recon_metrics: ws must be a contiguous device tensor of at least {need} bytes")
+        if any(t.device != recon.device for t in (target, sums, count, per_image, ws)):
+            raise _lib.VitamdError("recon_metrics: recon, target, the accumulators and the scratch must be on one device")
+        _lib.check(_L().vitamd_recon_metrics(_p(recon), int(recon.dtype == BF16), _p(target), _p(per_image), _p(sums), _p(count), _p(ws),
+                                             ws.numel() * ws.element_size(), B, C, H, W, float(data_range), int(clamp), int(ssim), _stream()),
+                   f"recon_metrics[B={B},C={C},H={H},W={W},clamp={int(clamp)},ssim={int(ssim)}]")
+    return per_image[:B]
+
+
+def code_hist(ids, hist, bad):
+    """hist int64 [K] += the occurrences of every id of ids (int64, any shape, contiguous) in [0, K); bad int64 [1] += the ids outside
+    that range, which form no address (include/vitamd_eval.h vitamd_code_hist).  Integer atomics: exact and reproducible.  Returns nothing."""
+    K = hist.numel() if isinstance(hist, torch.Tensor) else None
+    if K is not None and not 2 <= K <= CODE_HIST_MAX_K:
+        raise ValueError(f"code_hist: the codebook must hold 2 .. {CODE_HIST_MAX_K} codes, got {K}")
+    _need(ids, torch.int64, "ids")
+    _need(hist, torch.int64, "hist", 1); _need(bad, torch.int64, "bad", 1)
+    M = ids.numel()
+    if not 1 <= M <= CODE_HIST_MAX_M or bad.numel() != 1:
+        raise _lib.VitamdError(f"code_hist: expected 1 .. {CODE_HIST_MAX_M} ids and bad int64 [1], got {M} ids and bad {tuple(bad.shape)}")
+    if hist.device != ids.device or bad.device != ids.device:
+        raise _lib.VitamdError("code_hist: ids, hist and bad must be on one device")
+    with torch.cuda.device(ids.device):
+        _lib.check(_L().vitamd_code_hist(_p(ids), M, K, _p(hist), _p(bad), _stream()), f"code_hist[M={M},K={K}]")
